@@ -4,7 +4,7 @@ of models.ctrgcn.Model on the N-UCLA joint stream (20 joints x 64 frames), BASEL
 configs[1]: batch 256 per GPU, synthetic U(-1,1) clips, seeded init (de-degenerated so
 every branch of the block does real work).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config ucla|4stream]
+    python bench.py [--gpus N --steps K --warmup W] [--config ucla|4stream] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no launcher environment starts N fresh rank processes itself
@@ -16,7 +16,9 @@ and stream, ONE concatenated gradient bucket (4 x 6.77 MB) and one all-reduce pe
 One rank per GPU; the clip batch is sharded (weak scaling: 256 clips per GPU), gradients
 are averaged with ONE flat-bucket RCCL all-reduce (6.77 MB) per step.  The step is
 captured into a HIP graph (fwd+bwd, then the optimiser) and replayed; rank 0 prints one
-JSON line.  Besides the throughput it reports
+JSON line.  A plain run sets up, warms up, times K steps, writes the last step's outputs (--dump-outputs DIR) and
+prints that line.  With --full it then also reports
+  the step in the other GEMM mode (re-captured, a few replays; not with --single-mode);
   roofline     — the kernel with the largest share of the step, timed live with HIP events
                  around each of its launches during instrumented (eager) steps;
   cpu_baseline — the CPU oracle (stock-PyTorch restatement of the reference) on the box's
@@ -334,6 +336,28 @@ UCLA_BONE_PARENT = [1, 2, 2, 2, 2, 4, 5, 6, 2, 8, 9, 10, 0, 12, 13, 14, 0, 16, 1
 STREAMS = ('joint', 'bone', 'motion', 'bone_motion')
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(d, models, arena, bucket, loss):
+    """--dump-outputs: what a caller of the timed step holds after its last step, as float32 DIR/<name>.npy --
+    loss (shape (1,): the step's mean loss over the streams), grads (the all-reduced flat gradient bucket), params (the flat
+    parameter arena after the SGD update, alignment padding included) and bn_stats (every floating-point buffer of the
+    model(s) in named_buffers order: the BatchNorm running means and variances).  The inputs are seeded, so two builds
+    run with the same arguments can be compared array for array.  Whole arrays, 55 MB at most (--config 4stream: parameters
+    and gradients of four 6.8 MB arenas)."""
+    import numpy as np
+    arrays = dict(loss=loss.reshape(1), grads=bucket.flat, params=arena.flat,
+                  bn_stats=torch.cat([b.reshape(-1) for b in models.buffers() if b.is_floating_point()]))
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}')
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + '.npy'), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -378,7 +402,14 @@ def main():
                          "(tamgcn_set_split_mode(0)); 'split' = backward weight-gradient and C>=128 data-gradient GEMMs as a 2-term "
                          "bf16 split (mode 1; the line's dtype says so) -- for profiling that mode on its own")
     ap.add_argument('--single-mode', action='store_true',
-                    help='do not measure the other GEMM mode beside the headline (one rocprofv3 stats file per mode: tools/profile_round.sh)')
+                    help='--full: do not measure the other GEMM mode beside the headline (one rocprofv3 stats file per mode: '
+                         'tools/profile_round.sh)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure the other GEMM mode, the per-kernel roofline (instrumented eager '
+                         'steps) and the CPU baseline; a plain run does only what the headline needs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32): the step's loss, the gradient "
+                         'bucket, the parameters after the SGD step and the BatchNorm running statistics')
     args = ap.parse_args()
 
     # TAMGCN_BENCH_REHEARSAL=1: the multi-rank CONTROL FLOW (spawn, rendezvous, broadcast, step, one flat all-reduce, flat SGD,
@@ -414,12 +445,14 @@ def main():
     if args.overlap_allreduce > 1:
         args.no_graph = True
     from tam_gcn_amd.models.ctrgcn import Model
-    probe = None
+    probe = lib = None
     if not rehearsal:
         from tam_gcn_amd import _lib
-        probe = _Probe(_lib.load())
-        _lib._lib = probe                                 # every ABI launch goes through the probe
-        probe._lib.tamgcn_set_split_mode(0 if args.gemm_mode == 'exact' else 1)
+        lib = _lib.load()
+        if args.full:
+            probe = _Probe(lib)
+            _lib._lib = probe                             # every ABI launch goes through the probe
+        lib.tamgcn_set_split_mode(0 if args.gemm_mode == 'exact' else 1)
 
     four = args.config == '4stream'
     B = args.batch or (128 if four else PER_GPU_BATCH)
@@ -563,15 +596,17 @@ def main():
         dt = float(tt)
     final_loss = float(loss_buf)
     _log(f'timed {args.steps} steps in {dt:.3f}s ({mode})')
+    if args.dump_outputs and rank == 0:
+        # before anything below runs more steps on the same parameters
+        dump_outputs(args.dump_outputs, models, arena, bucket, loss_buf)
+        _log(f'outputs of the last timed step written to {args.dump_outputs}')
 
     out = None
     roof, shares, layer_rows, ms_other = None, {}, [], None
-    split = 0
-    if not rehearsal:
+    split = 0 if rehearsal else lib.tamgcn_get_split_mode()
+    if args.full and not rehearsal:
         # the same step in the OTHER GEMM mode, re-captured, a few replays: reported beside the headline (exact fp32 by
         # default; the other mode is then the 2-term bf16 split in the backward GEMMs) under its own keys
-        lib = probe._lib
-        split = lib.tamgcn_get_split_mode()
         if world == 1 and not args.single_mode:
             lib.tamgcn_set_split_mode(1 - split)
             try:
@@ -597,7 +632,7 @@ def main():
             finally:
                 lib.tamgcn_set_split_mode(split)
             _log(f'GEMM mode {1 - split} step: {ms_other:.2f} ms')
-    if not rehearsal:
+    if args.full and not rehearsal:
         # Per-kernel durations for the roofline: the same step, launched eagerly on ONE stream, HIP events around every ABI
         # launch.  (With the side streams on, kernels overlap and an event pair measures the overlap, not the kernel:
         # rocprofv3 --kernel-trace of that mode reports the same inflated durations.)
@@ -610,9 +645,10 @@ def main():
             roof, shares = roofline_of(agg)
             layer_rows = ctrgc_layer_table(layers)
     if rank == 0:
-        if args.no_cpu_baseline or world > 1 or rehearsal:
+        if not args.full or args.no_cpu_baseline or world > 1 or rehearsal:
             cpu = None
-            cpu_why = ('--no-cpu-baseline' if args.no_cpu_baseline else 'rehearsal' if rehearsal else
+            cpu_why = ('measured with --full only' if not args.full else '--no-cpu-baseline' if args.no_cpu_baseline else
+                       'rehearsal' if rehearsal else
                        'timed on rank 0 of the N = 1 run only (the host cores are shared by the N ranks here)')
         else:
             cpu, cpu_why = cpu_baseline(), None
@@ -626,7 +662,9 @@ def main():
             'value': None if rehearsal else clips / dt, 'unit': 'clips/s', 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': 1e3 * dt / args.steps, 'higher_is_better': True,
             'scaling': 'weak', 'vs_baseline': None, 'dtype': DTYPES[split], 'gemm_mode': split,
-            # the other GEMM mode, measured in the same run (null with --single-mode or N > 1): never the headline
+            # the other GEMM mode, measured in the same run with --full (null without it, with --single-mode or N > 1): never
+            # the headline.  roofline, cpu_baseline, ctrgc_fwd_layers and abi_ms_per_2_steps are --full figures as well
+            'full': args.full,
             f'ms_per_step_{other}': ms_other,
             f'value_{other}': None if (ms_other is None or rehearsal) else world * B * len(streams) / (ms_other * 1e-3),
             f'dtype_{other}': DTYPES[1 - split],

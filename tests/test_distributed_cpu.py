@@ -145,7 +145,9 @@ def _model_worker(rank, world, port, out):
     fill_state_(m.state_dict(), seed=50 + rank)              # replicas start different on purpose
     arena = ParamArena(m)
     broadcast_state(m, src=0, arena=arena)                    # ONE broadcast of the arena + one per dtype of packed buffers
-    out[f's{rank}'] = {k: v.clone() for k, v in m.state_dict().items()}
+    # as numpy arrays (pickled by value): a torch tensor crosses the manager as one shared-memory file descriptor per
+    # storage, and the ~700 state tensors of two ranks exceed a default 1024-descriptor limit
+    out[f's{rank}'] = {k: v.numpy().copy() for k, v in m.state_dict().items()}
     bucket = arena.grad_bucket()
     opt = SGDNesterov(arena.params, lr=0.01, momentum=0.9, weight_decay=1e-4, arena=arena, bucket=bucket)
     n_global = 8
@@ -179,7 +181,7 @@ def test_two_rank_real_model_arena_uneven_shards():
     ref = Model(**_MARGS)                                       # the packed broadcast delivered rank 0's whole state: parameters,
     fill_state_(ref.state_dict(), seed=50)                      # running statistics, num_batches_tracked counters
     for r in (0, 1):
-        st = out[f's{r}']
+        st = {k: torch.from_numpy(a) for k, a in out[f's{r}'].items()}
         assert list(st.keys()) == list(ref.state_dict().keys())
         assert all(torch.equal(st[k], v) and st[k].dtype == v.dtype for k, v in ref.state_dict().items())
     # single-process emulation: per-shard gradients (per-replica BatchNorm statistics, as nn.DataParallel computes them)
@@ -241,6 +243,26 @@ def test_bench_self_launches_two_ranks_rehearsal():
     r2 = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2'], env=env2, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, timeout=600)
     assert r2.returncode != 0 and b'WORLD_SIZE=1' in r2.stderr
+
+
+def test_bench_dump_outputs_rehearsal(tmp_path):
+    """A plain run (no --full) with --dump-outputs: one JSON line without the --full figures, and the last timed step's
+    loss, gradient bucket, parameter arena and BatchNorm statistics as float32 .npy files."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    env['TAMGCN_BENCH_REHEARSAL'] = '1'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                        '--dump-outputs', str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    js = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+    assert js['steps'] == 2 and js['full'] is False and js['roofline'] is None and js['cpu_baseline'] is None
+    out = {name: np.load(tmp_path / (name + '.npy')) for name in ('loss', 'grads', 'params', 'bn_stats')}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in out.values())
+    assert out['loss'].shape == (1,) and out['grads'].shape == out['params'].shape and out['bn_stats'].size > 0
 
 
 def _segment_worker(rank, world, port, out):

@@ -64,35 +64,45 @@ def test_cpu_tensor_fails_loudly():
         m(torch.zeros(1, 3, 8, 20, 1))
 
 
+def _state64(m):
+    """The model's state as the reference's fp64 fixture runs start from it: the fp32 values in float64."""
+    return O.clone_state({k: (v.double() if v.is_floating_point() else v) for k, v in m.state_dict().items()}, requires_grad=True)
+
+
 @pytest.mark.parametrize('case', [MODEL_CASES[0], MODEL_CASES[3]], ids=lambda c: c[0])
 def test_oracle_model_vs_golden(case, golden_models):
+    """The train step (fwd + CE + bwd) in fp64 against the reference's fp64 run ('...64' keys): in fp32 the
+    train-mode batch statistics and near-zero ReLU decisions turn the host's own rounding (its SIMD kernels, its thread
+    count) into differences above these tolerances, so an fp32 comparison holds only on the host that wrote the fixtures.
+    The eval forward, free of that coupling, stays in fp32 against the fp32 run."""
     tag, margs, shape = case
     gold = golden_models
     m = M.Model(**margs)
     fill_state_(m.state_dict(), seed=MODEL_PARAM_SEED)
-    sd = O.clone_state(m.state_dict(), requires_grad=True)
-    x = make_input(shape, seed=MODEL_X_SEED).requires_grad_(True)
+    sd = _state64(m)
+    x = make_input(shape, seed=MODEL_X_SEED).double().requires_grad_(True)
     lab = make_labels(shape[0], margs['num_class'], seed=MODEL_LABEL_SEED)
     logits = O.model_forward(x, sd, margs['num_point'], training=True)
     loss = torch.nn.functional.cross_entropy(logits, lab)
     loss.backward()
-    np.testing.assert_allclose(logits.detach().numpy(), gold[f'{tag}/logits_train'], rtol=1e-3, atol=1e-3)
-    assert np.array_equal(logits.detach().numpy().argmax(1), gold[f'{tag}/logits_train'].argmax(1))
-    np.testing.assert_allclose(float(loss.detach()), float(gold[f'{tag}/loss']), rtol=1e-4)
-    np.testing.assert_allclose(x.grad.numpy(), gold[f'{tag}/dx'], rtol=5e-3, atol=1e-6)
+    np.testing.assert_allclose(logits.detach().numpy(), gold[f'{tag}/logits_train64'], rtol=1e-3, atol=1e-3)
+    assert np.array_equal(logits.detach().numpy().argmax(1), gold[f'{tag}/logits_train64'].argmax(1))
+    np.testing.assert_allclose(float(loss.detach()), float(gold[f'{tag}/loss64']), rtol=1e-4)
+    np.testing.assert_allclose(x.grad.numpy(), gold[f'{tag}/dx64'], rtol=5e-3, atol=1e-6)
     pkeys = list(gold[f'{tag}/param_keys'])
-    gd = gold[f'{tag}/grad_digest']
+    gd = gold[f'{tag}/grad_digest64']
     for i, k in enumerate(pkeys):
         g = digest(sd[k].grad)
         tol = 5e-3 * abs(gd[i][1]) + 1e-6
         assert abs(g[0] - gd[i][0]) <= tol and abs(g[1] - gd[i][1]) <= tol, k
     bkeys = list(gold[f'{tag}/buf_keys'])
-    bd = gold[f'{tag}/buf_digest']
+    bd = gold[f'{tag}/buf_digest64']
     for i, k in enumerate(bkeys):
         g = digest(sd[k])
         assert abs(g[1] - bd[i][1]) <= 1e-4 * abs(bd[i][1]) + 1e-6, k
+    x = x.detach().float()
     with torch.no_grad():
-        sde = {k: v.detach() for k, v in sd.items()}
+        sde = O.clone_state(m.state_dict())          # the train step changed no parameter; its running statistics are replaced
         for k in list(sde):
             if 'running_' in k:
                 sde[k] = torch.from_numpy(gold[f'{tag}/evalbuf/{k}'])
@@ -113,26 +123,28 @@ def test_oracle_model_vs_golden(case, golden_models):
 def test_harness_sgd_steps_oracle(fix, golden_models):
     """three steps of the harness recipe (SGD momentum 0.9, nesterov, wd 1e-4 + CE, reference
     processor/recognition_rgb.py:19-28) captured from the reference model: the oracle under torch.optim.SGD reproduces
-    the losses and the final state (parameters, running statistics, num_batches_tracked)."""
+    the losses and the final state (parameters, running statistics, num_batches_tracked).  In fp64 against the reference's
+    fp64 run: three steps (one of them divergent, 'sgd3') carry the host's fp32 rounding into per-cent differences
+    (test_oracle_model_vs_golden)."""
     from cases import SGD_CASES
     lr, nb, nt = SGD_CASES[fix]
     margs = MODEL_CASES[0][1]
     m = M.Model(**margs)
     fill_state_(m.state_dict(), seed=43)
-    sd = O.clone_state(m.state_dict(), requires_grad=True)
+    sd = _state64(m)
     params = [v for v in sd.values() if v.requires_grad]
     opt = torch.optim.SGD(params, lr=lr, momentum=0.9, nesterov=True, weight_decay=1e-4)
     losses = []
     for step in range(3):
-        x = make_input((nb, 3, nt, 20, 1), seed=100 + step)
+        x = make_input((nb, 3, nt, 20, 1), seed=100 + step).double()
         lab = make_labels(nb, 10, seed=200 + step)
         opt.zero_grad()
         loss = torch.nn.functional.cross_entropy(O.model_forward(x, sd, 20, training=True), lab)
         loss.backward()
         opt.step()
         losses.append(float(loss.detach()))
-    np.testing.assert_allclose(losses, golden_models[f'{fix}/losses'], rtol=2e-5, atol=2e-6)
+    np.testing.assert_allclose(losses, golden_models[f'{fix}/losses64'], rtol=2e-5, atol=2e-6)
     assert list(sd.keys()) == [str(k) for k in golden_models[f'{fix}/keys']]
     got = np.stack([digest(v) for v in sd.values()])
-    ref = golden_models[f'{fix}/state_digest']
+    ref = golden_models[f'{fix}/state_digest64']
     np.testing.assert_allclose(got[:, 1], ref[:, 1], rtol=2e-4, atol=1e-5)        # sum |.| of every state tensor

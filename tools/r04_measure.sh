@@ -17,7 +17,7 @@ if [ "$WHAT" = configs ] || [ "$WHAT" = all ]; then
     TAMGCN_SPLIT_BF16=$m timeout -k 10 200 python tools/config_bench.py ucla52 2>/dev/null | tail -1 > $O/${TAG}_config1_ucla52_mode$m.json
   done
   timeout -k 10 300 python tools/config_bench.py syn 256 2>/dev/null | tail -1 > $O/${TAG}_config4_syn256_mode0.json
-  timeout -k 10 300 python bench.py --config 4stream --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_config2_4stream.json
+  timeout -k 10 300 python bench.py --full --config 4stream --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_config2_4stream.json
   for f in $O/${TAG}_config*.json; do echo "$f: $(cut -c1-200 $f)"; done
   bash tools/pmc_kernel.sh ctrgc64 python3 tools/kctrgc_only.py 64 64 64 > $O/${TAG}_pmc_ctrgc_64_64_T64.txt 2>&1
   bash tools/pmc_kernel.sh ctrgc256 python3 tools/kctrgc_only.py 256 256 16 > $O/${TAG}_pmc_ctrgc_256_256_T16.txt 2>&1
