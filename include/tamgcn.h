@@ -478,6 +478,32 @@ typedef struct tamgcn_f2_tcn_desc {
 } tamgcn_f2_tcn_desc;
 int tamgcn_f2_tcn(const tamgcn_f2_tcn_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Optimiser update in place over flat fp32 buffers of n elements (a ParamArena and its FlatGradBucket):
+ *   mode 0  torch.optim.SGD (foreach=False):  d = g + wd p;  with momentum m > 0:  s0 = d on the first step, else
+ *           s0 = m s0 + (1 - dampening) d;  d = nesterov ? d + m s0 : s0;  p -= lr d
+ *   mode 1  torch.optim.Adam (coupled L2 weight decay, no amsgrad):  g += wd p;  s0 = b1 s0 + (1 - b1) g;
+ *           s1 = b2 s1 + (1 - b2) g^2;  p -= (lr / (1 - b1^t)) s0 / (sqrt(s1) / sqrt(1 - b2^t) + eps)
+ * The learning rate (*lr) and the step count (*step, int32, 0 before the first call) are read on the device, and *step
+ * advances by one per call on the device: a HIP graph holding this call sees a changed *lr and counts its own replays.
+ * scal: 2 floats of scratch (this step's scalars, written by a one-thread launch before the update).  p, g, s0 and s1
+ * must be 16-byte aligned; s0 may be NULL for SGD without momentum, s1 is NULL for SGD.  Two launches.
+ * Added in ABI 401 without a version bump: a new entry point, no existing layout or semantics changed. */
+typedef struct tamgcn_optim_desc {
+    long long n;
+    float* p; const float* g;
+    float* s0;                                       /* SGD momentum buffer | Adam exp_avg */
+    float* s1;                                       /* Adam exp_avg_sq | NULL */
+    const float* lr;                                 /* [1] */
+    int* step;                                       /* [1] */
+    float* scal;                                     /* [2] scratch */
+    int mode;                                        /* 0 SGD, 1 Adam */
+    int nesterov;
+    float momentum, dampening, weight_decay, eps;
+    double beta1, beta2;
+} tamgcn_optim_desc;
+int tamgcn_optim_step(const tamgcn_optim_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

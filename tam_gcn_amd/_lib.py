@@ -96,6 +96,15 @@ class F2TcnDesc(C.Structure):
                [(k, C.c_void_p) for k in ('sp', 'tp', 'x', 'wr', 'br', 'out', 'xpart')]
 
 
+class OptimDesc(C.Structure):
+    _fields_ = [('n', C.c_longlong),
+                ('p', C.c_void_p), ('g', C.c_void_p), ('s0', C.c_void_p), ('s1', C.c_void_p),
+                ('lr', C.c_void_p), ('step', C.c_void_p), ('scal', C.c_void_p),
+                ('mode', C.c_int), ('nesterov', C.c_int),
+                ('momentum', C.c_float), ('dampening', C.c_float), ('weight_decay', C.c_float), ('eps', C.c_float),
+                ('beta1', C.c_double), ('beta2', C.c_double)]
+
+
 # name -> (restype, argtypes); must list every symbol of include/tamgcn.h
 _i, _p, _d, _f, _ll = C.c_int, C.c_void_p, C.c_double, C.c_float, C.c_longlong
 _SP = C.POINTER(Src)
@@ -161,6 +170,7 @@ SIGNATURES = {
     'tamgcn_f2_gcn': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2_gemm': (_i, [C.POINTER(F2GemmDesc), _p]),
     'tamgcn_f2_tcn': (_i, [C.POINTER(F2TcnDesc), _p]),
+    'tamgcn_optim_step': (_i, [C.POINTER(OptimDesc), _p]),
 }
 
 

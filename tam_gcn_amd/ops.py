@@ -821,3 +821,22 @@ def ce_bwd(g, dloss):
     dl = torch.empty_like(g)
     _lib.check(_lib_().tamgcn_ce_bwd(_ptr(g), _ptr(dloss), N, K, _ptr(dl), _stream()), 'tamgcn_ce_bwd')
     return dl
+
+
+def optim_step(p, g, s0, s1, lr, step, scal, mode, momentum=0.0, dampening=0.0, nesterov=False, weight_decay=0.0,
+               beta1=0.9, beta2=0.999, eps=1e-8):
+    """One in-place SGD (mode 0) or Adam (mode 1) update of the flat fp32 buffer p from g (tamgcn_optim_step).
+    lr: (1,) fp32 and step: (1,) int32 device tensors, read (and step advanced) on the device; scal: (2,) fp32 scratch."""
+    for name, t in (('p', p), ('g', g), ('s0', s0), ('s1', s1), ('scal', scal)):
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError(f'tam_gcn_amd.optim_step: {name} must be fp32')
+    if lr.dtype != torch.float32 or step.dtype != torch.int32:
+        raise RuntimeError('tam_gcn_amd.optim_step: lr must be fp32 and step int32')
+    if lr.numel() < 1 or step.numel() < 1 or scal.numel() < 2:
+        raise RuntimeError('tam_gcn_amd.optim_step: lr and step need 1 element, scal 2')
+    if g.numel() != p.numel() or any(t is not None and t.numel() != p.numel() for t in (s0, s1)):
+        raise RuntimeError('tam_gcn_amd.optim_step: p, g and the state buffers differ in size')
+    d = _lib.OptimDesc(p.numel(), _ptr(p), _ptr(g), _ptr(s0), _ptr(s1), _ptr(lr), _ptr(step), _ptr(scal),
+                       int(mode), int(bool(nesterov)), float(momentum), float(dampening), float(weight_decay), float(eps),
+                       float(beta1), float(beta2))
+    _lib.check(_lib_().tamgcn_optim_step(C.byref(d), _stream()), 'tamgcn_optim_step')
