@@ -18,6 +18,44 @@ from oracle import ctrgcn_oracle as O                                # noqa: E40
 A_BY_V = {20: ucla.Graph().A, 25: ntu_rgb_d.Graph().A, 64: synthetic.Graph().A}
 
 
+class KernelRecorder:
+    """Proxy around the ctypes library (as bench.py's _Probe): after every launching tamgcn_* call it records
+    (ABI name, tamgcn_last_kernel()).  Query entry points pass through unrecorded."""
+    QUERIES = ('tamgcn_last_error', 'tamgcn_last_kernel', 'tamgcn_version', 'tamgcn_conv_nparts', 'tamgcn_tconv_supported',
+               'tamgcn_tconv_nparts', 'tamgcn_tconv_wgrad_max_split', 'tamgcn_ew_nparts', 'tamgcn_ctrgc_lds_bytes',
+               'tamgcn_get_split_mode', 'tamgcn_set_split_mode', 'tamgcn_wgrad_max_split', 'tamgcn_ctrgc_tiled_supported',
+               'tamgcn_ctrgc_tiled_chunks')
+
+    def __init__(self, lib):
+        self._lib, self.seen = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith('tamgcn_') or name in self.QUERIES:
+            return fn
+
+        def wrapped(*args):
+            rc = fn(*args)
+            self.seen.append((name, self._lib.tamgcn_last_kernel().decode()))
+            return rc
+        return wrapped
+
+
+class record_kernels:
+    """with record_kernels() as rec: every ABI launch made through tam_gcn_amd._lib.load() lands in rec.seen."""
+
+    def __enter__(self):
+        from tam_gcn_amd import _lib
+        self.mod, self.lib = _lib, _lib.load()
+        self.rec = KernelRecorder(self.lib)
+        _lib._lib = self.rec
+        return self.rec
+
+    def __exit__(self, *exc):
+        self.mod._lib = self.lib
+        return False
+
+
 def build_module(kind, kw, V):
     cls = getattr(M, kind)
     if kind in NEEDS_A:
