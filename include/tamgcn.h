@@ -504,6 +504,29 @@ typedef struct tamgcn_optim_desc {
 } tamgcn_optim_desc;
 int tamgcn_optim_step(const tamgcn_optim_desc* d, void* stream);
 
+/* The same update behind a gradient guard (three launches, still no host sync):
+ *   norm = sqrt(sum g[i]^2) over the n elements of d->g, every square and the whole sum in fp64, reduced in a fixed shape
+ *          (one partial per workgroup, then one workgroup adds the partials in order; no floating-point atomics): two
+ *          calls on the same buffer give the same bits.
+ *   coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1, in fp32 (torch.nn.utils.clip_grad_norm_); the update
+ *          uses g * coef, applied before the weight-decay term.  d->g itself is NOT rewritten.  With coef == 1 and a
+ *          finite sum, p, s0, s1 and *step end bit-identical to tamgcn_optim_step.
+ *   finite = isfinite(sum g^2).  With skip_nonfinite and a non-finite sum the call leaves p, s0, s1, *step and scal
+ *          untouched and adds one to *skipped; without skip_nonfinite the non-finite values propagate as in torch
+ *          (error_if_nonfinite=False).
+ * partial: n_partial doubles of scratch, 8-byte aligned, at least one per workgroup of the reduction (2048 always
+ * suffices).  stat: 3 floats out: norm before clipping, coefficient applied, 1 / 0 for finite.  skipped: device counter,
+ * may be NULL when skip_nonfinite is 0.  Added in ABI 401 without a version bump: a new entry point. */
+typedef struct tamgcn_grad_guard {
+    float max_norm;                                  /* > 0: clip to this L2 norm; <= 0: measure only */
+    int skip_nonfinite;
+    double* partial;                                 /* [n_partial] scratch */
+    int n_partial;
+    float* stat;                                     /* [3] out */
+    int* skipped;                                    /* [1] */
+} tamgcn_grad_guard;
+int tamgcn_optim_step_guarded(const tamgcn_optim_desc* d, const tamgcn_grad_guard* g, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,11 @@ class OptimDesc(C.Structure):
                 ('beta1', C.c_double), ('beta2', C.c_double)]
 
 
+class GradGuard(C.Structure):
+    _fields_ = [('max_norm', C.c_float), ('skip_nonfinite', C.c_int), ('partial', C.c_void_p), ('n_partial', C.c_int),
+                ('stat', C.c_void_p), ('skipped', C.c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol of include/tamgcn.h
 _i, _p, _d, _f, _ll = C.c_int, C.c_void_p, C.c_double, C.c_float, C.c_longlong
 _SP = C.POINTER(Src)
@@ -171,6 +176,7 @@ SIGNATURES = {
     'tamgcn_f2_gemm': (_i, [C.POINTER(F2GemmDesc), _p]),
     'tamgcn_f2_tcn': (_i, [C.POINTER(F2TcnDesc), _p]),
     'tamgcn_optim_step': (_i, [C.POINTER(OptimDesc), _p]),
+    'tamgcn_optim_step_guarded': (_i, [C.POINTER(OptimDesc), C.POINTER(GradGuard), _p]),
 }
 
 

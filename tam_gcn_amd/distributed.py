@@ -115,7 +115,18 @@ class FlatGradBucket:
         for p in self.params:
             p.grad = None
 
-    def pack(self):
+    def pack(self, accumulate=False, alpha=1.0):
+        """Gathers the parameters' gradients into the bucket and re-points ``p.grad`` at the bucket's views.
+        ``accumulate=True`` adds ``alpha * p.grad`` to what the bucket holds instead of overwriting it (gradient
+        accumulation over micro-batches: ``alpha = 1 / k``, and the caller zeroes ``flat`` before the first of the k);
+        a parameter without a gradient, or whose ``p.grad`` is still the bucket's own view, contributes nothing."""
+        if accumulate:
+            pairs = [(v, p.grad) for p, v in zip(self.params, self.views) if p.grad is not None and p.grad is not v]
+            if pairs:
+                torch._foreach_add_([v for v, _ in pairs], [g for _, g in pairs], alpha=alpha)
+            for p, v in zip(self.params, self.views):
+                p.grad = v
+            return self.flat
         grads = [p.grad for p in self.params]
         if any(g is None for g in grads):                  # parameter unused this step
             self.flat.zero_()

@@ -823,20 +823,42 @@ def ce_bwd(g, dloss):
     return dl
 
 
+def _optim_desc(fn, p, g, s0, s1, lr, step, scal, mode, momentum, dampening, nesterov, weight_decay, beta1, beta2, eps):
+    for name, t in (('p', p), ('g', g), ('s0', s0), ('s1', s1), ('scal', scal)):
+        if t is not None and t.dtype != torch.float32:
+            raise RuntimeError(f'tam_gcn_amd.{fn}: {name} must be fp32')
+    if lr.dtype != torch.float32 or step.dtype != torch.int32:
+        raise RuntimeError(f'tam_gcn_amd.{fn}: lr must be fp32 and step int32')
+    if lr.numel() < 1 or step.numel() < 1 or scal.numel() < 2:
+        raise RuntimeError(f'tam_gcn_amd.{fn}: lr and step need 1 element, scal 2')
+    if g.numel() != p.numel() or any(t is not None and t.numel() != p.numel() for t in (s0, s1)):
+        raise RuntimeError(f'tam_gcn_amd.{fn}: p, g and the state buffers differ in size')
+    return _lib.OptimDesc(p.numel(), _ptr(p), _ptr(g), _ptr(s0), _ptr(s1), _ptr(lr), _ptr(step), _ptr(scal),
+                          int(mode), int(bool(nesterov)), float(momentum), float(dampening), float(weight_decay), float(eps),
+                          float(beta1), float(beta2))
+
+
 def optim_step(p, g, s0, s1, lr, step, scal, mode, momentum=0.0, dampening=0.0, nesterov=False, weight_decay=0.0,
                beta1=0.9, beta2=0.999, eps=1e-8):
     """One in-place SGD (mode 0) or Adam (mode 1) update of the flat fp32 buffer p from g (tamgcn_optim_step).
     lr: (1,) fp32 and step: (1,) int32 device tensors, read (and step advanced) on the device; scal: (2,) fp32 scratch."""
-    for name, t in (('p', p), ('g', g), ('s0', s0), ('s1', s1), ('scal', scal)):
-        if t is not None and t.dtype != torch.float32:
-            raise RuntimeError(f'tam_gcn_amd.optim_step: {name} must be fp32')
-    if lr.dtype != torch.float32 or step.dtype != torch.int32:
-        raise RuntimeError('tam_gcn_amd.optim_step: lr must be fp32 and step int32')
-    if lr.numel() < 1 or step.numel() < 1 or scal.numel() < 2:
-        raise RuntimeError('tam_gcn_amd.optim_step: lr and step need 1 element, scal 2')
-    if g.numel() != p.numel() or any(t is not None and t.numel() != p.numel() for t in (s0, s1)):
-        raise RuntimeError('tam_gcn_amd.optim_step: p, g and the state buffers differ in size')
-    d = _lib.OptimDesc(p.numel(), _ptr(p), _ptr(g), _ptr(s0), _ptr(s1), _ptr(lr), _ptr(step), _ptr(scal),
-                       int(mode), int(bool(nesterov)), float(momentum), float(dampening), float(weight_decay), float(eps),
-                       float(beta1), float(beta2))
+    d = _optim_desc('optim_step', p, g, s0, s1, lr, step, scal, mode, momentum, dampening, nesterov, weight_decay,
+                    beta1, beta2, eps)
     _lib.check(_lib_().tamgcn_optim_step(C.byref(d), _stream()), 'tamgcn_optim_step')
+
+
+def optim_step_guarded(p, g, s0, s1, lr, step, scal, mode, partial, stat, skipped=None, max_norm=0.0, skip_nonfinite=False,
+                       momentum=0.0, dampening=0.0, nesterov=False, weight_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8):
+    """optim_step behind the gradient guard (tamgcn_optim_step_guarded): the L2 norm of g is reduced on the device in fp64,
+    the update uses g * min(1, max_norm / (norm + 1e-6)) when max_norm > 0 (g itself keeps its values), and with
+    skip_nonfinite a non-finite norm leaves p, s0, s1 and step untouched and advances skipped.
+    partial: fp64 scratch, one element per workgroup of the reduction (2048 always suffices); stat: (3,) fp32 out
+    [norm before clipping, coefficient, 1/0 finite]; skipped: (1,) int32 counter (needed with skip_nonfinite)."""
+    d = _optim_desc('optim_step_guarded', p, g, s0, s1, lr, step, scal, mode, momentum, dampening, nesterov, weight_decay,
+                    beta1, beta2, eps)
+    if partial.dtype != torch.float64 or stat.dtype != torch.float32 or stat.numel() < 3:
+        raise RuntimeError('tam_gcn_amd.optim_step_guarded: partial must be fp64, stat fp32 with 3 elements')
+    if skipped is not None and (skipped.dtype != torch.int32 or skipped.numel() < 1):
+        raise RuntimeError('tam_gcn_amd.optim_step_guarded: skipped must be int32 with 1 element')
+    gd = _lib.GradGuard(float(max_norm), int(bool(skip_nonfinite)), _ptr(partial), partial.numel(), _ptr(stat), _ptr(skipped))
+    _lib.check(_lib_().tamgcn_optim_step_guarded(C.byref(d), C.byref(gd), _stream()), 'tamgcn_optim_step_guarded')
