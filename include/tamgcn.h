@@ -422,6 +422,38 @@ int tamgcn_stream_derive(const float* x, int N, int C, int T, int V, int M, cons
 int tamgcn_feeder_transform(const double* raw, const long long* offsets, const double* rot, const int* idx, const int* parent,
                             int N, int V, int time_steps, int center_joint, int mode, float* out, void* stream);
 
+/* The same batch without the host: the train path's draws on the device and the transform reading the resident split.
+ * Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed.
+ * _feeder_draw   for B batch slots, from device memory only: offsets int64 [n_clips + 1] of the whole split, clip_ids int64
+ *                 [B] (slot b takes clip clip_ids[b] mod n_clips, Python's sign rule), state int64 [2] = (seed, call counter).
+ *                 Both words of state are READ ON THE DEVICE, so a HIP graph holding this call sees their current values.
+ *                 train = 1 (reference :88-93, :110-115, same distributions, a counter-based stream of its own):
+ *                   Philox4x32-10, key = (seed low, seed high), counter = (call low, call high, b, j);
+ *                   block j = 0 -> w0..w3: agx = -60 + mulhi(w0, 121), agy = -60 + mulhi(w1, 121),
+ *                   s = 0.5 + ((w2 >> 5) 2^26 + (w3 >> 6)) 2^-53;
+ *                   blocks j = 1 .. ceil(time_steps / 4) -> u_0 .. u_{time_steps-1}; with n = 100 L (L = the clip's length,
+ *                   position p of `list(arange(L)) * 100` holds frame p mod L) Floyd's algorithm: for i = 0 .. time_steps - 1,
+ *                   J = n - time_steps + i, t = (u_i (J + 1)) >> 32, take t unless already taken, else J; idx = the
+ *                   positions mod L, sorted ascending.  Then the counter advances by one in a one-thread launch that
+ *                   follows the draw on the stream (plain store).  cossin: fp64 [121][2] = (cos, sin) of -60 .. 60 degrees
+ *                   computed by the caller's libm, so that rot uses the host's own values.
+ *                 train = 0 (:116-118): view (0, 0, 1), rot the identity, idx = np.linspace(0, L - 1, time_steps).astype(int)
+ *                   in fp64 as numpy computes it (i * ((L - 1) / (time_steps - 1)) truncated, last element L - 1); state is
+ *                   read by nobody and does not advance; cossin may be NULL.
+ *                 Out: view fp64 [B][3] = (agx, agy, s); rot fp64 [B][9] = Ry.Rx.S row-major (each 3 x 3 product summed left
+ *                 to right); idx int32 [B][time_steps]; labels_out int64 [B] = labels[clip] when both are given (both NULL:
+ *                 no gather).  time_steps <= 64 (one lane per output frame).  Clip lengths must satisfy 1 <= L and
+ *                 100 L < 2^24 -- the lengths live on the device, so it is the caller that checks (Feeder.load_data does).
+ * _feeder_transform_indexed  _feeder_transform's arithmetic (one device body) where slot b reads clip clip_ids[b] mod n_clips
+ *                 out of the resident split (raw, offsets [n_clips + 1]) instead of clip b of a gathered copy; rot [B][9],
+ *                 idx [B][time_steps], out (B, 3, time_steps, V, 1). */
+int tamgcn_feeder_draw(const long long* offsets, long long n_clips, const long long* clip_ids, int B, const long long* labels,
+                       long long* state, const double* cossin, int time_steps, int train, double* view, double* rot, int* idx,
+                       long long* labels_out, void* stream);
+int tamgcn_feeder_transform_indexed(const double* raw, const long long* offsets, long long n_clips, const long long* clip_ids,
+                                    const double* rot, const int* idx, const int* parent, int B, int V, int time_steps,
+                                    int center_joint, int mode, float* out, void* stream);
+
 /* ---- f2: the eval-mode TCN_GCN_unit for small batches (callers: reference
  * ensemble/ensemble_ctrgcn_resnet_eval.py:147-183, models/resnet_gcn_attention.py:82-85, visual.py:53-55 -- model(data)
  * on 1..16 clips in eval mode).  Five launches per block, each 50..130 workgroups per clip; V = 20, S = 3.  The CALLER folds

@@ -18,6 +18,22 @@ Differences, stated:
     scope: ``rgb_tensor`` is the zeros tensor the reference returns when a sample has no image (:132);
   * label paths containing both 'bone' and 'motion' select the bone stream in the reference (the ``elif`` at :124); the same
     here by default, ``stream='bone_motion'`` asks for motion-of-bone explicitly (upstream CTR-GCN's fourth stream).
+
+A second way to ask for a batch, with no host work per sample: ``batch_device(indices)`` takes the sample indices as a
+tensor on the device and draws the train path's view angles, scale and 52 frames per clip in a HIP kernel
+(``tamgcn_feeder_draw``: Philox4x32-10 keyed by ``seed``, counted by a call counter that lives on the device) --
+the reference's distributions, not its Python ``random`` stream, which ``batch()`` / ``__getitem__`` keep mirroring call
+for call.  It makes no host-to-device copy and no synchronisation, so ``GraphedBatch`` can hold it in a HIP graph:
+
+    fd = Feeder(path, 'train', data_dict=split, seed=1234)          # data-parallel: seed=base + rank, see below
+    gb = GraphedBatch(fd, 256)
+    perm = torch.randperm(len(fd), device=dev)
+    for i in range(0, len(fd) - 255, 256):
+        loss = train.step(*gb(perm[i:i + 256]))                    # training.CapturedStep
+
+Slot b of call c with seed s always gets the same draws, whatever the other slots hold.  Ranks of a data-parallel run
+must pass different seeds (``seed=base + rank``): with equal seeds every rank would apply the same views to its slots.
+``rng_state()`` / ``set_rng_state()`` carry (seed, call) through a checkpoint.
 """
 import json
 import math
@@ -59,7 +75,7 @@ def view_matrix(agx, agy, s):
 class Feeder(Dataset):
     def __init__(self, data_path, label_path, repeat=1, random_choose=False, random_shift=False, random_move=False,
                  window_size=-1, normalization=False, debug=False, use_mmap=True, data_dict=None, split_file=None,
-                 device='cuda', stream=None):
+                 device='cuda', stream=None, seed=0):
         self.data_path, self.label_path = data_path, label_path
         self.train_val = 'val' if 'val' in label_path else 'train'
         if data_dict is None and split_file is not None:
@@ -77,6 +93,7 @@ class Feeder(Dataset):
             raise ValueError(f'unknown stream {stream!r}')
         self.stream = stream
         self.device = torch.device(device)
+        self.seed, self.last_draws = self._check_seed(seed, 'seed'), None
         self.load_data()
         if normalization:
             self.get_mean_map()
@@ -89,6 +106,9 @@ class Feeder(Dataset):
             with open(os.path.join(self.data_path, name, name + '.json'), 'r') as f:
                 self.data.append(np.array(json.load(f)['skeletons'], dtype=np.float64))
         lens = [len(v) for v in self.data]
+        for info, n in zip(self.data_dict, lens):               # the device-side draw indexes 100 * length positions
+            if n < 1 or 100 * n >= 2 ** 24:
+                raise ValueError(f"clip {info['file_name']!r} has {n} frames: the feeder takes 1 .. {(2 ** 24 - 1) // 100}")
         self._offsets_cpu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
         raw = np.concatenate(self.data, axis=0) if self.data else np.zeros((0, 20, 3))
         if raw.shape[1:] != (20, 3):
@@ -96,6 +116,13 @@ class Feeder(Dataset):
         # the whole split stays resident in HBM (N-UCLA: 1484 clips x ~40 frames x 60 doubles = 28 MB)
         self._raw = torch.from_numpy(np.ascontiguousarray(raw)).to(self.device)
         self._parent = torch.tensor(BONE_PARENT, dtype=torch.int32, device=self.device)
+        # what batch_device() reads, resident once: frame offsets, labels, the host libm's cos / sin of -60 .. 60 degrees
+        # (so that the device's view matrix is built from view_matrix()'s own values) and the generator state
+        self._offsets = torch.from_numpy(self._offsets_cpu).to(self.device)
+        self._labels = torch.tensor(self.label, dtype=torch.int64, device=self.device)
+        self._cossin = torch.tensor([[math.cos(math.radians(a)), math.sin(math.radians(a))] for a in range(-60, 61)],
+                                    dtype=torch.float64, device=self.device)
+        self._rng = torch.tensor([self.seed, 0], dtype=torch.int64, device=self.device)
 
     def get_mean_map(self):
         raise NotImplementedError('normalization=True: the reference computes it over a 5-D array its own loader never '
@@ -138,6 +165,52 @@ class Feeder(Dataset):
         lab = torch.tensor([self.label[i] for i in indices], dtype=torch.int64, device=self.device)
         return out, lab, indices
 
+    # ---- the same batch without the host: draws on the device, the resident split read in place --------------------
+    def batch_device(self, indices):
+        """(data (B, 3, 52, 20, 1) float32, labels (B,) int64), both on the device, for ``indices`` an int64 tensor [B] on
+        the device (taken modulo the split's size, as ``batch()`` does for ``repeat``).  Train or val by ``label_path``,
+        stream by ``stream``, exactly as ``batch()``; the train path's draws come from the device-resident generator
+        (module docstring), whose call counter moves on by one.  Three launches on the current stream, no host loop, no
+        copy from the host, no synchronisation: capturable (``GraphedBatch``).  ``last_draws`` keeps what the launch
+        drew: ``view`` (B, 3) = (agx, agy, s), ``rot`` (B, 3, 3), ``idx`` (B, 52)."""
+        if not (isinstance(indices, torch.Tensor) and indices.dtype == torch.int64 and indices.dim() == 1
+                and indices.device == self._raw.device and indices.numel() > 0):
+            raise ValueError('Feeder.batch_device: indices must be a non-empty 1-D int64 tensor on the feeder\'s device '
+                             '(batch() takes host indices)')
+        if not self.data_dict:
+            raise ValueError('Feeder.batch_device: the split is empty')
+        indices = indices.contiguous()
+        view, rot, idx, lab = ops.feeder_draw(self._offsets, indices, self._rng, self._cossin, self.time_steps,
+                                              self.train_val == 'train', labels=self._labels)
+        out = ops.feeder_transform_indexed(self._raw, self._offsets, indices, rot, idx, self._parent, 20, self.time_steps, 1,
+                                           self.stream)
+        self.last_draws = {'view': view, 'rot': rot, 'idx': idx}
+        return out, lab
+
+    @staticmethod
+    def _check_seed(v, what):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 63:
+            raise ValueError(f'Feeder: {what} = {v!r} must be an integer in [0, 2^63)')
+        return v
+
+    def manual_seed(self, seed, call=0):
+        """Write (seed, call) into the device-resident generator state on the current stream.  Graphs captured earlier
+        read the state on every replay, so this takes effect on them too."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('Feeder.manual_seed: set the seed outside graph capture (a captured write would replay '
+                               'the value of capture time)')
+        self.seed = self._check_seed(seed, 'seed')
+        self._rng.copy_(torch.tensor([self.seed, self._check_seed(call, 'call')], dtype=torch.int64))
+
+    def rng_state(self):
+        """(seed, call): the next batch_device() call draws call number ``call`` (reads the device: a host sync)."""
+        seed, call = self._rng.tolist()
+        return seed, call
+
+    def set_rng_state(self, state):
+        seed, call = state
+        self.manual_seed(int(seed), int(call))
+
     def __getitem__(self, index):
         index = index % len(self.data_dict)
         out, _, _ = self.batch([index])
@@ -148,6 +221,46 @@ class Feeder(Dataset):
         rank = score.argsort()
         hit_top_k = [l in rank[i, -top_k:] for i, l in enumerate(self.label)]
         return sum(hit_top_k) * 1.0 / len(hit_top_k)
+
+
+class GraphedBatch:
+    """One ``feeder.batch_device`` call of ``batch_size`` samples held in a HIP graph.  ``x, y = gb(indices)`` copies the
+    indices (int64 [batch_size], on the device) into the graph's input and replays it: new draws every time, because the
+    generator state is read and advanced on the device.  ``x`` and ``y`` are the graph's own output tensors, overwritten by
+    the next call (``CapturedStep.step`` copies them into its inputs); ``feeder.last_draws`` are the replay's draws.
+    Building it warms the kernels up on a side stream and puts the generator state back: it consumes no draws."""
+
+    def __init__(self, feeder, batch_size):
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            raise ValueError(f'GraphedBatch: batch_size = {batch_size!r} must be an integer >= 1')
+        self.feeder, self.batch_size = feeder, batch_size
+        dev = feeder._raw.device
+        self.indices = torch.zeros(batch_size, dtype=torch.int64, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            saved = feeder._rng.clone()
+            feeder.batch_device(self.indices)
+            feeder._rng.copy_(saved)
+        cur.wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self._graph = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(self._graph):
+                self.x, self.y = feeder.batch_device(self.indices)
+        except Exception as e:                                  # noqa: BLE001  -- no silent eager fall-back
+            raise RuntimeError(f'GraphedBatch: HIP graph capture failed ({type(e).__name__}: {e})') from e
+        self.draws = feeder.last_draws
+
+    def __call__(self, indices):
+        if not isinstance(indices, torch.Tensor) or tuple(indices.shape) != (self.batch_size,) or indices.dtype != torch.int64:
+            raise ValueError(f'GraphedBatch: indices must be an int64 tensor of {self.batch_size} elements, got '
+                             f'{tuple(getattr(indices, "shape", ()))} {getattr(indices, "dtype", type(indices))}')
+        self.indices.copy_(indices)
+        self._graph.replay()
+        self.feeder.last_draws = self.draws
+        return self.x, self.y
 
 
 def import_class(name):

@@ -795,6 +795,59 @@ def feeder_transform(raw, offsets, rot, idx, parent, V, time_steps, center_joint
     return out
 
 
+def _want(t, name, dtype, shape=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == dtype):
+        raise RuntimeError(f'tam_gcn_amd: {name} must be a contiguous {dtype} tensor on the GPU')
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f'tam_gcn_amd: {name} is {tuple(t.shape)}, expected {tuple(shape)}')
+
+
+def feeder_draw(offsets, clip_ids, state, cossin, time_steps, train, labels=None):
+    """The feeder's per-sample draws on the device (tamgcn_feeder_draw, include/tamgcn.h has the stream's definition).
+    offsets int64 [n_clips + 1], clip_ids int64 [B] (taken modulo n_clips), state int64 [2] = (seed, call) read on the
+    device and, on the train path, advanced by one after the draw; cossin fp64 (121, 2) (None allowed when train is
+    false); labels int64 [n_clips] | None.  -> view fp64 (B, 3), rot fp64 (B, 3, 3), idx int32 (B, time_steps),
+    labels int64 (B,) | None.  Shapes come from the arguments' shapes only: no host sync, capturable."""
+    _want(offsets, 'offsets', torch.int64)
+    _want(clip_ids, 'clip_ids', torch.int64)
+    _want(state, 'state', torch.int64, (2,))
+    n_clips, B = offsets.numel() - 1, clip_ids.numel()
+    if offsets.dim() != 1 or clip_ids.dim() != 1:
+        raise RuntimeError('tam_gcn_amd: feeder_draw takes 1-D offsets and clip_ids')
+    if cossin is not None:
+        _want(cossin, 'cossin', torch.float64, (121, 2))
+    if labels is not None:
+        _want(labels, 'labels', torch.int64, (n_clips,))
+    dev = offsets.device
+    view = torch.empty(B, 3, device=dev, dtype=torch.float64)
+    rot = torch.empty(B, 3, 3, device=dev, dtype=torch.float64)
+    idx = torch.empty(B, time_steps, device=dev, dtype=torch.int32)
+    lab = torch.empty(B, device=dev, dtype=torch.int64) if labels is not None else None
+    _lib.check(_lib_().tamgcn_feeder_draw(_ptr(offsets), n_clips, _ptr(clip_ids), B, _ptr(labels), _ptr(state), _ptr(cossin),
+                                          time_steps, int(bool(train)), _ptr(view), _ptr(rot), _ptr(idx), _ptr(lab), _stream()),
+               'tamgcn_feeder_draw')
+    return view, rot, idx, lab
+
+
+def feeder_transform_indexed(raw, offsets, clip_ids, rot, idx, parent, V, time_steps, center_joint, mode):
+    """feeder_transform reading the resident split: raw (sum L, V, 3) fp64 and offsets int64 [n_clips + 1] of the WHOLE
+    split, clip_ids int64 [B] (slot b transforms clip clip_ids[b] % n_clips), rot fp64 (B, 3, 3), idx int32
+    (B, time_steps) with every entry inside its clip -> (B, 3, time_steps, V, 1) fp32."""
+    _want(offsets, 'offsets', torch.int64)
+    _want(clip_ids, 'clip_ids', torch.int64)
+    n_clips, B = offsets.numel() - 1, clip_ids.numel()
+    _want(raw, 'raw', torch.float64)
+    _want(rot, 'rot', torch.float64, (B, 3, 3))
+    _want(idx, 'idx', torch.int32, (B, time_steps))
+    _want(parent, 'parent', torch.int32, (V,))
+    m = STREAM_MODES[mode] if isinstance(mode, str) else int(mode)
+    out = torch.empty(B, 3, time_steps, V, 1, device=raw.device, dtype=torch.float32)
+    _lib.check(_lib_().tamgcn_feeder_transform_indexed(_ptr(raw), _ptr(offsets), n_clips, _ptr(clip_ids), _ptr(rot), _ptr(idx),
+                                                       _ptr(parent), B, V, time_steps, center_joint, m, _ptr(out), _stream()),
+               'tamgcn_feeder_transform_indexed')
+    return out
+
+
 # ---------------------------------------------------------------------------
 # loss of the harness step (SURVEY.md §8 f1)
 def ce_fwd(logits, labels):
