@@ -114,6 +114,15 @@ __device__ __forceinline__ T* cg_at_w(void* base, unsigned byte_off) {
     return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off);
 }
 
+// a wave-uniform element offset, held in an SGPR pair whatever the loop around it does to it: `kernel argument + cg_sgpr(offset)` is
+// then a scalar base and the loads take their "scalar base + 32-bit lane offset" form.  Left alone, loop strength reduction
+// turns every load of a K loop into a 64-bit per-lane pointer of its own, carried around the loop (22 registers in
+// ctrgc_fwd_kernel<.., false>).  The pointer itself is not laundered: an integer round trip would lose its address space.
+__device__ __forceinline__ long long cg_sgpr(long long v) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
 typedef __attribute__((address_space(1))) const void* cg_gptr;
 typedef __attribute__((address_space(3))) void* cg_lptr;
 
@@ -244,7 +253,7 @@ __global__ __launch_bounds__(512) void ctrgc_E_kernel(const EArgs a) {
 // also wait for those stores to drain to HBM -- the loads of the next chunk are therefore issued before the stores and
 // pinned before the first store leaves).
 // ---------------------------------------------------------------------------
-template <class G, int ST>
+template <class G, int ST, bool UL = false>      // UL: every lane loads (lanes outside the operand from offset 0), commit() zeroes them
 struct X3Pref {
     using P = Plan<G, ST>;
     static constexpr int NPF = G::NPF, NT = G::NT, SBK = G::SBK, CT = G::CT;
@@ -260,20 +269,26 @@ struct X3Pref {
         const int cs = a.T * V;                                     // host: 4 * SBK * T * V < 2^32
         const float* xk = a.x + ((long long)n * a.x_ctot + a.x_coff + k0) * cs + (long long)t0 * V;    // wave-uniform
         const float* wk = a.w3 + (long long)c0 * a.Cin + k0;                                            // wave-uniform
+        if constexpr (UL) {
+            xk = a.x + cg_sgpr(((long long)n * a.x_ctot + a.x_coff + k0) * cs + (long long)t0 * V);
+            wk = a.w3 + cg_sgpr((long long)c0 * a.Cin + k0);
+        }
 #pragma unroll
         for (int i = 0; i < NAF; ++i) {
             const int e = tid + i * NT;
             const int kk = e % SBK, row = e / SBK;
             const int sidx = row / CT, c = row - sidx * CT;
             const bool ok = row < P::NR && k0 + kk < a.Cin;
-            wv[i] = ok ? *cg_at<float>(wk, 4u * (unsigned)((sidx * a.Cout + c) * a.Cin + kk)) : 0.f;
+            if constexpr (UL) wv[i] = *cg_at<float>(wk, ok ? 4u * (unsigned)((sidx * a.Cout + c) * a.Cin + kk) : 0u);
+            else wv[i] = ok ? *cg_at<float>(wk, 4u * (unsigned)((sidx * a.Cout + c) * a.Cin + kk)) : 0.f;
         }
 #pragma unroll
         for (int i = 0; i < NPF; ++i) {
             const int e = tid + i * NT;
             const int kk = e / ROWV, pos = (e - kk * ROWV) * 4;
             const bool ok = kk < SBK && k0 + kk < a.Cin && pos < ncols;
-            rv[i] = ok ? *cg_at<float4>(xk, 4u * (unsigned)(kk * cs + pos)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (UL) rv[i] = *cg_at<float4>(xk, ok ? 4u * (unsigned)(kk * cs + pos) : 0u);
+            else rv[i] = ok ? *cg_at<float4>(xk, 4u * (unsigned)(kk * cs + pos)) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
     __device__ __forceinline__ void pin() {
@@ -282,19 +297,29 @@ struct X3Pref {
 #pragma unroll
         for (int i = 0; i < NAF; ++i) asm volatile("" : "+v"(wv[i]));
     }
-    __device__ __forceinline__ void commit(float* As, float* Bs, int tid) const {    // registers -> LDS stage
+    // (Cin, k0, ncols) are those of the load() that filled the registers: with UL the lanes outside the operand were loaded from
+    // offset 0 and are zeroed here
+    __device__ __forceinline__ void commit(float* As, float* Bs, int tid, int Cin, int k0, int ncols) const {    // registers -> LDS stage
         if (TG_CKO & 4) return;
 #pragma unroll
         for (int i = 0; i < NAF; ++i) {
             const int e = tid + i * NT;
             const int kk = e % SBK, row = e / SBK;
-            if (row < P::NRT * 16) As[row * G::SBKP + kk] = wv[i];
+            if constexpr (UL) {
+                if (row < P::NRT * 16) As[row * G::SBKP + kk] = (row < P::NR && k0 + kk < Cin) ? wv[i] : 0.f;
+            } else {
+                if (row < P::NRT * 16) As[row * G::SBKP + kk] = wv[i];
+            }
         }
 #pragma unroll
         for (int i = 0; i < NPF; ++i) {
             const int e = tid + i * NT;
             const int kk = e / ROWV, pos = (e - kk * ROWV) * 4;
-            if (kk < SBK) *reinterpret_cast<float4*>(Bs + kk * G::PITCHB + pos) = rv[i];
+            if constexpr (UL) {
+                if (kk < SBK) *reinterpret_cast<float4*>(Bs + kk * G::PITCHB + pos) = (k0 + kk < Cin && pos < ncols) ? rv[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                if (kk < SBK) *reinterpret_cast<float4*>(Bs + kk * G::PITCHB + pos) = rv[i];
+            }
         }
     }
 };
@@ -305,8 +330,8 @@ struct X3Pref {
 // frame chunk (loaded by the caller, or by the previous call); when a next frame chunk exists its first K chunk is
 // requested right after the K loop, so that it travels under the tile write, the aggregation and the copy-out.
 // ---------------------------------------------------------------------------
-template <class G, int ST, class Pre>
-__device__ __forceinline__ void x3_chunk(const CtrgcArgs& a, int n, int c0, int t0, int bt, float* X3, X3Pref<G, ST>& pf, int next_t0, int next_bt, int tid, Pre&& pre) {
+template <class G, int ST, bool UL, class Pre>
+__device__ __forceinline__ void x3_chunk(const CtrgcArgs& a, int n, int c0, int t0, int bt, float* X3, X3Pref<G, ST, UL>& pf, int next_t0, int next_bt, int tid, Pre&& pre, float* B3s = nullptr, float b3v = 0.f) {
     // the tile leaves as X3[(c*BT + frame)*KP + s*V + v], KP = S*V: a (channel, frame) row holds the aggregation's k axis
     using P = Plan<G, ST>;
     constexpr int V = G::V, CW = G::CW, SBK = G::SBK, SBKP = G::SBKP, CT = G::CT;
@@ -331,7 +356,11 @@ __device__ __forceinline__ void x3_chunk(const CtrgcArgs& a, int n, int c0, int 
 #pragma unroll
     for (int c = 0; c < CW; ++c) { int col = (cw0 + c) * 16 + j; bcol[c] = (col < ncols && (c < 2 || third)) ? col : 0; }
 
-    float b3r[NRT][4];                                 // fetched here: in flight under the K loop, not exposed after it
+    // b3 of the lane's rows.  !UL: fetched here, in flight under the K loop, not exposed after it (twelve registers across the
+    // loop).  UL: thread `row` carries b3[row] (b3v, one register) and parks it in B3s -- the z tile, dead from the chunk's
+    // first barrier to the aggregation -- from where the tile write reads four values per row tile as one 16-byte vector
+    float b3r[NRT][4];
+    if constexpr (!UL) {
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
@@ -340,12 +369,19 @@ __device__ __forceinline__ void x3_chunk(const CtrgcArgs& a, int n, int c0, int 
             const int sidx = row / CT, c = row - sidx * CT;
             b3r[rt][r] = row < NR ? a.b3[sidx * a.Cout + c0 + c] : 0.f;
         }
+    }
     for (int k0 = 0; k0 < a.Cin; k0 += SBK) {
         __syncthreads();                               // previous users of the region are done
-        pf.commit(As, Bs, tid);
+        if constexpr (UL) { if (k0 == 0 && tid < NRT * 16) B3s[tid] = b3v; }
+        pf.commit(As, Bs, tid, a.Cin, k0, ncols);
         __syncthreads();
+        if constexpr (UL) {                            // one load site: the chunk after this one is (t0, k0 + SBK) or (next_t0, 0)
+            const bool more = k0 + SBK < a.Cin;
+            if (more || next_bt > 0) pf.load(a, n, c0, more ? t0 : next_t0, more ? bt : next_bt, more ? k0 + SBK : 0, tid);
+        } else {
         if (k0 + SBK < a.Cin) pf.load(a, n, c0, t0, bt, k0 + SBK, tid);      // in flight under the MFMAs
         else if (next_bt > 0) pf.load(a, n, c0, next_t0, next_bt, 0, tid);   // the next frame chunk's first K chunk
+        }
         const float* at = As + j * SBKP + kq;
         const float* bt_ = Bs + kq * PB;
 #pragma unroll
@@ -377,6 +413,11 @@ __device__ __forceinline__ void x3_chunk(const CtrgcArgs& a, int n, int c0, int 
     __syncthreads();                                   // stage dead; X3 may be overwritten
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt) {
+        if constexpr (UL) {
+            const f32x4 b = *reinterpret_cast<const f32x4*>(B3s + rt * 16 + kq * 4);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) b3r[rt][r] = b[r];
+        }
 #pragma unroll
         for (int c = 0; c < CW; ++c) {
             int col = (cw0 + c) * 16 + j;
@@ -451,17 +492,22 @@ __device__ __forceinline__ void aggregate_mfma(const float* Ek, const float* X3,
 // The same product with the B fragments (rows of E) taken from global memory instead of an LDS-resident tile: lane (j, kq)'s vector m
 // of row u is E[n][s][c][u][v0 .. v0+3] with 16 m + 4 kq = s V + v0 (V % 4 == 0: a vector never leaves its subset) -- the layout
 // tamgcn_ctrgc_build_e writes, read as it lies.  A workgroup re-reads its 77 KB per frame chunk from L2; without the tile two
-// 16-channel workgroups share a CU.  ld() requests one channel's fragments; the caller requests the first channel's before the
-// x3 tile write so that they travel under it.
+// 16-channel workgroups share a CU.  ld() requests one channel's fragments (or vectors m0 .. m1 - 1 of them); the caller requests
+// the first channel's before or during the x3 tile write so that they travel under it.
 template <class G, int ST>
 struct EFrag {
     static constexpr int V = G::V, KP = ST * V, NM = (KP + 15) / 16, NUT = (V + 15) / 16;
     f32x4 bv[NUT][NM];
     __device__ __forceinline__ void ld(const float* __restrict__ En, int Cout, int ch, int tid) {   // En = E + n*S*Cout*VV, ch = absolute channel (wave-uniform)
+        ld(En, Cout, ch, tid, 0, NM);
+    }
+    // vectors m0 .. m1 - 1 only: a caller that still holds other registers requests the fragments in the order the MFMAs use them
+    __device__ __forceinline__ void ld(const float* __restrict__ En, int Cout, int ch, int tid, int m0, int m1) {
         const int lane = tid & 63, j = lane & 15, kq = lane >> 4;
         const float* Ec = En + ch * G::VV;
 #pragma unroll
         for (int m = 0; m < NM; ++m) {
+            if (m < m0 || m >= m1) continue;
             const int k = 16 * m + 4 * kq;
             const bool in = k < KP;
             const int kk = in ? k : 0, sidx = kk / V, v0 = kk - sidx * V;
@@ -475,7 +521,11 @@ struct EFrag {
     }
 };
 
-template <class G, int ST, bool DB = false>      // DB: the next channel's fragments in a second register set
+// The next channel's fragments are requested INTO the registers of this channel's, vector by vector, as soon as the MFMAs that
+// read a vector have been issued: three quarters of a channel's MFMAs cover the request of the first vector, no second register
+// set (a second set, 32 registers, was what put ctrgc_fwd2_kernel over its 128; one set refilled after the channel's last MFMA
+// left every request exposed).  The order in which an accumulator receives its products is that of aggregate_mfma.
+template <class G, int ST>
 __device__ __forceinline__ void aggregate_mfma_g(const float* __restrict__ En, int Cout, int c0, EFrag<G, ST>& e0, const float* X3, float* Zs, int bt, int tid) {
     constexpr int V = G::V, CT = G::CT, KP = ST * V, NM = (KP + 15) / 16, NUT = (V + 15) / 16;
     static_assert(G::BT == 16, "one 16-frame MFMA row tile per chunk");
@@ -484,8 +534,6 @@ __device__ __forceinline__ void aggregate_mfma_g(const float* __restrict__ En, i
 #pragma unroll
     for (int ci = 0; ci < CT / G::NW; ++ci) {
         const int c = wave + ci * G::NW;
-        EFrag<G, ST> en;
-        if (DB && ci + 1 < CT / G::NW) en.ld(En, Cout, c0 + c + G::NW, tid);
         f32x4 av[NM];
 #pragma unroll
         for (int m = 0; m < NM; ++m) {
@@ -497,11 +545,13 @@ __device__ __forceinline__ void aggregate_mfma_g(const float* __restrict__ En, i
 #pragma unroll
         for (int ut = 0; ut < NUT; ++ut) acc[ut] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int m = 0; m < NM; ++m)
+        for (int m = 0; m < NM; ++m) {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int ut = 0; ut < NUT; ++ut) acc[ut] = mfma16(av[m][r], e0.bv[ut][m][r], acc[ut]);
+            if (ci + 1 < CT / G::NW) e0.ld(En, Cout, c0 + c + G::NW, tid, m, m + 1);
+        }
 #pragma unroll
         for (int ut = 0; ut < NUT; ++ut) {
             const int u = ut * 16 + j;
@@ -510,10 +560,6 @@ __device__ __forceinline__ void aggregate_mfma_g(const float* __restrict__ En, i
                 const int fr = kq * 4 + r;
                 if (u < V && fr < bt) Zs[c * G::NCOLS + fr * V + u] = acc[ut][r];
             }
-        }
-        if (ci + 1 < CT / G::NW) {
-            if (DB) e0 = en;
-            else e0.ld(En, Cout, c0 + c + G::NW, tid);                        // no registers for a second set
         }
     }
 }
@@ -590,7 +636,10 @@ __global__ __launch_bounds__(G::NT, ER ? 2 : 4) void ctrgc_fwd_kernel(const Ctrg
     static_assert(ER || CT % G::NW == 0, "whole channels per wave");
 
     TG_T(tt0);
-    X3Pref<G, ST> pf;
+    X3Pref<G, ST, !ER> pf;
+    float b3v = 0.f;                                   // !ER: thread `row` of the x3 GEMM carries b3[row] (see x3_chunk)
+    if constexpr (!ER) b3v = tid0 < P::NR ? a.b3[(tid0 / CT) * a.Cout + c0 + tid0 % CT] : 0.f;
+    if constexpr (!ER) asm volatile("" : "+v"(b3v));   // waited for here (with the first operands, which the first commit needs at once), not inside the frame loop
     pf.load(a, n, c0, 0, min(G::BT, a.T), 0, tid0);          // first operands of the first chunk: in flight under the E load
     if constexpr (ER) load_E_k<G, ST>(a.E, a.Cout, n, c0, Es);
     TG_T(tt1); TG_ACC(0, tt1 - tt0);
@@ -601,14 +650,15 @@ __global__ __launch_bounds__(G::NT, ER ? 2 : 4) void ctrgc_fwd_kernel(const Ctrg
         const int ncols = bt * V;
         const int nt0 = t0 + G::BT, nbt = nt0 < a.T ? min(G::BT, a.T - nt0) : 0;
         // 128 registers per wave (ER = false): everything derived from the thread index is recomputed per frame chunk instead of
-        // being hoisted out of this loop and spilled (a scratch reload is a vmcnt wait behind every prefetch in flight)
+        // being hoisted out of this loop (a spill's scratch reload is a vmcnt wait behind every prefetch in flight; the kernel has
+        // none: tools/kernel_resources.py --spill-free checks it)
         int tid = tid0;
         if constexpr (!ER) asm volatile("" : "+v"(tid));
         const int c = tid / (G::NTQ * 4);
         const int lrow = tid % (G::NTQ * 4);           // lane index inside the channel row (copy-out)
         TG_T(ta);
         EFrag<G, ST> ef;
-        x3_chunk<G, ST>(a, n, c0, t0, bt, X3, pf, nt0, nbt, tid, [&] { if constexpr (!ER) ef.ld(En, a.Cout, c0 + __builtin_amdgcn_readfirstlane(tid >> 6), tid); });
+        x3_chunk<G, ST, !ER>(a, n, c0, t0, bt, X3, pf, nt0, nbt, tid, [&] { if constexpr (!ER) ef.ld(En, a.Cout, c0 + __builtin_amdgcn_readfirstlane(tid >> 6), tid); }, Zs, b3v);
         TG_T(tb); TG_ACC(1, tb - ta);
         if constexpr (!ER) aggregate_mfma_g<G, ST>(En, a.Cout, c0, ef, X3, Zs, bt, tid);
         else if (!(TG_CKO & 16)) aggregate_mfma<G, ST>(Es, X3, Zs, bt);      // frames beyond bt hold stale data: their rows are not stored
@@ -704,8 +754,9 @@ __global__ __launch_bounds__(G::NT, ER ? 2 : 4) void ctrgc_fwd_kernel(const Ctrg
 //   * the x3 GEMM's operands travel by LDS-DMA into two 25 KB stages inside the x3 tile's region (16 input channels each):
 //     no staging registers, no commit pass, one barrier per K chunk -- the register-staged form spent 28 % of the launch on the
 //     loads and their commit once two workgroups shared the CU;
-//   * 128 registers per wave: everything derived from the thread index is recomputed per frame chunk (an opaque copy of it) --
-//     hoisted out of the loop the compiler spilled 143 registers, and a scratch reload is a vmcnt wait behind every request in flight;
+//   * 128 registers per wave, none spilled (tools/kernel_resources.py --spill-free checks it): what is derived from the thread index for
+//     a phase is recomputed per frame chunk (an opaque copy of it) -- hoisted out of the loop the compiler spilled 143 registers, and a
+//     scratch reload is a vmcnt wait behind every request in flight; only the DMA source offsets (poff / plim) and b3 live across chunks;
 //   * the first stage of the NEXT frame chunk is requested after the copy-out's LDS reads and BEFORE its global stores (vmcnt
 //     retires in order): the next chunk's first wait allows exactly those stores to be still in flight.
 // Applies to S = 3, Cout % 16 == 0, Cin % 16 == 0, 16-byte aligned x and w3; everything else stays on ctrgc_fwd_kernel.
@@ -758,47 +809,70 @@ __global__ __launch_bounds__(G::NT, 4) void ctrgc_fwd2_kernel(const CtrgcArgs a,
     const int nst = NV4 * (x3_out ? ST + 1 : 1);                          // store instructions of one copy-out
 
     // one K chunk (16 input channels from k0) of the frames from t0 into stage `stage`: per lane a 16-byte slot of each of the
-    // wave's pieces -- the image is linear in LDS, the layout sits in the source address
+    // wave's pieces -- the image is linear in LDS, the layout sits in the source address.  A piece's source is a wave-uniform
+    // base (x or w3 at (k0, t0)) plus a lane offset that depends on nothing but the thread: poff / plim are computed once per
+    // launch (eight registers; recomputed per frame chunk -- two divisions per piece at three call sites -- they were what the
+    // 128-register form spilled).  plim: the lane's first column of an x piece (requested while < ncols); 0 / INT_MAX for the
+    // lanes of a weight piece inside / outside the 16 x 48 block.
+    unsigned poff[F::NPW];
+    int plim[F::NPW];
+    {
+        const int lane = tid0 & 63, wave = tid0 >> 6;
+#pragma unroll
+        for (int i = 0; i < F::NPW; ++i) {
+            const int L = (wave + i * G::NW) * 64 + lane;
+            if (L < F::XSL) {
+                const int row = L / F::RS, c4 = L - row * F::RS;
+                poff[i] = 4u * (unsigned)(row * cs + c4 * 4);
+                plim[i] = c4 * 4;
+            } else {
+                const int La = L - F::XSL;
+                const int row = La / (AP / 4), q = La - row * (AP / 4);
+                const int sidx = row / CT, c = row - sidx * CT;
+                const bool ok = q < SBK / 4 && La < F::ASL;
+                poff[i] = ok ? 4u * (unsigned)((sidx * a.Cout + c) * a.Cin + q * 4) : 0u;
+                plim[i] = ok ? 0 : 0x7fffffff;
+            }
+        }
+    }
     auto issue = [&](int stage, int t0, int ncols, int k0, int tid) -> int {   // returns the number of requests this wave made (wave-uniform)
         if (TG_CKO & 2) return 0;
         int cnt = 0;
-        const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         float* st = X3 + stage * F::STG;
-        const float* xk = xn + (long long)k0 * cs + (long long)t0 * V;
-        const float* wk = wk0 + k0;
+        const float* xk = xn + cg_sgpr((long long)k0 * cs + (long long)t0 * V);
+        const float* wk = wk0 + cg_sgpr((long long)k0);
 #pragma unroll
         for (int i = 0; i < F::NPW; ++i) {
             const int p = wave + i * G::NW;                                // wave-uniform
             if (p < F::NPIECE) {
-                const int L = p * 64 + lane;
-                if (p * 64 < F::XSL) {
-                    const int row = L / F::RS, c4 = L - row * F::RS;
-                    const bool ok = c4 * 4 < ncols;
-                    if (__ballot(ok) != 0ull) {                              // the request exists or not for the whole wave: it is counted
-                        if (ok) __builtin_amdgcn_global_load_lds((cg_gptr)cg_at<float>(xk, 4u * (unsigned)(row * cs + c4 * 4)), (cg_lptr)(st + p * 256), 16, 0, 0);
-                        ++cnt;
-                    }
-                } else {
-                    const int La = L - F::XSL;
-                    const int row = La / (AP / 4), q = La - row * (AP / 4);
-                    const int sidx = row / CT, c = row - sidx * CT;
-                    const bool ok = q < SBK / 4 && La < F::ASL;
-                    if (__ballot(ok) != 0ull) {
-                        if (ok) __builtin_amdgcn_global_load_lds((cg_gptr)cg_at<float>(wk, 4u * (unsigned)((sidx * a.Cout + c) * a.Cin + q * 4)), (cg_lptr)(st + p * 256), 16, 0, 0);
-                        ++cnt;
-                    }
+                const bool ok = plim[i] < ncols;
+                const float* base = p * 64 < F::XSL ? xk : wk;              // wave-uniform
+                unsigned o = poff[i];
+                asm volatile("" : "+v"(o));                                  // base + o is formed HERE (as scalar base + lane offset), not as a 64-bit lane pointer per piece and base carried through the launch
+                if (__ballot(ok) != 0ull) {                                  // the request exists or not for the whole wave: it is counted
+                    if (ok) __builtin_amdgcn_global_load_lds((cg_gptr)cg_at<float>(base, o), (cg_lptr)(st + p * 256), 16, 0, 0);
+                    ++cnt;
                 }
             }
         }
         return cnt;
     };
 
+    // thread `row` of the x3 GEMM carries b3[row] and parks it in the (dead) z tile during the K loop, from where the tile write
+    // takes the four values of a row tile as one 16-byte read: no global load between the K loop and the tile write
+    static_assert(NSTG == 2, "a third stage would reach into the z tile where b3 is parked");
     int cnt = 0;                                       // requests per stage of the current frame chunk (this wave)
 #pragma unroll
     for (int sg = 0; sg < NSTG - 1; ++sg)
         if (sg < nk) cnt = issue(sg, 0, min(G::BT, a.T) * V, sg * SBK, tid0);
     int after = 0;                                     // requests this wave made after the chunk's first stage (the previous copy-out's stores)
     float st1 = 0.f, st2 = 0.f;
+    // requested behind the first stage and waited for HERE: the first K chunk waits for everything in flight anyway.  Left to
+    // the compiler, the wait lands in front of the first use -- inside the frame loop, where a vmcnt(0) per chunk would also wait
+    // for the previous copy-out's stores, which the counted wait of the chunk's first stage exists to leave in flight
+    float b3v = tid0 < P::NR ? a.b3[(tid0 / CT) * a.Cout + c0 + tid0 % CT] : 0.f;
+    asm volatile("" : "+v"(b3v));
     for (int t0 = 0; t0 < a.T; t0 += G::BT) {
         const int bt = min(G::BT, a.T - t0);
         const int ncols = bt * V;
@@ -825,6 +899,7 @@ __global__ __launch_bounds__(G::NT, 4) void ctrgc_fwd2_kernel(const CtrgcArgs a,
             cg_wait_vmcnt((kc < NSTG - 1 ? after : 0) + (min(kc + NSTG - 2, nk - 1) - kc) * cnt);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // everyone's have; nobody reads stage kc - 1 any more
             if (kc + NSTG - 1 < nk) issue((kc + NSTG - 1) % NSTG, t0, ncols, (kc + NSTG - 1) * SBK, tid);
+            if (kc == 0 && tid < P::NR) Zs[tid] = b3v;                           // the z tile is dead from this barrier to the aggregation
             const int slot = kc % NSTG;
             const float* As = X3 + slot * F::STG + F::XSL * 4 + j * AP + kq;
             const float* Bs = X3 + slot * F::STG + kq * PB;
@@ -846,46 +921,47 @@ __global__ __launch_bounds__(G::NT, 4) void ctrgc_fwd2_kernel(const CtrgcArgs a,
                 }
             }
         }
-        float b3r[NRT][4];
-#pragma unroll
-        for (int rt = 0; rt < NRT; ++rt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) b3r[rt][r] = a.b3[rt * a.Cout + c0 + kq * 4 + r];       // row = rt*16 + kq*4 + r = (subset rt, channel kq*4 + r)
+        // the first channel's E rows are requested while the tile is written, a quarter behind each third of it: the registers of a
+        // row tile of accumulators are free by then (all of them requested in front of the tile write, accumulators and fragments
+        // alone are 68 of the 128 registers and the kernel wanted 144)
         EFrag<G, ST> ef;
-        ef.ld(En, a.Cout, c0 + wave, tid);             // the first channel's E rows travel under the tile write
+        static_assert(EFrag<G, ST>::NM == NRT + 1, "one vector of E fragments per row tile written, two behind the last");
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // stages dead: the x3 tile may be written
 #pragma unroll
         for (int rt = 0; rt < NRT; ++rt) {
+            const f32x4 b3r = *reinterpret_cast<const f32x4*>(Zs + rt * 16 + kq * 4);           // row = rt*16 + kq*4 + r = (subset rt, channel kq*4 + r)
 #pragma unroll
             for (int c = 0; c < CW; ++c) {
                 const int col = (cw0 + c) * 16 + j;
                 if (col >= ncols || (c == 2 && !third)) continue;
                 const int fr = col / V, v = col - fr * V;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) X3[((kq * 4 + r) * G::BT + fr) * (ST * V) + rt * V + v] = acc[rt][c][r] + b3r[rt][r];
+                for (int r = 0; r < 4; ++r) X3[((kq * 4 + r) * G::BT + fr) * (ST * V) + rt * V + v] = acc[rt][c][r] + b3r[r];
             }
+            ef.ld(En, a.Cout, c0 + wave, tid, rt, rt + 1 < NRT ? rt + 1 : NRT + 1);
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        aggregate_mfma_g<G, ST, true>(En, a.Cout, c0, ef, X3, Zs, bt, tid);
+        aggregate_mfma_g<G, ST>(En, a.Cout, c0, ef, X3, Zs, bt, tid);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
         // ---- copy-out: LDS -> registers, then (everybody done with the region) the next chunk's first stage, then the stores
+        // lanes beyond the chunk's columns read the last vector of their row again (their stores are predicated): every read is
+        // unconditional -- a `valid ? read : 0` keeps twelve zero registers alive around the whole frame loop
         const int c = tid / RL, lrow = tid % RL;
-        float4 zv[NV4], xv[ST][NV4];
+        f32x4 zv[NV4], xv[ST][NV4];
 #pragma unroll
         for (int i = 0; i < NV4; ++i) {
-            const int p4 = lrow + i * RL;
-            zv[i] = p4 < (ncols >> 2) ? reinterpret_cast<const float4*>(Zs + c * G::NCOLS)[p4] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const int p4 = min(lrow + i * RL, (ncols >> 2) - 1);
+            zv[i] = reinterpret_cast<const f32x4*>(Zs + c * G::NCOLS)[p4];
         }
         if (x3_out) {
 #pragma unroll
             for (int s = 0; s < ST; ++s)
 #pragma unroll
                 for (int i = 0; i < NV4; ++i) {
-                    const int p4 = lrow + i * RL;
+                    const int p4 = min(lrow + i * RL, (ncols >> 2) - 1);
                     const int fr = p4 / (V / 4), q = p4 - fr * (V / 4);
-                    xv[s][i] = p4 < (ncols >> 2) ? *reinterpret_cast<const float4*>(X3 + (c * G::BT + fr) * (ST * V) + s * V + 4 * q)
-                                                 : make_float4(0.f, 0.f, 0.f, 0.f);
+                    xv[s][i] = *reinterpret_cast<const f32x4*>(X3 + (c * G::BT + fr) * (ST * V) + s * V + 4 * q);
                 }
         }
         if (nbt > 0) {
@@ -894,8 +970,13 @@ __global__ __launch_bounds__(G::NT, 4) void ctrgc_fwd2_kernel(const CtrgcArgs a,
             for (int sg = 0; sg < NSTG - 1; ++sg)      // slots 0 .. NSTG - 2, as the next K loop expects them (the z tile is dead too: barrier above)
                 if (sg < nk) cnt = issue(sg, nt0, nbt * V, sg * SBK, tid);
             asm volatile("" ::: "memory");             // the stores below stay below: `after` counts them
+            // A next chunk exists, so this one is full (bt = BT): every one of the NV4 vectors of a row has lanes that store it in
+            // every wave, no store instruction can be skipped for an empty exec mask, and a wave issues exactly nst of them.
+            // tools/kernel_resources.py holds the kernel's 16-byte store instructions (the copy-out has the only ones) against the
+            // n of the marker below: a compiler that merged, split or duplicated them would break the count silently.
             after = nst;
         }
+        asm volatile("; cg_fwd2_copyout_stores n=%0" :: "n"(NV4 * (ST + 1)) : "memory");
         const unsigned rowb = 4u * (unsigned)(c * a.T * V);
         if (x3_out) {
 #pragma unroll
@@ -904,7 +985,7 @@ __global__ __launch_bounds__(G::NT, 4) void ctrgc_fwd2_kernel(const CtrgcArgs a,
 #pragma unroll
                 for (int i = 0; i < NV4; ++i) {
                     const int p4 = lrow + i * RL;
-                    if (p4 < (ncols >> 2)) *cg_at_w<float4>(xo, rowb + 16u * (unsigned)p4) = xv[s][i];
+                    if (p4 < (ncols >> 2)) *cg_at_w<f32x4>(xo, rowb + 16u * (unsigned)p4) = xv[s][i];
                 }
             }
         }
@@ -913,9 +994,9 @@ __global__ __launch_bounds__(G::NT, 4) void ctrgc_fwd2_kernel(const CtrgcArgs a,
         for (int i = 0; i < NV4; ++i) {
             const int p4 = lrow + i * RL;
             if (p4 < (ncols >> 2)) {
-                *cg_at_w<float4>(ybase, rowb + 16u * (unsigned)p4) = zv[i];
-                st1 += (zv[i].x + zv[i].y) + (zv[i].z + zv[i].w);
-                st2 = fmaf(zv[i].x, zv[i].x, fmaf(zv[i].y, zv[i].y, fmaf(zv[i].z, zv[i].z, fmaf(zv[i].w, zv[i].w, st2))));
+                *cg_at_w<f32x4>(ybase, rowb + 16u * (unsigned)p4) = zv[i];
+                st1 += (zv[i][0] + zv[i][1]) + (zv[i][2] + zv[i][3]);
+                st2 = fmaf(zv[i][0], zv[i][0], fmaf(zv[i][1], zv[i][1], fmaf(zv[i][2], zv[i][2], fmaf(zv[i][3], zv[i][3], st2))));
             }
         }
     }
@@ -1068,12 +1149,17 @@ static int fill_args(const tamgcn_ctrgc_desc* d, CtrgcArgs* a, const char* who, 
 
 static unsigned grid_blocks(const CtrgcArgs& a) { return 8u * (unsigned)ceil_div(a.N, 8) * (unsigned)a.nct; }
 
+static bool debug_occ() {                    // TAMGCN_DEBUG_OCC, read once per process
+    static const bool on = getenv("TAMGCN_DEBUG_OCC") != nullptr;
+    return on;
+}
+
 #define CTRGC_LAUNCH(KERNEL, GEO, ST_, FLAG, ...)                                                               \
     do {                                                                                                        \
         static tg_devmask FLAG = 0;                                                                             \
         constexpr size_t lds_ = Plan<GEO, ST_>::LDS;                                                            \
         tg_allow_lds((const void*)KERNEL<GEO, ST_>, lds_, &FLAG);   /* exact size */                            \
-        if (getenv("TAMGCN_DEBUG_OCC")) {                                                                       \
+        if (debug_occ()) {                                                                                      \
             int nb_ = -1;                                                                                       \
             (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, (const void*)KERNEL<GEO, ST_>, GEO::NT, lds_); \
             fprintf(stderr, "[tamgcn] %s<CT %d, %d>: %d workgroups per CU (%zu B LDS, %d threads)\n", #KERNEL, GEO::CT, ST_, nb_, lds_, GEO::NT); \
@@ -1129,10 +1215,14 @@ extern "C" int tamgcn_ctrgc_fwd(const tamgcn_ctrgc_desc* d, float* y, float* sta
     CtrgcArgs a;
     const int ct = fwd_ct(d->Cout);
     if (fill_args(d, &a, "tamgcn_ctrgc_fwd", ct)) return -1;
-    // 16-channel tiles, S = 3: two workgroups per CU without a resident E tile (round 4).  Measured per layer shape (256 clips, us):
-    //   resident E (ctrgc_fwd_kernel<.., true>)    158 / 206 / 400 / 297 / 590 / 488   (l1 l2 l5 l6 l8 l9)
-    //   E from L2, register-staged operands        151 / 200 / 385 / 277 / 545 / 442
-    //   E from L2, LDS-DMA operands (fwd2)           - / 218 / 421 / 287 / 553 / 420
+    // 16-channel tiles, S = 3: two workgroups per CU without a resident E tile (round 4; both forms free of scratch since
+    // profiles/ctrgc_fwd_spillfree_ab.txt).  Measured per layer shape (256 clips, us, two interleaved rounds on one box, launches alone):
+    //   resident E (ctrgc_fwd_kernel<.., true>)    156-160 /   -     /   -     /   -     /   -     /   -       (l1 l2 l5 l6 l8 l9)
+    //   E from L2, register-staged operands        130-131 / 180-184 / 387-391 / 279-291 / 579-586 / 467-469
+    //   E from L2, LDS-DMA operands (fwd2)            -    / 179-183 / 390-391 / 275-279 / 550-552 / 445-450
+    // Neither form is faster at every shape it serves: fwd2 wins at Cin = 256 and at l8 (128 -> 256), the two tie at Cin = 64.  Inside
+    // the training step fwd2 at every Cin >= 16 (mode 2) measured 27.75-27.90 ms against 27.58-27.90 ms for the dispatch below, so the
+    // dispatch stays as it was.  The three forms are bit-identical to each other in y, x3 and the moments.
     // TAMGCN_CTRGC_FWD2: 0 resident E everywhere, 1 (default) the faster of the other two by Cin, 2 fwd2 wherever it applies, 3 never fwd2.
     static const int mode = [] { const char* e = getenv("TAMGCN_CTRGC_FWD2"); return e ? atoi(e) : 1; }();
     const bool al16 = (((uintptr_t)d->x.x1 | (uintptr_t)d->w3) & 15) == 0;
@@ -1151,7 +1241,7 @@ extern "C" int tamgcn_ctrgc_fwd(const tamgcn_ctrgc_desc* d, float* y, float* sta
         static tg_devmask fw3e = 0;
         constexpr size_t lds_ = Plan<G20W, 3>::LDS_NOE;
         tg_allow_lds((const void*)ctrgc_fwd_kernel<G20W, 3, false>, lds_, &fw3e);
-        if (getenv("TAMGCN_DEBUG_OCC")) {
+        if (debug_occ()) {
             int nb_ = -1;
             (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, (const void*)ctrgc_fwd_kernel<G20W, 3, false>, G20W::NT, lds_);
             fprintf(stderr, "[tamgcn] ctrgc_fwd_kernel<CT 16, 3, E from L2>: %d workgroups per CU (%zu B LDS)\n", nb_, lds_);
