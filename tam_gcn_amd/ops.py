@@ -558,26 +558,40 @@ def ctrgc_bwd_dx3(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, E=None, 
     return dx3, (reduce_sum(db3_part, N, chunks=[(Cout,)] * S) if per_subset else reduce_sum(db3_part, N))
 
 
-def ctrgc_bwd_de(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, x3=None, per_subset=False):
-    """The dE chain: dA [S,V,V], dw4 [S,Cout,R], db4 [S,Cout], dalpha [1], dpq [S*2*R,N,V]: a streaming accumulation of
-    dE from dy and the x3 ctrgc_fwd kept (recomputed by one pointwise GEMM if it was not), then one per-(n, s) tail launch."""
-    N, _, T, V = x.x1.shape
-    d = _ctrgc_desc(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R)
-    dyc = dy.c()
-    like = x.x1
-    route = ctrgc_route(V)
-    dE = None
-    if route != 'fused':
-        if x3 is None:
-            x3 = _x3_gemm(x, w3, b3, Cin, Cout, S)
-        dE = empty(N, S, Cout, V, V, like=like)
+def ctrgc_bwd_de_acc(dy, x3, Cout, S):
+    """dE (N, S, Cout, V, V) = sum_t dy[n,c,t,u] x3[n,s*Cout+c,t,v]: the streaming accumulation of the dE chain.
+    dy: an operand S(...) whose channels coff..coff+Cout are the gradient; x3 (N, S*Cout, T, V)."""
+    N, _, T, V = x3.shape
+    d = CtrgcDesc()
+    d.N, d.Cout, d.S, d.T, d.V = N, Cout, S, T, V
+    dE = empty(N, S, Cout, V, V, like=x3)
+    if ctrgc_route(V) != 'fused':
         for n0, n1 in n_chunks(N, S * Cout * T * V):
             d.N = n1 - n0
             dyc = _slice_src(dy, n0, n1).c()
             _lib.check(_lib_().tamgcn_ctrgc_tiled_de_acc(C.byref(d), C.byref(dyc), _ptr(x3[n0:n1]), _ptr(dE[n0:n1]), _stream()),
                        'tamgcn_ctrgc_tiled_de_acc')
-        d.N = N
-    if route == 'tiled':
+    else:
+        dyc = dy.c()
+        _lib.check(_lib_().tamgcn_ctrgc_bwd_de_acc(C.byref(d), C.byref(dyc), _ptr(x3), _ptr(dE), _stream()),
+                   'tamgcn_ctrgc_bwd_de_acc')
+    return dE
+
+
+def ctrgc_bwd_de_tail(dE, pq, w4, b4, alpha, R, per_subset=False, groups=1):
+    """dE (N, S, Cout, V, V) through E = alpha (W4 tanh(p_u - q_v) + b4) + A: dA [S,V,V], dw4 [S,Cout,R], db4 [S,Cout],
+    dalpha [1], dpq [S*2*R,N,V], one per-(n, s) tail launch.  groups: channel groups per (n, subset) of the LDS-resident
+    tail (V in {20, 25}); the per-workgroup fixed cost (D fill, dp/dq sums) equals ~1.4 channel chunks, so splitting did
+    not pay (measured) and the model runs one."""
+    N, S, Cout, V, _ = dE.shape
+    d = CtrgcDesc()
+    d.N, d.Cout, d.S, d.R, d.V = N, Cout, S, R, V
+    d.pq, d.w4, d.b4, d.alpha = _ptr(pq), _ptr(w4), _ptr(b4), _ptr(alpha)
+    like = dE
+    ps = per_subset
+    if ctrgc_route(V) == 'tiled':
+        if groups != 1:
+            raise RuntimeError('tam_gcn_amd: the tiled dE tail (V in {32, 64}) has no channel groups')
         NUC = _lib_().tamgcn_ctrgc_tiled_chunks(V)
         dA_part = empty(N, S, V, V, like=like)
         dw4_part = empty(N * NUC, S, Cout, R, like=like)
@@ -586,20 +600,12 @@ def ctrgc_bwd_de(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, x3=None, 
         dpq = empty(NUC, S * 2 * R, N, V, like=like)
         _lib.check(_lib_().tamgcn_ctrgc_tiled_de_tail(C.byref(d), _ptr(dE), _ptr(dA_part), _ptr(dw4_part), _ptr(db4_part), _ptr(dal_part),
                                                       _ptr(dpq), _stream()), 'tamgcn_ctrgc_tiled_de_tail')
-        ps = per_subset
         return (reduce_sum(dA_part, N), reduce_sum(dw4_part, N * NUC, chunks=[(Cout, R, 1, 1)] * S if ps else None),
                 reduce_sum(db4_part, N * NUC, chunks=[(Cout,)] * S if ps else None), reduce_sum(dal_part, N * S * NUC),
                 reduce_sum(dpq, NUC, immediate=True))
     if R > 32:
         raise RuntimeError('tam_gcn_amd: CTRGC with R > 32 rel-channels is not built')
-    if dE is None:
-        if x3 is None:                                      # the caller did not keep x3: one more pointwise GEMM
-            x3 = _x3_gemm(x, w3, b3, Cin, Cout, S)
-        dE = empty(N, S, Cout, V, V, like=like)
-        _lib.check(_lib_().tamgcn_ctrgc_bwd_de_acc(C.byref(d), C.byref(dyc), _ptr(x3), _ptr(dE), _stream()),
-                   'tamgcn_ctrgc_bwd_de_acc')
-    G = 1                                               # channel groups per (n, subset); the per-workgroup fixed cost (D fill,
-    #                                                     dp/dq sums) equals ~1.4 channel chunks, so splitting did not pay (measured)
+    G = groups
     dA_part = empty(N * G, S, V, V, like=like)
     dw4_part = empty(N, S, Cout, R, like=like)
     db4_part = empty(N, S, Cout, like=like)
@@ -607,10 +613,18 @@ def ctrgc_bwd_de(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, x3=None, 
     dpq = empty(G, S * 2 * R, N, V, like=like)
     _lib.check(_lib_().tamgcn_ctrgc_bwd_de_tail(C.byref(d), _ptr(dE), _ptr(dA_part), _ptr(dw4_part), _ptr(db4_part),
                                                 _ptr(dal_part), _ptr(dpq), G, _stream()), 'tamgcn_ctrgc_bwd_de_tail')
-    dpq = dpq[0]
-    ps = per_subset
+    dpq = dpq[0] if G == 1 else reduce_sum(dpq, G, immediate=True)       # every group holds a partial dp / dq of its channels
     return (reduce_sum(dA_part, N * G), reduce_sum(dw4_part, N, chunks=[(Cout, R, 1, 1)] * S if ps else None),
             reduce_sum(db4_part, N, chunks=[(Cout,)] * S if ps else None), reduce_sum(dal_part, N * S * G), dpq)
+
+
+def ctrgc_bwd_de(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, x3=None, per_subset=False):
+    """The dE chain: dA [S,V,V], dw4 [S,Cout,R], db4 [S,Cout], dalpha [1], dpq [S*2*R,N,V]: a streaming accumulation of
+    dE from dy and the x3 ctrgc_fwd kept (recomputed by one pointwise GEMM if it was not), then one per-(n, s) tail launch."""
+    if x3 is None:                                          # the caller did not keep x3: one more pointwise GEMM
+        x3 = _x3_gemm(x, w3, b3, Cin, Cout, S)
+    dE = ctrgc_bwd_de_acc(dy, x3, Cout, S)
+    return ctrgc_bwd_de_tail(dE, pq, w4, b4, alpha, R, per_subset=per_subset)
 
 
 def ctrgc_bwd(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, x3=None, E=None):
