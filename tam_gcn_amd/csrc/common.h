@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 #include "../../include/tamgcn.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -37,17 +38,36 @@ int tamgcn_split_mode(void);     // TAMGCN_SPLIT_BF16: 0 (default) = exact fp32-
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE property of a kernel: the guard is a bit per device
-// ordinal (nn.DataParallel drives several devices from one process), not a process-wide flag.  Not a stream operation.
-typedef unsigned long long tg_devmask;
-static inline void tg_allow_lds(const void* fn, size_t bytes, tg_devmask* done) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const tg_devmask bit = 1ull << (dev & 63);
-    if (!(__atomic_load_n(done, __ATOMIC_RELAXED) & bit)) {
-        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        __atomic_fetch_or(done, bit, __ATOMIC_RELAXED);
+constexpr int NTHREADS = 256;    // workgroup of the register-staged GEMM kernels (conv.hip, wgrad.hip)
+
+static inline bool tg_debug_occ() {          // TAMGCN_DEBUG_OCC, read once per process
+    static const bool on = getenv("TAMGCN_DEBUG_OCC") != nullptr;
+    return on;
+}
+
+// The launch of a kernel that may ask for more dynamic LDS than the default limit.  A request above 48 KB needs
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize), a per-DEVICE property of a kernel and not a stream operation: it is set once per
+// kernel (one guard per instantiation of this template) and device (a bit per device ordinal: nn.DataParallel drives several
+// devices from one process), to `bound` -- which therefore must cover the LARGEST request the kernel can ever get, not this one.
+// TAMGCN_DEBUG_OCC prints the resident workgroups per CU of every such launch.
+template <auto Kernel, typename... Args>
+static inline void tg_launch_lds(size_t bound, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args) {
+    static unsigned long long done = 0;
+    if (lds > 48 * 1024) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        const unsigned long long bit = 1ull << (dev & 63);
+        if (!(__atomic_load_n(&done, __ATOMIC_RELAXED) & bit)) {
+            (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bound);
+            __atomic_fetch_or(&done, bit, __ATOMIC_RELAXED);
+        }
     }
+    if (tg_debug_occ()) {
+        int nb = -1;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)Kernel, (int)(block.x * block.y * block.z), lds);
+        fprintf(stderr, "[tamgcn] %s: %d workgroups per CU (%zu B LDS, %u threads)\n", __PRETTY_FUNCTION__, nb, lds, block.x * block.y * block.z);
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
 }
 
 // ---------------------------------------------------------------------------
@@ -137,6 +157,31 @@ __device__ __forceinline__ f32x4 mfma_split(const bf16x8_t& ah, const bf16x8_t& 
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
 }
+
+// LDS-DMA (global_load_lds) operands
+typedef __attribute__((address_space(1))) const void* tg_gptr;
+typedef __attribute__((address_space(3))) void* tg_lptr;
+
+// s_waitcnt vmcnt(n) for a run-time, wave-uniform n.  The count is an immediate, so every n is a case of a switch inside the
+// kernel: NMAX is the largest one the kernel carries, any larger n waits for everything.
+#define TG_VMCNT_CASE(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
+template <int NMAX>
+__device__ __forceinline__ void tg_wait_vmcnt(int n) {
+    static_assert(NMAX <= 24, "add the cases");
+    switch (n > NMAX ? -1 : n) {
+        TG_VMCNT_CASE(0) TG_VMCNT_CASE(1) TG_VMCNT_CASE(2) TG_VMCNT_CASE(3) TG_VMCNT_CASE(4) TG_VMCNT_CASE(5) TG_VMCNT_CASE(6)
+        TG_VMCNT_CASE(7) TG_VMCNT_CASE(8) TG_VMCNT_CASE(9) TG_VMCNT_CASE(10) TG_VMCNT_CASE(11) TG_VMCNT_CASE(12)
+        TG_VMCNT_CASE(13) TG_VMCNT_CASE(14) TG_VMCNT_CASE(15) TG_VMCNT_CASE(16) TG_VMCNT_CASE(17) TG_VMCNT_CASE(18)
+        TG_VMCNT_CASE(19) TG_VMCNT_CASE(20) TG_VMCNT_CASE(21) TG_VMCNT_CASE(22) TG_VMCNT_CASE(23) TG_VMCNT_CASE(24)
+        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    }
+}
+#undef TG_VMCNT_CASE
+
+// x / d for 0 <= x < 2^20 and a divisor 4 <= d <= 1024 through rcp = 1.0f / d: three VALU instead of the ~25 of an integer
+// division.  (x + 0.5) / d lies at least 0.5 / d from an integer; x + 0.5 is exact, rcp and the product round once each
+// (2^-23 relative together), which moves the quotient by less than 2^-23 x / d <= 0.125 / d.
+__device__ __forceinline__ int tg_rcp_div(int x, float rcp) { return (int)(((float)x + 0.5f) * rcp); }
 
 // tanh(x) = 1 - 2/(exp(2x)+1): absolute error ~1e-7 (D is O(1) and enters E linearly)
 __device__ __forceinline__ float fast_tanh(float x) {

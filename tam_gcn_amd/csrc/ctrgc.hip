@@ -123,9 +123,6 @@ __device__ __forceinline__ long long cg_sgpr(long long v) {
     return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
-typedef __attribute__((address_space(1))) const void* cg_gptr;
-typedef __attribute__((address_space(3))) void* cg_lptr;
-
 template <class G, int ST>
 __device__ __forceinline__ void load_E_k(const float* __restrict__ Eg, int Cout, int n, int c0, float* Ek) {
     constexpr int V = G::V, VV = G::VV, CT = G::CT, KP = ST * V;
@@ -143,7 +140,7 @@ __device__ __forceinline__ void load_E_k(const float* __restrict__ Eg, int Cout,
             const int sidx = k / V, v = k - sidx * V;
             const int c = cu / V, u = cu - c * V;
             const float* gp = Eg + (((long long)n * ST + sidx) * Cout + c0 + c) * VV + u * V + v;
-            __builtin_amdgcn_global_load_lds((cg_gptr)gp, (cg_lptr)(Ek + piece * 256), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((tg_gptr)gp, (tg_lptr)(Ek + piece * 256), 16, 0, 0);
         }
     }
 }
@@ -761,17 +758,6 @@ __global__ __launch_bounds__(G::NT, ER ? 2 : 4) void ctrgc_fwd_kernel(const Ctrg
 //     retires in order): the next chunk's first wait allows exactly those stores to be still in flight.
 // Applies to S = 3, Cout % 16 == 0, Cin % 16 == 0, 16-byte aligned x and w3; everything else stays on ctrgc_fwd_kernel.
 // ---------------------------------------------------------------------------
-#define CG_VMCNT_CASE(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-__device__ __forceinline__ void cg_wait_vmcnt(int n) {     // n is wave-uniform
-    switch (n) {
-        CG_VMCNT_CASE(0) CG_VMCNT_CASE(1) CG_VMCNT_CASE(2) CG_VMCNT_CASE(3) CG_VMCNT_CASE(4) CG_VMCNT_CASE(5) CG_VMCNT_CASE(6)
-        CG_VMCNT_CASE(7) CG_VMCNT_CASE(8) CG_VMCNT_CASE(9) CG_VMCNT_CASE(10) CG_VMCNT_CASE(11) CG_VMCNT_CASE(12)
-        CG_VMCNT_CASE(13) CG_VMCNT_CASE(14) CG_VMCNT_CASE(15) CG_VMCNT_CASE(16) CG_VMCNT_CASE(17) CG_VMCNT_CASE(18)
-        CG_VMCNT_CASE(19) CG_VMCNT_CASE(20) CG_VMCNT_CASE(21) CG_VMCNT_CASE(22) CG_VMCNT_CASE(23) CG_VMCNT_CASE(24)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
 template <class G, int ST>
 struct Fwd2 {
     using P = Plan<G, ST>;
@@ -851,7 +837,7 @@ __global__ __launch_bounds__(G::NT, 4) void ctrgc_fwd2_kernel(const CtrgcArgs a,
                 unsigned o = poff[i];
                 asm volatile("" : "+v"(o));                                  // base + o is formed HERE (as scalar base + lane offset), not as a 64-bit lane pointer per piece and base carried through the launch
                 if (__ballot(ok) != 0ull) {                                  // the request exists or not for the whole wave: it is counted
-                    if (ok) __builtin_amdgcn_global_load_lds((cg_gptr)cg_at<float>(base, o), (cg_lptr)(st + p * 256), 16, 0, 0);
+                    if (ok) __builtin_amdgcn_global_load_lds((tg_gptr)cg_at<float>(base, o), (tg_lptr)(st + p * 256), 16, 0, 0);
                     ++cnt;
                 }
             }
@@ -896,7 +882,7 @@ __global__ __launch_bounds__(G::NT, 4) void ctrgc_fwd2_kernel(const CtrgcArgs a,
         for (int kc = 0; kc < nk; ++kc) {
             // this wave's pieces of stage kc have landed: the stages requested after it (and, for the stages requested before the
             // copy-out's stores, those stores) may still be in flight
-            cg_wait_vmcnt((kc < NSTG - 1 ? after : 0) + (min(kc + NSTG - 2, nk - 1) - kc) * cnt);
+            tg_wait_vmcnt<24>((kc < NSTG - 1 ? after : 0) + (min(kc + NSTG - 2, nk - 1) - kc) * cnt);
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // everyone's have; nobody reads stage kc - 1 any more
             if (kc + NSTG - 1 < nk) issue((kc + NSTG - 1) % NSTG, t0, ncols, (kc + NSTG - 1) * SBK, tid);
             if (kc == 0 && tid < P::NR) Zs[tid] = b3v;                           // the z tile is dead from this barrier to the aggregation
@@ -1149,22 +1135,10 @@ static int fill_args(const tamgcn_ctrgc_desc* d, CtrgcArgs* a, const char* who, 
 
 static unsigned grid_blocks(const CtrgcArgs& a) { return 8u * (unsigned)ceil_div(a.N, 8) * (unsigned)a.nct; }
 
-static bool debug_occ() {                    // TAMGCN_DEBUG_OCC, read once per process
-    static const bool on = getenv("TAMGCN_DEBUG_OCC") != nullptr;
-    return on;
-}
-
-#define CTRGC_LAUNCH(KERNEL, GEO, ST_, FLAG, ...)                                                               \
+#define CTRGC_LAUNCH(KERNEL, GEO, ST_, ...)                                                                     \
     do {                                                                                                        \
-        static tg_devmask FLAG = 0;                                                                             \
-        constexpr size_t lds_ = Plan<GEO, ST_>::LDS;                                                            \
-        tg_allow_lds((const void*)KERNEL<GEO, ST_>, lds_, &FLAG);   /* exact size */                            \
-        if (debug_occ()) {                                                                                      \
-            int nb_ = -1;                                                                                       \
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, (const void*)KERNEL<GEO, ST_>, GEO::NT, lds_); \
-            fprintf(stderr, "[tamgcn] %s<CT %d, %d>: %d workgroups per CU (%zu B LDS, %d threads)\n", #KERNEL, GEO::CT, ST_, nb_, lds_, GEO::NT); \
-        }                                                                                                       \
-        hipLaunchKernelGGL((KERNEL<GEO, ST_>), dim3(grid_blocks(a)), dim3(GEO::NT), lds_, (hipStream_t)stream, __VA_ARGS__); \
+        constexpr size_t lds_ = Plan<GEO, ST_>::LDS;   /* the kernel's only request */                         \
+        tg_launch_lds<KERNEL<GEO, ST_>>(lds_, dim3(grid_blocks(a)), dim3(GEO::NT), lds_, (hipStream_t)stream, __VA_ARGS__); \
         tamgcn_note_kernel(#KERNEL "<Geo<%d, %d, %d, %d, %d>, %d>", GEO::V, GEO::CT, GEO::TB, GEO::NTQ, GEO::SBK, ST_); \
     } while (0)
 
@@ -1197,13 +1171,9 @@ extern "C" int tamgcn_ctrgc_build_e(const tamgcn_ctrgc_desc* d, float* E, void* 
     a.pq = d->pq; a.w4 = d->w4; a.b4 = d->b4; a.A = d->A; a.alpha = d->alpha; a.E = E;
     const size_t lds = sizeof(float) * ((size_t)d->R * d->V * d->V + 2 * (size_t)d->R * d->V);
     if (d->V == 20) {
-        static tg_devmask f = 0;
-        tg_allow_lds((const void*)ctrgc_E_kernel<20>, 160 * 1024, &f);
-        hipLaunchKernelGGL((ctrgc_E_kernel<20>), dim3(d->N * d->S), dim3(512), lds, (hipStream_t)stream, a);
+        tg_launch_lds<ctrgc_E_kernel<20>>(160 * 1024, dim3(d->N * d->S), dim3(512), lds, (hipStream_t)stream, a);
     } else {
-        static tg_devmask f = 0;
-        tg_allow_lds((const void*)ctrgc_E_kernel<25>, 160 * 1024, &f);
-        hipLaunchKernelGGL((ctrgc_E_kernel<25>), dim3(d->N * d->S), dim3(512), lds, (hipStream_t)stream, a);
+        tg_launch_lds<ctrgc_E_kernel<25>>(160 * 1024, dim3(d->N * d->S), dim3(512), lds, (hipStream_t)stream, a);
     }
     tamgcn_note_kernel("ctrgc_E_kernel<%d>", d->V);
     TG_LAUNCH_CHECK("tamgcn_ctrgc_build_e");
@@ -1228,32 +1198,23 @@ extern "C" int tamgcn_ctrgc_fwd(const tamgcn_ctrgc_desc* d, float* y, float* sta
     const bool al16 = (((uintptr_t)d->x.x1 | (uintptr_t)d->w3) & 15) == 0;
     const bool two = ct == 16 && d->S == 3 && mode != 0 && (d->Cin >= 64 || mode >= 2);   // the stem layer (Cin = 3) is faster with E resident inside the step (144 vs 173 us)
     if (two && d->Cin % 16 == 0 && al16 && (mode == 2 || (mode == 1 && d->Cin >= 256))) {
-        static tg_devmask fw3g = 0;
         constexpr size_t lds_ = Plan<G20W, 3>::LDS_NOE;
         static_assert(lds_ <= 80 * 1024, "two workgroups per CU");
         // two stages: a third one (it fits, reaching into the z tile while the K loop runs) was measured SLOWER at every shape --
         // 231 / 450 / 316 / 607 / 487 us against 223 / 422 / 292 / 564 / 440 (l2 l5 l6 l8 l9, same box): more requests in flight
         // load the L2 -> LDS path further, they do not hide its latency
-        tg_allow_lds((const void*)ctrgc_fwd2_kernel<G20W, 3, 2>, lds_, &fw3g);
-        hipLaunchKernelGGL((ctrgc_fwd2_kernel<G20W, 3, 2>), dim3(grid_blocks(a)), dim3(G20W::NT), lds_, (hipStream_t)stream, a, y, stats_part, x3_out);
+        tg_launch_lds<ctrgc_fwd2_kernel<G20W, 3, 2>>(lds_, dim3(grid_blocks(a)), dim3(G20W::NT), lds_, (hipStream_t)stream, a, y, stats_part, x3_out);
         tamgcn_note_kernel("ctrgc_fwd2_kernel<Geo<%d, %d, %d, %d, %d>, 3>", G20W::V, G20W::CT, G20W::TB, G20W::NTQ, G20W::SBK);
     } else if (two) {
-        static tg_devmask fw3e = 0;
         constexpr size_t lds_ = Plan<G20W, 3>::LDS_NOE;
-        tg_allow_lds((const void*)ctrgc_fwd_kernel<G20W, 3, false>, lds_, &fw3e);
-        if (debug_occ()) {
-            int nb_ = -1;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, (const void*)ctrgc_fwd_kernel<G20W, 3, false>, G20W::NT, lds_);
-            fprintf(stderr, "[tamgcn] ctrgc_fwd_kernel<CT 16, 3, E from L2>: %d workgroups per CU (%zu B LDS)\n", nb_, lds_);
-        }
-        hipLaunchKernelGGL((ctrgc_fwd_kernel<G20W, 3, false>), dim3(grid_blocks(a)), dim3(G20W::NT), lds_, (hipStream_t)stream, a, y, stats_part, x3_out);
+        tg_launch_lds<ctrgc_fwd_kernel<G20W, 3, false>>(lds_, dim3(grid_blocks(a)), dim3(G20W::NT), lds_, (hipStream_t)stream, a, y, stats_part, x3_out);
         tamgcn_note_kernel("ctrgc_fwd_kernel<Geo<%d, %d, %d, %d, %d>, 3, E from L2>", G20W::V, G20W::CT, G20W::TB, G20W::NTQ, G20W::SBK);
     } else if (ct == 16) {
-        if (d->S == 3) CTRGC_LAUNCH(ctrgc_fwd_kernel, G20W, 3, fw3, a, y, stats_part, x3_out);
-        else CTRGC_LAUNCH(ctrgc_fwd_kernel, G20W, 1, fw1, a, y, stats_part, x3_out);
+        if (d->S == 3) CTRGC_LAUNCH(ctrgc_fwd_kernel, G20W, 3, a, y, stats_part, x3_out);
+        else CTRGC_LAUNCH(ctrgc_fwd_kernel, G20W, 1, a, y, stats_part, x3_out);
     } else {
-        if (d->S == 3) CTRGC_LAUNCH(ctrgc_fwd_kernel, G20, 3, f3, a, y, stats_part, x3_out);
-        else CTRGC_LAUNCH(ctrgc_fwd_kernel, G20, 1, f1, a, y, stats_part, x3_out);
+        if (d->S == 3) CTRGC_LAUNCH(ctrgc_fwd_kernel, G20, 3, a, y, stats_part, x3_out);
+        else CTRGC_LAUNCH(ctrgc_fwd_kernel, G20, 1, a, y, stats_part, x3_out);
     }
     TG_LAUNCH_CHECK("tamgcn_ctrgc_fwd");
     return 0;
@@ -1267,8 +1228,8 @@ extern "C" int tamgcn_ctrgc_bwd_dx3(const tamgcn_ctrgc_desc* d, const tamgcn_src
     if (!dd.w3) dd.w3 = (const float*)d->E;
     if (!dd.b3) dd.b3 = (const float*)d->E;
     if (fill_args(&dd, &a, "tamgcn_ctrgc_bwd_dx3", G20::CT)) return -1;
-    if (d->S == 3) CTRGC_LAUNCH(ctrgc_bwd_dx3_kernel, G20, 3, f3, a, make_src(*dy), dx3, db3_part);
-    else CTRGC_LAUNCH(ctrgc_bwd_dx3_kernel, G20, 1, f1, a, make_src(*dy), dx3, db3_part);
+    if (d->S == 3) CTRGC_LAUNCH(ctrgc_bwd_dx3_kernel, G20, 3, a, make_src(*dy), dx3, db3_part);
+    else CTRGC_LAUNCH(ctrgc_bwd_dx3_kernel, G20, 1, a, make_src(*dy), dx3, db3_part);
     TG_LAUNCH_CHECK("tamgcn_ctrgc_bwd_dx3");
     return 0;
 }

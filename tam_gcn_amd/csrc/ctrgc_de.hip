@@ -200,9 +200,6 @@ constexpr int tail_pitch(int vv) {   // smallest pitch >= vv with pitch % 16 == 
     return p;
 }
 
-typedef __attribute__((address_space(1))) const void* de_gptr;
-typedef __attribute__((address_space(3))) void* de_lptr;
-
 template <int V, int RT, bool DBR>
 __global__ __launch_bounds__(512) void ctrgc_de_tail_kernel(const TailArgs a) {
     // 512 threads: the kernel holds one workgroup per CU at R = 32 (D alone is 51 KB), so parallelism inside the
@@ -244,7 +241,7 @@ __global__ __launch_bounds__(512) void ctrgc_de_tail_kernel(const TailArgs a) {
             if (piece < NPIECE) {
                 int f = piece * 256 + lane * 4;
                 if (f > CH - 4) f = CH - 4;
-                __builtin_amdgcn_global_load_lds((de_gptr)(dEg + (long long)c0 * VV + f), (de_lptr)(DEs + buf * CHP + piece * 256), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((tg_gptr)(dEg + (long long)c0 * VV + f), (tg_lptr)(DEs + buf * CHP + piece * 256), 16, 0, 0);
             }
         }
     };
@@ -299,10 +296,10 @@ __global__ __launch_bounds__(512) void ctrgc_de_tail_kernel(const TailArgs a) {
             for (int piece = 0; piece < WQ / 256; ++piece) {
                 int f = piece * 256 + lane * 4;
                 if (f > 16 * a.R - 4) f = 16 * a.R - 4;
-                __builtin_amdgcn_global_load_lds((de_gptr)(g4 + f), (de_lptr)(dst + piece * 256), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((tg_gptr)(g4 + f), (tg_lptr)(dst + piece * 256), 16, 0, 0);
             }
             const int fb = lane < 4 ? lane * 4 : 12;
-            __builtin_amdgcn_global_load_lds((de_gptr)(a.b4 + s * a.Cout + c0 + fb), (de_lptr)(dst + WQ), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((tg_gptr)(a.b4 + s * a.Cout + c0 + fb), (tg_lptr)(dst + WQ), 16, 0, 0);
         }
     };
     issue_small(cbeg, 0);
@@ -687,11 +684,6 @@ __global__ __launch_bounds__(512) void ctrgc_de_tail_reg_kernel(const TailArgs a
     }
 }
 
-template <typename K>
-void allow_lds(K kernel, size_t lds, tg_devmask* done) {       // once per instantiation and device
-    if (lds > 48 * 1024) tg_allow_lds(reinterpret_cast<const void*>(kernel), lds, done);
-}
-
 template <int V>
 size_t tail_lds(int R, int RT, bool dbr) {
     const size_t chp = ((size_t)16 * V * V + 255) & ~(size_t)255;
@@ -707,10 +699,8 @@ size_t tail_reg_lds(int R, int RT) { return sizeof(float) * ((size_t)(R + 16) * 
 #define DE_ACC_CASE(VV_, SS_)                                                                                          \
     if (d->V == VV_ && d->S == SS_) {                                                                                  \
         using G = AccGeo<VV_, SS_>;                                                                                    \
-        static tg_devmask flag = 0;                                                                                    \
-        allow_lds(ctrgc_de_acc_kernel<G>, G::LDS, &flag);                                                              \
-        hipLaunchKernelGGL((ctrgc_de_acc_kernel<G>), dim3(d->N * (d->Cout / G::CA)), dim3(G::NT), G::LDS, (hipStream_t)stream, \
-                           d->N, d->Cout, d->T, x3, make_src(*dy), dE);                                                \
+        tg_launch_lds<ctrgc_de_acc_kernel<G>>(G::LDS, dim3(d->N * (d->Cout / G::CA)), dim3(G::NT), G::LDS, (hipStream_t)stream, \
+                                              d->N, d->Cout, d->T, x3, make_src(*dy), dE);                             \
         tamgcn_note_kernel("ctrgc_de_acc_kernel<AccGeo<%d, %d>>", VV_, SS_);                                           \
         launched = true;                                                                                               \
     }
@@ -728,19 +718,15 @@ extern "C" int tamgcn_ctrgc_bwd_de_acc(const tamgcn_ctrgc_desc* d, const tamgcn_
 
 #define DE_TAIL_REG_CASE(VV_, RT_)                                                                                     \
     if (d->V == VV_ && rt == RT_) {                                                                                    \
-        static tg_devmask flag = 0;                                                                                    \
-        const size_t lds = tail_reg_lds<VV_>(d->R, RT_);                                                               \
-        allow_lds(ctrgc_de_tail_reg_kernel<VV_, RT_>, tail_reg_lds<VV_>(32, 2), &flag);                                \
-        hipLaunchKernelGGL((ctrgc_de_tail_reg_kernel<VV_, RT_>), dim3(d->N * d->S * groups), dim3(512), lds, (hipStream_t)stream, a); \
+        tg_launch_lds<ctrgc_de_tail_reg_kernel<VV_, RT_>>(tail_reg_lds<VV_>(32, 2), dim3(d->N * d->S * groups), dim3(512),   \
+                                                          tail_reg_lds<VV_>(d->R, RT_), (hipStream_t)stream, a);       \
         tamgcn_note_kernel("ctrgc_de_tail_reg_kernel<%d, %d>", VV_, RT_);                                              \
         launched = true;                                                                                               \
     }
 #define DE_TAIL_CASE(VV_, RT_, DBR_)                                                                                   \
     if (d->V == VV_ && rt == RT_ && dbr == DBR_) {                                                                     \
-        static tg_devmask flag = 0;                                                                                    \
-        const size_t lds = tail_lds<VV_>(d->R, RT_, DBR_);                                                             \
-        allow_lds(ctrgc_de_tail_kernel<VV_, RT_, DBR_>, tail_lds<VV_>(RT_ == 2 ? 32 : 16, RT_, DBR_), &flag);          \
-        hipLaunchKernelGGL((ctrgc_de_tail_kernel<VV_, RT_, DBR_>), dim3(d->N * d->S * groups), dim3(512), lds, (hipStream_t)stream, a); \
+        tg_launch_lds<ctrgc_de_tail_kernel<VV_, RT_, DBR_>>(tail_lds<VV_>(RT_ == 2 ? 32 : 16, RT_, DBR_), dim3(d->N * d->S * groups), dim3(512), \
+                                                            tail_lds<VV_>(d->R, RT_, DBR_), (hipStream_t)stream, a);   \
         tamgcn_note_kernel("ctrgc_de_tail_kernel<%d, %d, %d>", VV_, RT_, (int)DBR_);                                   \
         launched = true;                                                                                               \
     }

@@ -671,11 +671,8 @@ extern "C" int tamgcn_ctrgc_tiled_build_e(const tamgcn_ctrgc_desc* d, float* E, 
     a.pq = d->pq; a.w4 = d->w4; a.b4 = d->b4; a.A = d->A; a.alpha = d->alpha; a.E = E;
     const int UT = 512 / d->V, NUC = d->V / UT;
     const size_t lds = sizeof(float) * ((size_t)d->R * (512 + 16) + (size_t)d->R * (UT + d->V));
-    static tg_devmask f64 = 0, f32 = 0;
-    TL_DISPATCH_V(tg_allow_lds((const void*)ctrgc_E_tiled_kernel<64>, 80 * 1024, &f64);
-                  hipLaunchKernelGGL((ctrgc_E_tiled_kernel<64>), dim3(d->N * d->S * NUC), dim3(512), lds, (hipStream_t)stream, a),
-                  tg_allow_lds((const void*)ctrgc_E_tiled_kernel<32>, 80 * 1024, &f32);
-                  hipLaunchKernelGGL((ctrgc_E_tiled_kernel<32>), dim3(d->N * d->S * NUC), dim3(512), lds, (hipStream_t)stream, a));
+    TL_DISPATCH_V(tg_launch_lds<ctrgc_E_tiled_kernel<64>>(80 * 1024, dim3(d->N * d->S * NUC), dim3(512), lds, (hipStream_t)stream, a),
+                  tg_launch_lds<ctrgc_E_tiled_kernel<32>>(80 * 1024, dim3(d->N * d->S * NUC), dim3(512), lds, (hipStream_t)stream, a));
     tamgcn_note_kernel("ctrgc_E_tiled_kernel<%d>", d->V);
     TG_LAUNCH_CHECK("tamgcn_ctrgc_tiled_build_e");
     return 0;
@@ -683,10 +680,8 @@ extern "C" int tamgcn_ctrgc_tiled_build_e(const tamgcn_ctrgc_desc* d, float* E, 
 
 #define TL_CASE(KERNEL, VV_, SS_, LDS_, ...)                                                                          \
     if (d->V == VV_ && d->S == SS_) {                                                                                 \
-        static tg_devmask flag = 0;                                                                                   \
-        const size_t lds_ = (LDS_);                                                                                   \
-        tg_allow_lds((const void*)KERNEL<VV_, SS_>, lds_, &flag);                                                     \
-        hipLaunchKernelGGL((KERNEL<VV_, SS_>), dim3((unsigned)(d->N * d->Cout)), dim3(256), lds_, (hipStream_t)stream, __VA_ARGS__); \
+        const size_t lds_ = (LDS_);   /* fixed per instantiation */                                                   \
+        tg_launch_lds<KERNEL<VV_, SS_>>(lds_, dim3((unsigned)(d->N * d->Cout)), dim3(256), lds_, (hipStream_t)stream, __VA_ARGS__); \
         tamgcn_note_kernel(#KERNEL "<%d, %d>", VV_, SS_);                                                             \
         launched = true;                                                                                              \
     }
@@ -758,11 +753,10 @@ extern "C" int tamgcn_ctrgc_tiled_de_acc(const tamgcn_ctrgc_desc* d, const tamgc
 
 #define TL_TAIL_CASE(VV_, RT_)                                                                                        \
     if (d->V == VV_ && rt == RT_) {                                                                                   \
-        static tg_devmask flag = 0;                                                                                   \
         const int UT = 512 / VV_;                                                                                     \
         const size_t lds = sizeof(float) * ((size_t)(d->R + 16) * (512 + 2) + 8 * 16 * RT_ * 16 + (size_t)d->R * (UT + VV_)); \
-        tg_allow_lds((const void*)ctrgc_de_tail_tiled_kernel<VV_, RT_>, 136 * 1024, &flag);   /* R = 32: 124 KB; static LDS on top */ \
-        hipLaunchKernelGGL((ctrgc_de_tail_tiled_kernel<VV_, RT_>), dim3(d->N * d->S * (VV_ / UT)), dim3(512), lds, (hipStream_t)stream, a); \
+        /* bound: R = 32 is 124 KB; static LDS on top */                                                              \
+        tg_launch_lds<ctrgc_de_tail_tiled_kernel<VV_, RT_>>(136 * 1024, dim3(d->N * d->S * (VV_ / UT)), dim3(512), lds, (hipStream_t)stream, a); \
         tamgcn_note_kernel("ctrgc_de_tail_tiled_kernel<%d, %d>", VV_, RT_);                                           \
         launched = true;                                                                                              \
     }

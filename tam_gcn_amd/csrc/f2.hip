@@ -27,9 +27,6 @@ namespace {
 constexpr int F2_NT = 256, F2_V = 20, F2_VV = 400, F2_BT = 4, F2_NCT = 5, F2_PB = 84;   // 4 frames x 20 joints = 80 columns = 5 MFMA tiles
 // pitch 84: the four k rows (4*kq + i) a fragment read touches sit 4*84 = 16 (mod 64) banks apart: conflict-free
 
-typedef __attribute__((address_space(1))) const void* f2_gptr;
-typedef __attribute__((address_space(3))) void* f2_lptr;
-
 // A fragment of one 16-k block: lane (j, kq) holds A[row j][k0 + 4*kq + i], i = 0..3 (MFMA step i of the block contracts
 // k = k0 + 4*kq + i on BOTH operands: any bijection between (step, kq) and k is a valid K order)
 __device__ __forceinline__ void f2_load_a(const float* arow, int K, int k0, int kq, bool vec, float (&a)[4]) {
@@ -306,7 +303,7 @@ __global__ __launch_bounds__(F2_NT) void f2_gcn_kernel(const F2GcnArgs a) {
         int f = q * 256 + lane * 4;
         if (f > CT * VV - 4) f = CT * VV - 4;                     // lanes past the run re-read its last slot into the padding
         const float* g = a.E + (((long long)n * a.S + s) * a.Cout + c0) * VV + f;
-        __builtin_amdgcn_global_load_lds((f2_gptr)g, (f2_lptr)(Es + s * ES + q * 256), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((tg_gptr)g, (tg_lptr)(Es + s * ES + q * 256), 16, 0, 0);
     }
     const int rt = wave & 1, kh = wave >> 1;
     const float* arow;
@@ -627,10 +624,7 @@ int f2_fill(const tamgcn_f2_gcn_desc* d, F2GcnArgs* a, const char* who) {
 extern "C" int tamgcn_f2_e(const tamgcn_f2_gcn_desc* d, void* stream) {
     F2GcnArgs a;
     if (f2_fill(d, &a, "tamgcn_f2_e")) return -1;
-    static tg_devmask flag = 0;
-    const size_t lds = f2_e_lds(d->Cin, d->R);
-    tg_allow_lds((const void*)f2_e_kernel, f2_e_lds(256, 32), &flag);
-    hipLaunchKernelGGL(f2_e_kernel, dim3(d->S * (d->Cout / 16), d->N), dim3(F2_NT), lds, (hipStream_t)stream, a);
+    tg_launch_lds<f2_e_kernel>(f2_e_lds(256, 32), dim3(d->S * (d->Cout / 16), d->N), dim3(F2_NT), f2_e_lds(d->Cin, d->R), (hipStream_t)stream, a);
     tamgcn_note_kernel("f2_e_kernel");
     TG_LAUNCH_CHECK("tamgcn_f2_e");
     return 0;
@@ -640,10 +634,7 @@ extern "C" int tamgcn_f2_gcn(const tamgcn_f2_gcn_desc* d, void* stream) {
     F2GcnArgs a;
     if (f2_fill(d, &a, "tamgcn_f2_gcn")) return -1;
     TG_CHECK(d->sum && d->diff && al16(d->sum) && al16(d->diff), "tamgcn_f2_gcn: null or misaligned output");
-    static tg_devmask flag = 0;
-    const size_t lds = f2_gcn_lds(d->Cin);
-    tg_allow_lds((const void*)f2_gcn_kernel, f2_gcn_lds(256), &flag);
-    hipLaunchKernelGGL(f2_gcn_kernel, dim3(ceil_div(d->T, F2_BT) * (d->Cout / F2_CT), d->N), dim3(F2_NT), lds, (hipStream_t)stream, a);
+    tg_launch_lds<f2_gcn_kernel>(f2_gcn_lds(256), dim3(ceil_div(d->T, F2_BT) * (d->Cout / F2_CT), d->N), dim3(F2_NT), f2_gcn_lds(d->Cin), (hipStream_t)stream, a);
     tamgcn_note_kernel("f2_gcn_kernel");
     TG_LAUNCH_CHECK("tamgcn_f2_gcn");
     return 0;
@@ -661,9 +652,7 @@ extern "C" int tamgcn_f2_gemm(const tamgcn_f2_gemm_desc* d, void* stream) {
     a.N = d->N; a.K = d->K; a.M = d->M; a.T = d->T; a.mode = d->mode; a.relu_rows = d->relu_rows;
     a.vec = d->K % 16 == 0 && al16(d->w);
     a.x = d->x; a.w = d->w; a.b = d->b; a.add = d->add; a.out = d->out;
-    static tg_devmask flag = 0;
-    tg_allow_lds((const void*)f2_gemm_kernel, f2_gemm_lds(256), &flag);
-    hipLaunchKernelGGL(f2_gemm_kernel, dim3(ceil_div(d->T, F2_BT) * (d->M / 16), d->N), dim3(F2_NT), f2_gemm_lds(d->K), (hipStream_t)stream, a);
+    tg_launch_lds<f2_gemm_kernel>(f2_gemm_lds(256), dim3(ceil_div(d->T, F2_BT) * (d->M / 16), d->N), dim3(F2_NT), f2_gemm_lds(d->K), (hipStream_t)stream, a);
     tamgcn_note_kernel("f2_gemm_kernel");
     TG_LAUNCH_CHECK("tamgcn_f2_gemm");
     return 0;
@@ -702,9 +691,7 @@ extern "C" int tamgcn_f2_tcn(const tamgcn_f2_tcn_desc* d, void* stream) {
     a.h = d->h; a.sp = d->sp; a.tp = d->tp; a.x = d->x; a.wr = d->wr; a.br = d->br; a.out = d->out; a.xpart = d->xpart;
     const size_t lds = f2_tcn_lds(d->Cin, d->Cb, d->res_mode);
     TG_CHECK(lds <= 160 * 1024, "tamgcn_f2_tcn: %zu bytes of LDS", lds);
-    static tg_devmask flag = 0;
-    tg_allow_lds((const void*)f2_tcn_kernel, 160 * 1024, &flag);
-    hipLaunchKernelGGL(f2_tcn_kernel, dim3(ceil_div(a.T2, F2_BT) * (d->Cout / 16), d->N), dim3(F2_NT), lds, (hipStream_t)stream, a);
+    tg_launch_lds<f2_tcn_kernel>(160 * 1024, dim3(ceil_div(a.T2, F2_BT) * (d->Cout / 16), d->N), dim3(F2_NT), lds, (hipStream_t)stream, a);
     tamgcn_note_kernel("f2_tcn_kernel");
     TG_LAUNCH_CHECK("tamgcn_f2_tcn");
     return 0;

@@ -56,17 +56,14 @@ struct TcArgs {
     int BT, TIN, LB, Vs, Vp, nsl, mh, ntiles, nby, ntt, tpw;    // ntiles = ceil(ntt / tpw) * nsl workgroup units per (sample, branch)
 };
 
-// x / d for 0 <= x < 2^20 and 4 <= d <= 64 through the reciprocal (rcp = 1.0f / d): three VALU instead of the ~25 of an
-// integer division.  (x + 0.5) / d lies at least 0.5 / d >= 0.0078 from an integer, float rounding moves it by < 0.07.
-// The kernel's address arithmetic had ~30 divisions per tile and lane: more issue slots than its MFMAs
-// (tools/tconv_phases.py: 3.7 k of 13.6 k clocks per tile went into "issuing 13 loads").
-__device__ __forceinline__ int tc_div(int x, float rcp) { return (int)(((float)x + 0.5f) * rcp); }
+// Divisions by Vs / Vp go through tg_rcp_div (x < 2^20, 4 <= d <= 64): the kernel's address arithmetic had ~30 divisions per
+// tile and lane, more issue slots than its MFMAs (tools/tconv_phases.py: 3.7 k of 13.6 k clocks per tile went into "issuing 13 loads").
 
 // four consecutive columns col0..col0+3 of one output row: contiguous in HBM (full-width tiles: the row is the flat
 // (t, v) run; joint slices: Vs % 4 == 0 keeps the group inside its frame).  Only a full-width tile can end in a partial group.
 __device__ __forceinline__ long long tc_off(int V, int Vs, float rVs, int v0, int t0, int col0, bool flat) {
     if (flat) return (long long)t0 * V + col0;
-    const int fr = tc_div(col0, rVs);
+    const int fr = tg_rcp_div(col0, rVs);
     return (long long)(t0 + fr) * V + v0 + (col0 - fr * Vs);
 }
 
@@ -102,7 +99,7 @@ __global__ __launch_bounds__(TC_NT) void tpool_kernel(const TcArgs a) {
             for (int u = 0; u < PB; ++u) {                 // every load unconditional (clamped to the centre row / a valid group)
                 const int c = cb + 64 * u;
                 const int cc = c < c_hi ? c : c_lo;
-                const int fr = tc_div(cc, rVs), v = cc - fr * Vs;
+                const int fr = tg_rcp_div(cc, rVs), v = cc - fr * Vs;
                 vec[u] = c < c_hi && v + 4 <= Vs && c + 4 <= c_hi;
                 const int vv = v + 4 <= Vs ? v : 0;         // a group that leaves its frame is redone element-wise below
                 const int th = fr * a.stride;
@@ -115,7 +112,7 @@ __global__ __launch_bounds__(TC_NT) void tpool_kernel(const TcArgs a) {
             for (int u = 0; u < PB; ++u) {
                 const int c = cb + 64 * u;
                 if (vec[u]) {
-                    const int fr = tc_div(c, rVs), v = c - fr * Vs;
+                    const int fr = tg_rcp_div(c, rVs), v = c - fr * Vs;
                     f32x4 o;
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -125,7 +122,7 @@ __global__ __launch_bounds__(TC_NT) void tpool_kernel(const TcArgs a) {
                     s2 = fmaf(o[0], o[0], fmaf(o[1], o[1], fmaf(o[2], o[2], fmaf(o[3], o[3], s2))));
                 } else if (c < c_hi) {
                     for (int r = 0; r < 4 && c + r < c_hi; ++r) {
-                        const int cc = c + r, f2 = tc_div(cc, rVs), v2 = cc - f2 * Vs, th = f2 * a.stride;
+                        const int cc = c + r, f2 = tg_rcp_div(cc, rVs), v2 = cc - f2 * Vs, th = f2 * a.stride;
                         const float* p = xrow + (long long)th * V + v0 + v2;
                         float m = fmaf(c1, p[0], c0);
                         if (th > 0) m = fmaxf(m, fmaf(c1, p[-V], c0));
@@ -215,7 +212,7 @@ __global__ __launch_bounds__(TC_NT * MT, MT == 4 ? 4 : 2) void tconv_kernel(cons
 #pragma unroll
         for (int i = 0; i < NPFW; ++i) {
             const int pos = (psub + 16 * i) << 2;
-            const int slot = tc_div(pos, rVp), v = pos - slot * Vp;
+            const int slot = tg_rcp_div(pos, rVp), v = pos - slot * Vp;
             int th = tin0 + slot;
             bool ok = (psub + 16 * i) < LB4 && th >= 0;
             if (a.up == 2) { ok = ok && !(th & 1); th >>= 1; }      // zero-upsampled source of a stride-2 forward (host: up <= 2)
@@ -325,7 +322,7 @@ __global__ __launch_bounds__(TC_NT * MT, MT == 4 ? 4 : 2) void tconv_kernel(cons
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
             const int col = (wave * CT + c) * 16 + j;
-            if (col < ncols) { const int fr = tc_div(col, rVs); boff[c] = fr * a.stride * Vp + (col - fr * Vs); }
+            if (col < ncols) { const int fr = tg_rcp_div(col, rVs); boff[c] = fr * a.stride * Vp + (col - fr * Vs); }
             else boff[c] = 0;                                  // padding tile: reads in-bounds data, never stored
         }
 #pragma unroll
@@ -487,9 +484,7 @@ template <bool BWD>
 static int tc_launch(const TcArgs& a, const TcPlan& p, int KT, dim3 grid, hipStream_t s) {
 #define TC_CASE(MT_, CT_, KT_)                                                                                          \
     if (p.mt == MT_ && p.ct == CT_ && KT == KT_) {                                                                      \
-        static tg_devmask done = 0;                                                                                     \
-        tg_allow_lds((const void*)tconv_kernel<MT_, CT_, KT_, BWD>, 160 * 1024, &done);                                 \
-        hipLaunchKernelGGL((tconv_kernel<MT_, CT_, KT_, BWD>), grid, dim3(TC_NT * MT_), p.lds, s, a);                   \
+        tg_launch_lds<tconv_kernel<MT_, CT_, KT_, BWD>>(160 * 1024, grid, dim3(TC_NT * MT_), p.lds, s, a);              \
         tamgcn_note_kernel("tconv_kernel<%d, %d, %d, %s>", MT_, CT_, KT_, BWD ? "true" : "false");                         \
         return 0;                                                                                                       \
     }
@@ -714,7 +709,7 @@ __global__ __launch_bounds__(TW_NT, 2) void tconv_wgrad_kernel(const TwArgs a) {
 #pragma unroll
             for (int i = 0; i < TC_NPF; ++i) {
                 const int pos = (psub + 16 * i) << 2;
-                const int slot = tc_div(pos, rVp), v = pos - slot * Vp;
+                const int slot = tg_rcp_div(pos, rVp), v = pos - slot * Vp;
                 const int th = tin0 + slot;
                 const bool ok = psub + 16 * i < LB4 && th >= 0 && th < a.T_in;
                 if (ok) okm |= 1u << i;
@@ -751,7 +746,7 @@ __global__ __launch_bounds__(TW_NT, 2) void tconv_wgrad_kernel(const TwArgs a) {
                 const int col = (psub + 16 * i) << 2;
                 const bool full = col + 4 <= ncols;
                 const int cc = full ? col : 0;
-                const int fr = tc_div(cc, rVs), v = cc - fr * Vs;
+                const int fr = tg_rcp_div(cc, rVs), v = cc - fr * Vs;
                 goff[i] = flatg ? t0 * V + cc : (t0 + fr) * V + v0 + v;
                 g1[i] = *reinterpret_cast<const float4*>(a.gy.x1 + gb + goff[i]);
                 g2[i] = *reinterpret_cast<const float4*>(g2p + gb + goff[i]);
@@ -765,7 +760,7 @@ __global__ __launch_bounds__(TW_NT, 2) void tconv_wgrad_kernel(const TwArgs a) {
                         o[0] = fmaf(c1, g1[i].x, fmaf(c2, g2[i].x, c0)); o[1] = fmaf(c1, g1[i].y, fmaf(c2, g2[i].y, c0));
                         o[2] = fmaf(c1, g1[i].z, fmaf(c2, g2[i].z, c0)); o[3] = fmaf(c1, g1[i].w, fmaf(c2, g2[i].w, c0));
                     } else if (col < ncols) {              // the tile's last, partial group (V % 4 != 0): element-wise
-                        const int fr = tc_div(col, rVs), v = col - fr * Vs;
+                        const int fr = tg_rcp_div(col, rVs), v = col - fr * Vs;
                         const long long off = flatg ? (long long)t0 * V + col : (long long)(t0 + fr) * V + v0 + v;
                         for (int r = 0; r < 4 && col + r < ncols; ++r)
                             o[r] = fmaf(c1, a.gy.x1[gb + off + r], fmaf(c2, g2p[gb + off + r], c0));
@@ -781,7 +776,7 @@ __global__ __launch_bounds__(TW_NT, 2) void tconv_wgrad_kernel(const TwArgs a) {
         for (int g = wave; g < ngrp; g += 4) {
             const int col = 4 * g + kq;                    // this lane's contraction column (a column >= ncols has a zero in Gs)
             const int cc = col < ncols ? col : 0;
-            const int fr = tc_div(cc, rVs);
+            const int fr = tg_rcp_div(cc, rVs);
             const int boff = fr * a.stride * Vp + (cc - fr * Vs);
             float bv[MTL];
 #pragma unroll
@@ -880,8 +875,8 @@ extern "C" int tamgcn_tconv_wgrad_max_split(const tamgcn_tconv_desc* d) {
  * prologue (T_in frames); d->y = part [nsplit][nb][Cb][Cb][KT], d->yctot = nsplit.  Everything else as tamgcn_tconv_bwd. */
 extern "C" int tamgcn_tconv_wgrad(const tamgcn_tconv_desc* d, void* stream) {
     if (tc_common_checks(d, "tamgcn_tconv_wgrad", false)) return -1;
-    TG_CHECK((long long)d->mask->ctot * d->T_in * d->V < (1LL << 31), "tamgcn_tconv_wgrad: a sample exceeds 2^31 elements");
     TG_CHECK(d->mask && d->mask->x1 && !d->mask->x2, "tamgcn_tconv_wgrad: needs the forward source (single-source prologue) in `mask`");
+    TG_CHECK((long long)d->mask->ctot * d->T_in * d->V < (1LL << 31), "tamgcn_tconv_wgrad: a sample exceeds 2^31 elements");
     TG_CHECK(d->src.coff + d->nb * d->Cb <= d->src.ctot && d->mask->coff + d->nb * d->Cb <= d->mask->ctot, "tamgcn_tconv_wgrad: channel slice out of range");
     const int T_out = (d->T_in - 1) / d->stride + 1;
     TG_CHECK(d->T_out == T_out, "tamgcn_tconv_wgrad: T_out=%d inconsistent with T_in=%d stride=%d", d->T_out, d->T_in, d->stride);
@@ -901,9 +896,7 @@ extern "C" int tamgcn_tconv_wgrad(const tamgcn_tconv_desc* d, void* stream) {
     dim3 grid((unsigned)nsplit, (unsigned)(d->nb * p.nblk));
 #define TW_CASE(KTL_, MTL_, KT_)                                                                                        \
     if (p.ktl == KTL_ && p.mtl == MTL_ && d->KT == KT_) {                                                               \
-        static tg_devmask done = 0;                                                                                     \
-        tg_allow_lds((const void*)tconv_wgrad_kernel<KTL_, MTL_, KT_>, 160 * 1024, &done);                              \
-        hipLaunchKernelGGL((tconv_wgrad_kernel<KTL_, MTL_, KT_>), grid, dim3(TW_NT), p.lds, (hipStream_t)stream, a);    \
+        tg_launch_lds<tconv_wgrad_kernel<KTL_, MTL_, KT_>>(160 * 1024, grid, dim3(TW_NT), p.lds, (hipStream_t)stream, a); \
         tamgcn_note_kernel("tconv_wgrad_kernel<%d, %d, %d>", KTL_, MTL_, KT_);                                          \
         TG_LAUNCH_CHECK("tamgcn_tconv_wgrad");                                                                          \
         return 0;                                                                                                       \

@@ -30,7 +30,7 @@ def source_symbols():
         found += [f'{k}<{v}, {s}>' for k, v, s in re.findall(r'\bTL_CASE\((\w+), (\d+), (\d+),', src)]
         found += [f'ctrgc_de_tail_tiled_kernel<{v}, {rt}>' for v, rt in re.findall(r'\bTL_TAIL_CASE\((\d+), (\d+)\)', src)]
         found += [f'{k}<{GEO[g]}, {s}>' for k, g, s in re.findall(r'\bCTRGC_LAUNCH\((\w+), (G20W?), (\d+),', src)]
-        for k, args in re.findall(r'hipLaunchKernelGGL\(\((ctrgc_\w+)<([^<>()]*)>\)', src):     # launches outside the macros
+        for k, args in re.findall(r'(?:hipLaunchKernelGGL\(\(|tg_launch_lds<)(ctrgc_\w+)<([^<>()]*)>', src):   # launches outside the macros
             args = [a.strip() for a in args.split(',')]
             if all(re.fullmatch(r'\d+|true|false|G20W?', a) for a in args):                     # a macro's own launch has parameter names
                 found.append(f'{k}<{", ".join(GEO.get(a, a) for a in args)}>')

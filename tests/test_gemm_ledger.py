@@ -9,13 +9,14 @@ import torch
 import fp64_bars as B
 import test_gpu_gemm_forms as L
 
-CONV_HIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tam_gcn_amd', 'csrc', 'conv.hip')
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tam_gcn_amd', 'csrc')
+GEMM_HIP = ('conv.hip', 'wgrad.hip')                                    # the files that hold the GEMM family's dispatch
 LAUNCHERS = ('TG_GLDS_CASE', 'TG_CONV_CASE', 'launch_wgrad', 'launch_wgrad_glds_src')
 
 
 def source_tuples():
-    """(launcher, literal template / macro arguments) of every dispatch site in conv.hip."""
-    src = open(CONV_HIP).read()
+    """(launcher, literal template / macro arguments) of every dispatch site in conv.hip and wgrad.hip."""
+    src = ''.join(open(os.path.join(CSRC, f)).read() for f in GEMM_HIP)
     found = set()
     for name in LAUNCHERS:
         for m in re.finditer(r'\b' + name + r'\s*[(<]([^()<>]*)[)>]', src):
@@ -35,7 +36,7 @@ def test_every_dispatch_site_is_pinned_or_unreachable():
     assert not stale, f'ledger entries for instantiations conv.hip no longer has: {stale}'
     both = sorted(k for k in L.UNREACHABLE if k in pinned)
     assert not both, f'instantiations listed as unreachable but pinned by a case: {both}'
-    src = open(CONV_HIP).read()
+    src = open(os.path.join(CSRC, 'conv.hip')).read()
     assert 'tamgcn_note_kernel("conv_kernel")' in src and 'conv1x1_glds_split_kernel<2, false, 4>' in src
 
 

@@ -639,6 +639,28 @@ def test_tconv_fused_branches_fwd_bwd(case):
         assert float((dws[b].double().cpu() - wr).abs().max()) <= 3e-6 * float(wr.abs().max()), b
 
 
+def test_tconv_wgrad_without_forward_source_is_an_error():
+    """tamgcn_tconv_wgrad with mask = NULL (the forward's source is missing) returns an error that says so -- a host-side
+    check in front of any device work -- instead of reading through the null pointer."""
+    import ctypes as C
+    from tam_gcn_amd import _lib
+    from tam_gcn_amd.ops import S
+    N, Cb, T, V, KT, dils = 2, 16, 13, 20, 5, (1, 2)
+    gy = torch.zeros(N, len(dils) * Cb, T, V, device=dev())
+    part = torch.zeros(1, len(dils), Cb, Cb, KT, device=dev())
+    d = _lib.TconvDesc()
+    d.src = S(gy).c()
+    d.N, d.T_in, d.T_out, d.V, d.Cb, d.nb, d.KT, d.stride = N, T, T, V, Cb, len(dils), KT, 1
+    for b, dl in enumerate(dils):
+        d.dil[b] = dl
+    d.y, d.yctot, d.ycoff = part.data_ptr(), 1, 0
+    assert not d.mask                                              # a null pointer
+    rc = _lib.load().tamgcn_tconv_wgrad(C.byref(d), None)
+    assert rc != 0
+    assert 'forward source' in _lib.load().tamgcn_last_error().decode()
+    assert float(part.abs().max()) == 0
+
+
 def test_de_tail_r16_bit_identical_beside_other_streams_in_a_graph():
     """VERDICT r03 item 6 / ADVICE r03: the captured multi-stream step of round 3 was once ~1e-4 off in ONE model's
     gradients.  The records (gpurun_out r03c/r03d/r03e logs, quoted in DESIGN.md section 3) localise every occurrence to a

@@ -1,4 +1,4 @@
-"""What each part of the LDS-DMA weight-gradient kernel costs at the dW3 shapes of the C = 256 layers: side builds of conv.hip with
+"""What each part of the LDS-DMA weight-gradient kernel costs at the dW3 shapes of the C = 256 layers: side builds of wgrad.hip with
 -DTG_WKO=<mask> (results wrong by design), each in a child process.   here: python tools/wgrad_knockout.py build    box: python tools/wgrad_knockout.py
 (Round 4's run, which also carried a 256 x 256 tile that was rejected: profiles/r04_wgrad_knockout.txt.)"""
 import os, subprocess, sys
@@ -31,22 +31,22 @@ if len(sys.argv) > 1 and sys.argv[1] == 'build':       # knock-out side builds (
     B.build()
     os.makedirs(SIDE, exist_ok=True)
     csrc = os.path.join(ROOT, 'tam_gcn_amd', 'csrc')
-    others = [os.path.splitext(s)[0] + '.o' for s in B.sources() if os.path.basename(s) != 'conv.hip']
+    others = [os.path.splitext(s)[0] + '.o' for s in B.sources() if os.path.basename(s) != 'wgrad.hip']
     for old in os.listdir(SIDE):
         os.remove(os.path.join(SIDE, old))
     procs = []
     for m in MASKS:
-        o = os.path.join(SIDE, f'conv_wko{m}.o')
+        o = os.path.join(SIDE, f'wgrad_wko{m}.o')
         procs.append(subprocess.Popen([B._hipcc(), f'--offload-arch={B.ARCH}', '-O3', '-std=c++17', '-fPIC', f'-DTG_WKO={m}', '-c',
-                                       os.path.join(csrc, 'conv.hip'), '-o', o]))
+                                       os.path.join(csrc, 'wgrad.hip'), '-o', o]))
         if len(procs) == 4:
             for p in procs: assert p.wait() == 0
             procs = []
     for p in procs: assert p.wait() == 0
     for m in MASKS:
         subprocess.check_call([B._hipcc(), f'--offload-arch={B.ARCH}', '-shared', '-fPIC', '-o', os.path.join(SIDE, f'libtamgcn_wko{m}.so'),
-                               os.path.join(SIDE, f'conv_wko{m}.o')] + others)
-        os.remove(os.path.join(SIDE, f'conv_wko{m}.o'))
+                               os.path.join(SIDE, f'wgrad_wko{m}.o')] + others)
+        os.remove(os.path.join(SIDE, f'wgrad_wko{m}.o'))
     print('built', sorted(os.listdir(SIDE)))
     sys.exit(0)
 kos = [m for m in MASKS if os.path.exists(os.path.join(SIDE, f'libtamgcn_wko{m}.so'))]
