@@ -456,7 +456,8 @@ int tamgcn_feeder_transform_indexed(const double* raw, const long long* offsets,
 
 /* ---- f2: the eval-mode TCN_GCN_unit for small batches (callers: reference
  * ensemble/ensemble_ctrgcn_resnet_eval.py:147-183, models/resnet_gcn_attention.py:82-85, visual.py:53-55 -- model(data)
- * on 1..16 clips in eval mode).  Five launches per block, each 50..130 workgroups per clip; V = 20, S = 3.  The CALLER folds
+ * on 1..16 clips in eval mode).  Five launches per block, each 50..130 workgroups per clip; V = 20, S = 3 (V = 25: the f2v
+ * entry points below).  The CALLER folds
  * every eval-mode BatchNorm into the weights it passes (bn(W x + b) = (s W) x + (s b + t), s = gamma / sqrt(var + eps),
  * t = beta - mean s) -- tam_gcn_amd/f2.py does.  Reference arithmetic: models/ctrgcn.py:172-177, :252-261 (unit_gcn with
  * the offset_conv branch), :93-146 (MultiScale_TemporalConv), :281-283 (residual + ReLU of TCN_GCN_unit).
@@ -509,6 +510,27 @@ typedef struct tamgcn_f2_tcn_desc {
     float* xpart;                                    /* NULL | (N, ceil(T_out/4), Cout, V): per-tile frame sums of out */
 } tamgcn_f2_tcn_desc;
 int tamgcn_f2_tcn(const tamgcn_f2_tcn_desc* d, void* stream);
+
+/* ---- f2v: the same four stages for NTU-RGB+D's V = 25, S = 3 (tam_gcn_amd/csrc/f2v.hip, tam_gcn_amd/f2v.py): the f2 descriptors
+ * and the algebra above, unchanged, with d->V == 25.  What differs is where the frames lie.  Only the BLOCK's input and output
+ * are contiguous (N, C, T, 25); every buffer that lives between the launches of one block has frames (rows of joints) of
+ * VP = 28 floats, so that each is 16-byte aligned whatever T is:
+ *   _f2v_e     reads d->x (N, Cin, T, 25) contiguous, or d->xpart (N, ceil(T/4), Cin, 28);  writes d->E (N, S, Cout, 25, 28):
+ *              E[c][u][v] at u*28 + v, columns 25..27 zero
+ *   _f2v_gcn   reads d->x contiguous and d->E;  writes d->sum, d->diff (N, Cout, T, 28), columns 25..27 zero
+ *   _f2v_gemm  x, add, out: (N, K | M, T, 28).  Columns 25..27 of out get the epilogue of whatever x and add hold there
+ *              (finite when those are); no kernel lets them reach a joint
+ *   _f2v_tcn   d->h (N, Cout, T, 28);  d->x contiguous (N, Cin, T, 25);  d->out contiguous (N, Cout, T_out, 25);
+ *              d->xpart (N, ceil(T_out/4), Cout, 28): sums of out over each FOUR-frame tile (as f2), columns 25..27 zero
+ * Alignment: x and out 4 bytes, everything else 16.  The contiguous input is read in 16-byte pieces from dword-aligned
+ * addresses; the last piece of a frame reaches 12 bytes past it, so 12 readable bytes must follow x (tam_gcn_amd.ops.empty /
+ * with_slack); what is read there is discarded.  Each entry point computes its LDS request and refuses one above 160 KB
+ * (none arises for Cin, K <= 256, R <= 32, Cb <= 64).  Deterministic: two runs are bit-equal.
+ * Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed. */
+int tamgcn_f2v_e(const tamgcn_f2_gcn_desc* d, void* stream);
+int tamgcn_f2v_gcn(const tamgcn_f2_gcn_desc* d, void* stream);
+int tamgcn_f2v_gemm(const tamgcn_f2_gemm_desc* d, void* stream);
+int tamgcn_f2v_tcn(const tamgcn_f2_tcn_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------
  * Optimiser update in place over flat fp32 buffers of n elements (a ParamArena and its FlatGradBucket):

@@ -177,6 +177,10 @@ SIGNATURES = {
     'tamgcn_f2_gcn': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2_gemm': (_i, [C.POINTER(F2GemmDesc), _p]),
     'tamgcn_f2_tcn': (_i, [C.POINTER(F2TcnDesc), _p]),
+    'tamgcn_f2v_e': (_i, [C.POINTER(F2GcnDesc), _p]),
+    'tamgcn_f2v_gcn': (_i, [C.POINTER(F2GcnDesc), _p]),
+    'tamgcn_f2v_gemm': (_i, [C.POINTER(F2GemmDesc), _p]),
+    'tamgcn_f2v_tcn': (_i, [C.POINTER(F2TcnDesc), _p]),
     'tamgcn_optim_step': (_i, [C.POINTER(OptimDesc), _p]),
     'tamgcn_optim_step_guarded': (_i, [C.POINTER(OptimDesc), C.POINTER(GradGuard), _p]),
 }

@@ -112,11 +112,16 @@ def _ptr(t):
 
 
 class FusedEval:
+    """The V = 20 engine.  tam_gcn_amd.f2v.FusedEvalV derives the V = 25 one from it: the folding (_Block), the state key and
+    the re-fold are the same; V, FAMILY and _block (which registered operator runs a block) are what a family sets."""
+    V = 20
+    FAMILY = 'f2'
+
     def __init__(self, model):
         if model.training:
             raise ValueError('FusedEval: put the model in eval() mode first')
-        if getattr(model, 'num_point', None) != 20:
-            raise Unsupported(f'{getattr(model, "num_point", None)} joints (the f2 kernels are built for V = 20)')
+        if getattr(model, 'num_point', None) != self.V:
+            raise Unsupported(f'{getattr(model, "num_point", None)} joints (the {self.FAMILY} kernels are built for V = {self.V})')
         self.model = model
         self.lib = _lib.load()
         self._watch = list(model.parameters()) + list(model.buffers())
@@ -172,7 +177,7 @@ class FusedEval:
             N, T, VC = x.shape
             x = x.view(N, T, m.num_point, -1).permute(0, 3, 1, 2).contiguous().unsqueeze(-1)
         N, C_, T, V, M = x.shape
-        if V != 20:
+        if V != self.V:
             raise Unsupported(f'{V} joints')
         blocks = self._packed(x.device)
         h = Fn.StemFn.run(m.data_bn, x.contiguous(), m.data_bn.weight, m.data_bn.bias)

@@ -494,26 +494,40 @@ class Model(nn.Module):
         from .. import f2
         if not f2.enabled() or (x.shape[0] * (x.shape[4] if x.dim() == 5 else 1)) > f2.F2_MAX_CLIPS:
             return None
+        return self._small_batch_engine(x, '_tamgcn_f2', f2.FusedEval)
+
+    def _f2v(self, x):
+        """The same for 25-joint models (tam_gcn_amd.f2v): batches of at most F2V_MAX_FRAMES clip-persons x frames."""
+        if self.training or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32 or self.num_point != 25:
+            return None
+        from .. import f2v
+        frames = x.shape[0] * x.shape[4] * x.shape[2] if x.dim() == 5 else x.shape[0] * x.shape[1]
+        if not f2v.enabled() or frames > f2v.F2V_MAX_FRAMES:
+            return None
+        return self._small_batch_engine(x, '_tamgcn_f2v', f2v.FusedEvalV)
+
+    def _small_batch_engine(self, x, slot, cls):
+        from .. import f2
         # the engine calls the block operator directly: forward hooks on any sub-module would not fire.  A model that
         # carries hooks (feature extraction, visualisation: visual.py:53-55 style) takes the general path, module by module
         for mod in self.modules():
             if mod._forward_hooks or mod._forward_pre_hooks:
                 return None
-        eng = self.__dict__.get('_tamgcn_f2')
+        eng = self.__dict__.get(slot)
         if eng and eng.model is not self:                  # an nn.DataParallel replica carries the original's __dict__: its own engine
             eng = None
         if eng is None:
             try:
-                eng = f2.FusedEval(self)
+                eng = cls(self)
                 eng._packed(x.device)                      # geometry checks happen here, before anything is launched
             except f2.Unsupported:
                 eng = False                                # this model is outside the family: the general eval path serves it
-            self.__dict__['_tamgcn_f2'] = eng
+            self.__dict__[slot] = eng
         return eng or None
 
     def forward(self, x):
         x = _require_hip(x)
-        eng = self._f2(x)
+        eng = self._f2(x) or self._f2v(x)
         if eng is not None:
             return eng(x)
         if isinstance(self.drop_out, nn.Dropout):          # drop_out > 0: pool here, torch's dropout + linear (reference :343-348)
@@ -527,7 +541,7 @@ class Model(nn.Module):
 
     def extract_feature(self, x):
         x = _require_hip(x)
-        eng = self._f2(x)
+        eng = self._f2(x) or self._f2v(x)
         x, N, M = eng.blocks(x) if eng is not None else self._blocks(x)
         _, C, T, V = x.size()
         x = x.view(N, M, C, T, V).permute(0, 2, 3, 4, 1).contiguous()

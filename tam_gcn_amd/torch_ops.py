@@ -15,6 +15,8 @@ backward is itself a registered op:
 
     tamgcn::tcn_gcn_unit_eval(x, xpart, params, geom) -> (out, xpart)   the whole eval-mode TCN_GCN_unit (:266-284) for small
                                                  batches, BatchNorm folded; registered by tam_gcn_amd/f2.py with the engine that uses it
+    tamgcn::tcn_gcn_unit_eval_v25(x, xpart, params, geom) -> (out, xpart)   the same for 25 joints (tam_gcn_amd/f2v.py); xpart there
+                                                 has frames of 28 floats
 
 The TRAINING block-level nodes (unit_gcn / MultiScale_TemporalConv / TCN_GCN_unit / st_gcn) stay ``autograd.Function``s: they update
 BatchNorm running statistics in place, keep ~20 intermediate tensors between forward and backward and take their

@@ -1,59 +1,107 @@
-"""GPU-box tool: forward-only throughput (eval mode, no_grad) of the N-UCLA model at a few batch sizes -- what the
-inference-only callers (cross-modal attention, ensemble eval, visualisation) see.  Eager launches and HIP-graph replay.
-    python tools/infer_bench.py [--t T] [batch ...]        (default T = 64, batches 1 16 256)
-Batches of at most TAMGCN_F2_MAX_CLIPS clips take the small-batch kernel family (tam_gcn_amd/f2.py); TAMGCN_F2=0 puts them on
-the general eval path for comparison."""
-import os, sys, time, torch
+"""GPU-box tool: forward-only throughput (eval mode, no_grad) of the N-UCLA or the NTU-RGB+D model at a few batch sizes -- what
+the inference-only callers (cross-modal attention, ensemble eval, visualisation) see.  Eager launches and HIP-graph replay.
+    python tools/infer_bench.py [--graph ucla|ntu] [--t T] [--ab R] [batch ...]     (default ucla, T = 64, batches 1 16 256)
+--graph ntu: 25 joints, 2 persons (a batch of B clips is 2B clip-persons).
+Batches of at most TAMGCN_F2_MAX_CLIPS clips (ucla) / TAMGCN_F2V_MAX_FRAMES clip-persons x frames (ntu) take the small-batch
+kernel family (tam_gcn_amd/f2.py, f2v.py); TAMGCN_F2=0 puts them on the general eval path for comparison.
+--ab R: the family against the general path of the same process, alternating, R timings each (median [min .. max]); the
+family is forced on whatever the routing bound says (that bound is what this mode is for)."""
+import os, statistics, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tam_gcn_amd.models.ctrgcn import Model
 dev = torch.device('cuda:0')
 torch.manual_seed(0)
-m = Model(num_class=10, num_point=20, num_person=1, graph='graph.ucla.Graph', graph_args=dict(labeling_mode='spatial')).to(dev).eval()
+args = sys.argv[1:]
+T, graph, ab = 64, 'ucla', 0
+while args and args[0].startswith('--'):
+    if args[0] == '--t':
+        T = int(args[1])
+    elif args[0] == '--graph':
+        graph = args[1]
+    elif args[0] == '--ab':
+        ab = int(args[1])
+    else:
+        sys.exit(__doc__)
+    args = args[2:]
+if graph == 'ntu':
+    V, P = 25, 2
+    m = Model(num_class=60, num_point=25, num_person=2, graph='graph.ntu_rgb_d.Graph', graph_args=dict(labeling_mode='spatial'))
+else:
+    V, P = 20, 1
+    m = Model(num_class=10, num_point=20, num_person=1, graph='graph.ucla.Graph', graph_args=dict(labeling_mode='spatial'))
+m = m.to(dev).eval()
 with torch.no_grad():
     for k, p in m.named_parameters():
         if k.endswith('alpha'):
             p.fill_(0.5)
-args = sys.argv[1:]
-T = 64
-if args and args[0] == '--t':
-    T = int(args[1]); args = args[2:]
-print(f'T = {T}, TAMGCN_F2 = {os.environ.get("TAMGCN_F2", "1")}', flush=True)
+n = 50
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n
+
+
+def capture(x):
+    s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        y = m(x)
+    torch.cuda.current_stream().wait_stream(s); torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        y = m(x)
+    g.replay(); torch.cuda.synchronize()
+    return g, y
+
+
+print(f'graph = {graph} (V = {V}, M = {P}), T = {T}, TAMGCN_F2 = {os.environ.get("TAMGCN_F2", "1")}', flush=True)
 for B in ([int(v) for v in args] or (1, 16, 256)):
-    x = torch.rand(B, 3, T, 20, 1, device=dev) * 2 - 1
+    x = torch.rand(B, 3, T, V, P, device=dev) * 2 - 1
     with torch.no_grad():
+        if ab:
+            if graph == 'ntu':
+                from tam_gcn_amd import f2v
+                f2v.F2V_MAX_FRAMES = 1 << 40
+            else:
+                from tam_gcn_amd import f2
+                f2.F2_MAX_CLIPS = 1 << 40
+            runs, keep = {}, []
+            for on in ('1', '0'):
+                os.environ['TAMGCN_F2'] = on
+                for _ in range(3):
+                    m(x)
+                g, y = capture(x)
+                keep.append((g, y))
+                runs[on] = (g, {'eager': [], 'graph': []})
+            for _ in range(ab):
+                for on in ('1', '0'):
+                    os.environ['TAMGCN_F2'] = on
+                    g, r = runs[on]
+                    r['eager'].append(timed(lambda: m(x)))
+                    r['graph'].append(timed(g.replay))
+            d = float((keep[0][1] - keep[1][1]).abs().max()) / float(keep[1][1].abs().max())
+            for on, name in (('1', 'family '), ('0', 'general')):
+                r = runs[on][1]
+                print(f'batch {B:4d} x {P} x {T} ({B * P * T:6d} frames) {name}: ' + '   '.join(
+                    f'{k} {statistics.median(v) * 1e3:7.3f} ms [{min(v) * 1e3:7.3f} .. {max(v) * 1e3:7.3f}]' for k, v in r.items()), flush=True)
+            print(f'      family vs general logits: {d:.1e} relative', flush=True)
+            continue
         for _ in range(3):
             y = m(x)
-        torch.cuda.synchronize()
-        n = 50
-        t0 = time.perf_counter()
-        for _ in range(n):
-            y = m(x)
-        torch.cuda.synchronize()
-        eager = (time.perf_counter() - t0) / n
-        s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            y = m(x)
-        torch.cuda.current_stream().wait_stream(s); torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            y = m(x)
-        g.replay(); torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            g.replay()
-        torch.cuda.synchronize()
-        graph = (time.perf_counter() - t0) / n
+        eager = timed(lambda: m(x))
+        g, y = capture(x)
+        graph_t = timed(g.replay)
         extra = ''
         for sp in ([int(v) for v in os.environ.get('INFER_SPLITS', '').split(',') if v] if B >= 16 else []):
             from tam_gcn_amd.inference import GraphedForward
             fast = GraphedForward(m, split=sp)
             ys = fast(x); torch.cuda.synchronize()
             assert float((ys - y).abs().max()) <= 1e-4 * float(y.abs().max()), float((ys - y).abs().max())   # (slices of <= 32 clips take the f2 kernels)
-            t0 = time.perf_counter()
-            for _ in range(n):
-                fast(x)
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t0) / n
+            dt = timed(lambda: fast(x))
             extra += f'   split {sp}: {dt * 1e3:6.2f} ms ({B / dt:8.0f} clips/s)'
-    print(f'batch {B:4d}: eager {eager * 1e3:7.2f} ms ({B / eager:9.0f} clips/s)   hip graph {graph * 1e3:7.2f} ms ({B / graph:9.0f} clips/s)' + extra, flush=True)
+    print(f'batch {B:4d}: eager {eager * 1e3:7.2f} ms ({B / eager:9.0f} clips/s)   hip graph {graph_t * 1e3:7.2f} ms ({B / graph_t:9.0f} clips/s)' + extra, flush=True)
