@@ -532,6 +532,42 @@ int tamgcn_f2v_gcn(const tamgcn_f2_gcn_desc* d, void* stream);
 int tamgcn_f2v_gemm(const tamgcn_f2_gemm_desc* d, void* stream);
 int tamgcn_f2v_tcn(const tamgcn_f2_tcn_desc* d, void* stream);
 
+/* ---- grouped: the four stages of both families for `groups` models of ONE geometry in one launch (a multi-stream ensemble:
+ * tam_gcn_amd.inference.StreamEnsemble).  The descriptors above, unchanged, plus `int groups`:
+ *   samples      d->N is the TOTAL number of clip-persons, N % groups == 0; samples [g N/groups, (g+1) N/groups) belong to group g
+ *   activations  x, E, sum, diff, h, out, xpart (and the 28-float frames of f2v): the layouts above, indexed by the total sample
+ *   parameters   every parameter pointer of the descriptor is group 0's; group g's array follows densely at g times the array's
+ *                own size as the descriptor's dimensions give it:  w12 S*2R*Cin,  b12 S*2R,  w4 S*Cout*R,  b4 S*Cout,  A S*V*V,
+ *                alpha 1,  w3 S*Cout*Cin,  b3 S*Cout,  sy, ty Cout,  wd Cout*Cin,  bd Cout;  gemm w M*K, b M;  tcn wt[b] Cb*Cb*ks,
+ *                bt[b], sp, tp Cb,  wr Cout*Cin,  br Cout.  An absent optional array (wd / bd, wr / br) is absent for every group.
+ *   alignment    where a launch reads a weight array in 16-byte pieces (row length a multiple of 16 and a 16-byte aligned base)
+ *                the group stride must be a multiple of four floats; it always is under that condition, and is checked.
+ * All groups share one geometry; g = sample / (N / groups) is uniform per workgroup.  Arithmetic, tiling and summation order
+ * are those of the plain entry points: group g's outputs are bit-equal to a plain call on group g's slice and parameters.
+ * Added in ABI 401 without a version bump: new entry points only. */
+int tamgcn_f2_e_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream);
+int tamgcn_f2_gcn_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream);
+int tamgcn_f2_gemm_grouped(const tamgcn_f2_gemm_desc* d, int groups, void* stream);
+int tamgcn_f2_tcn_grouped(const tamgcn_f2_tcn_desc* d, int groups, void* stream);
+int tamgcn_f2v_e_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream);
+int tamgcn_f2v_gcn_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream);
+int tamgcn_f2v_gemm_grouped(const tamgcn_f2_gemm_desc* d, int groups, void* stream);
+int tamgcn_f2v_tcn_grouped(const tamgcn_f2_tcn_desc* d, int groups, void* stream);
+
+/* Stem and head of such an ensemble, one launch each:
+ *   _stem_streams_eval  x (N, C, T, V, M) joint clips -> out (G*N*M, C, T, V), row g*N*M + n*M + m = model g's eval-mode data_bn
+ *                       (coef [G][3][J], J = C*V*M, each in _stem_apply's layout: c1 at [0][j], c0 at [2][j]) of stream modes[g]
+ *                       of x (0 joint, 1 bone, 2 motion, 3 bone-motion: _stream_derive's arithmetic, then _stem_apply's fma --
+ *                       bit-equal to that pair).  parent int32 [V], modes int32 [G] on the device.  The frame after the last is
+ *                       never read (the motion of the last frame is 0).  modes and parent live on the device and are NOT
+ *                       validated (as _stream_derive trusts its parent table): a mode outside 0..3 behaves as 3, a parent
+ *                       entry outside [0, V) reads outside the frame -- the caller checks both (inference.StreamEnsemble does).
+ *   _head_fc_grouped    pooled (G*N, C) (tamgcn_head_pool_fwd with N := G*N), W [G][K][C], b [G][K] or NULL ->
+ *                       scores [G][N][K], tamgcn_score_fuse's layout; per row the arithmetic of _head_fc_fwd. */
+int tamgcn_stem_streams_eval(const float* x, const int* parent, const int* modes, const float* coef, int G, int N, int C, int T, int V, int M,
+                             float* out, void* stream);
+int tamgcn_head_fc_grouped(const float* pooled, const float* W, const float* b, int G, int N, int C, int K, float* scores, void* stream);
+
 /* ------------------------------------------------------------------------
  * Optimiser update in place over flat fp32 buffers of n elements (a ParamArena and its FlatGradBucket):
  *   mode 0  torch.optim.SGD (foreach=False):  d = g + wd p;  with momentum m > 0:  s0 = d on the first step, else

@@ -181,6 +181,16 @@ SIGNATURES = {
     'tamgcn_f2v_gcn': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2v_gemm': (_i, [C.POINTER(F2GemmDesc), _p]),
     'tamgcn_f2v_tcn': (_i, [C.POINTER(F2TcnDesc), _p]),
+    'tamgcn_f2_e_grouped': (_i, [C.POINTER(F2GcnDesc), _i, _p]),
+    'tamgcn_f2_gcn_grouped': (_i, [C.POINTER(F2GcnDesc), _i, _p]),
+    'tamgcn_f2_gemm_grouped': (_i, [C.POINTER(F2GemmDesc), _i, _p]),
+    'tamgcn_f2_tcn_grouped': (_i, [C.POINTER(F2TcnDesc), _i, _p]),
+    'tamgcn_f2v_e_grouped': (_i, [C.POINTER(F2GcnDesc), _i, _p]),
+    'tamgcn_f2v_gcn_grouped': (_i, [C.POINTER(F2GcnDesc), _i, _p]),
+    'tamgcn_f2v_gemm_grouped': (_i, [C.POINTER(F2GemmDesc), _i, _p]),
+    'tamgcn_f2v_tcn_grouped': (_i, [C.POINTER(F2TcnDesc), _i, _p]),
+    'tamgcn_stem_streams_eval': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    'tamgcn_head_fc_grouped': (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     'tamgcn_optim_step': (_i, [C.POINTER(OptimDesc), _p]),
     'tamgcn_optim_step_guarded': (_i, [C.POINTER(OptimDesc), C.POINTER(GradGuard), _p]),
 }

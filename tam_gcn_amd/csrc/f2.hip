@@ -119,10 +119,23 @@ struct F2GcnArgs {
     int vec12, vec4, vec3, vecd;
 };
 
+// Grouped launches (include/tamgcn.h, "grouped"): samples [g*npg, (g+1)*npg) use the g-th of the parameter arrays that follow
+// one another densely behind group 0's.  g comes from blockIdx.y alone: the offset bases stay scalar.
+__device__ __forceinline__ F2GcnArgs f2_group(F2GcnArgs a, int g) {
+    const long long SC = (long long)a.S * a.Cout;
+    a.w12 += g * (long long)a.S * 2 * a.R * a.Cin; a.b12 += g * a.S * 2 * a.R;
+    a.w4 += g * SC * a.R; a.b4 += g * SC;
+    a.A += g * a.S * F2_VV; a.alpha += g;
+    a.w3 += g * SC * a.Cin; a.b3 += g * SC;
+    a.sy += g * a.Cout; a.ty += g * a.Cout;
+    if (a.res_mode == 2) { a.wd += (long long)g * a.Cout * a.Cin; a.bd += g * a.Cout; }
+    return a;
+}
+
 // ---- E for 16 channels of one (sample, subset)
 constexpr int F2_PX = 36, F2_PD = 404;     // xbar / pq pitch (20 columns in two tiles), D pitch (4*404 = 16 mod 64)
 
-__global__ __launch_bounds__(F2_NT) void f2_e_kernel(const F2GcnArgs a) {
+__device__ __forceinline__ void f2_e_body(const F2GcnArgs& a) {
     constexpr int V = F2_V, VV = F2_VV, NT = F2_NT, PX = F2_PX, PD = F2_PD, NTP = 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Kp = (a.Cin + 15) & ~15, R2 = 2 * a.R, R2p = R2 < 16 ? 16 : R2, Rp = (a.R + 15) & ~15;
@@ -282,10 +295,13 @@ __global__ __launch_bounds__(F2_NT) void f2_e_kernel(const F2GcnArgs a) {
     }
 }
 
+__global__ __launch_bounds__(F2_NT) void f2_e_kernel(const F2GcnArgs a) { f2_e_body(a); }
+__global__ __launch_bounds__(F2_NT) void f2_e_grouped_kernel(const F2GcnArgs a, int npg) { f2_e_body(f2_group(a, blockIdx.y / npg)); }
+
 // ---- x3 GEMM + aggregation + BatchNorm + residual for 8 channels x 4 frames
 constexpr int F2_CT = 8, F2_ES = 3328;     // E run of one subset: 8 * 400 floats = 12.5 DMA pieces of 1 KB, padded to 13
 
-__global__ __launch_bounds__(F2_NT) void f2_gcn_kernel(const F2GcnArgs a) {
+__device__ __forceinline__ void f2_gcn_body(const F2GcnArgs& a) {
     constexpr int V = F2_V, VV = F2_VV, NT = F2_NT, PB = F2_PB, CT = F2_CT, ES = F2_ES;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Kp = (a.Cin + 15) & ~15;
@@ -372,6 +388,9 @@ __global__ __launch_bounds__(F2_NT) void f2_gcn_kernel(const F2GcnArgs a) {
     }
 }
 
+__global__ __launch_bounds__(F2_NT) void f2_gcn_kernel(const F2GcnArgs a) { f2_gcn_body(a); }
+__global__ __launch_bounds__(F2_NT) void f2_gcn_grouped_kernel(const F2GcnArgs a, int npg) { f2_gcn_body(f2_group(a, blockIdx.y / npg)); }
+
 // ---------------------------------------------------------------------------------------------------------------------
 // 16 rows x 4 frames of a pointwise product with the block's epilogues
 // ---------------------------------------------------------------------------------------------------------------------
@@ -381,7 +400,7 @@ struct F2GemmArgs {
     float* out;
 };
 
-__global__ __launch_bounds__(F2_NT) void f2_gemm_kernel(const F2GemmArgs a) {
+__device__ __forceinline__ void f2_gemm_body(const F2GemmArgs& a) {
     constexpr int V = F2_V, NT = F2_NT, PB = F2_PB;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Kp = (a.K + 15) & ~15;
@@ -432,6 +451,15 @@ __global__ __launch_bounds__(F2_NT) void f2_gemm_kernel(const F2GemmArgs a) {
     }
 }
 
+__global__ __launch_bounds__(F2_NT) void f2_gemm_kernel(const F2GemmArgs a) { f2_gemm_body(a); }
+__global__ __launch_bounds__(F2_NT) void f2_gemm_grouped_kernel(const F2GemmArgs a, int npg) {
+    F2GemmArgs b = a;
+    const int g = blockIdx.y / npg;
+    b.w += (long long)g * a.M * a.K;
+    b.b += g * a.M;
+    f2_gemm_body(b);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // MS-TCN after its entry convs + the block's residual and ReLU: 16 output channels x 4 output frames
 // ---------------------------------------------------------------------------------------------------------------------
@@ -448,7 +476,7 @@ struct F2TcnArgs {
 
 constexpr int F2_HF = 15, F2_PH = F2_HF * F2_V + 4;    // halo tile: 3*stride + (ks-1)*dil + 1 <= 15 frames
 
-__global__ __launch_bounds__(F2_NT) void f2_tcn_kernel(const F2TcnArgs a) {
+__device__ __forceinline__ void f2_tcn_body(const F2TcnArgs& a, const int g) {
     constexpr int V = F2_V, NT = F2_NT, PB = F2_PB, PH = F2_PH;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Kp = a.res_mode == 2 ? (a.Cin + 15) & ~15 : 0;
@@ -507,13 +535,13 @@ __global__ __launch_bounds__(F2_NT) void f2_tcn_kernel(const F2TcnArgs a) {
                 boff[ct] = tl * a.stride * V + v;
             }
             const int K = a.Cb * a.ks;
-            f2_gemm16<F2_NCT>(acc, a.wt[branch] + (long long)(cb0 + j) * K, K, a.vect != 0, wave, 4, kq, [&](int k, int ct) {
+            f2_gemm16<F2_NCT>(acc, a.wt[branch] + (long long)g * a.Cb * K + (long long)(cb0 + j) * K, K, a.vect != 0, wave, 4, kq, [&](int k, int ct) {
                 const int ci = k / a.ks, tap = k - ci * a.ks;
                 return Hs[ci * PH + tap * d * V + boff[ct]];
             });
         }
         if (a.res_mode == 2)
-            f2_gemm16<F2_NCT>(acc, a.wr + (long long)(c0 + j) * a.Cin, a.Cin, a.vecr != 0, wave, 4, kq,
+            f2_gemm16<F2_NCT>(acc, a.wr + (long long)g * a.Cout * a.Cin + (long long)(c0 + j) * a.Cin, a.Cin, a.vecr != 0, wave, 4, kq,
                               [&](int k, int ct) { return Xs[k * PB + ct * 16 + j]; });
 #pragma unroll
         for (int ct = 0; ct < F2_NCT; ++ct)
@@ -535,7 +563,7 @@ __global__ __launch_bounds__(F2_NT) void f2_tcn_kernel(const F2TcnArgs a) {
         const int c = c0 + row, cb = cb0 + row, tq = t0 + tl, ts = tq * a.stride;
         f32x4 val;
         if (temporal) {
-            const float b = a.bt[branch][cb];
+            const float b = a.bt[branch][g * a.Cb + cb];
             val = (f32x4){b, b, b, b};
         } else if (branch == a.nb) {                               // MaxPool2d((3,1), stride, pad 1) of the ReLU'd entry output, then its BatchNorm
             const float* hp = a.h + ((long long)n * a.Cout + c) * TV + v;
@@ -550,7 +578,7 @@ __global__ __launch_bounds__(F2_NT) void f2_tcn_kernel(const F2TcnArgs a) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) m[i] = fmaxf(m[i], q[i]);
             }
-            const float sp = a.sp[cb], tp = a.tp[cb];
+            const float sp = a.sp[g * a.Cb + cb], tp = a.tp[g * a.Cb + cb];
 #pragma unroll
             for (int i = 0; i < 4; ++i) val[i] = fmaf(sp, m[i], tp);
         } else {                                                   // plain branch: computed with the entry convs (rows >= Ch of h)
@@ -561,7 +589,7 @@ __global__ __launch_bounds__(F2_NT) void f2_tcn_kernel(const F2TcnArgs a) {
             const f32x4 q = *reinterpret_cast<const f32x4*>(a.x + ((long long)n * a.Cin + c) * TV + (long long)tq * V + v);
             val += q;
         } else if (a.res_mode == 2) {
-            const float b = a.br[c];
+            const float b = a.br[g * a.Cout + c];
 #pragma unroll
             for (int i = 0; i < 4; ++i) val[i] += b;
         }
@@ -583,6 +611,9 @@ __global__ __launch_bounds__(F2_NT) void f2_tcn_kernel(const F2TcnArgs a) {
         }
     }
 }
+
+__global__ __launch_bounds__(F2_NT) void f2_tcn_kernel(const F2TcnArgs a) { f2_tcn_body(a, 0); }
+__global__ __launch_bounds__(F2_NT) void f2_tcn_grouped_kernel(const F2TcnArgs a, int npg) { f2_tcn_body(a, blockIdx.y / npg); }
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -619,63 +650,84 @@ int f2_fill(const tamgcn_f2_gcn_desc* d, F2GcnArgs* a, const char* who) {
     return 0;
 }
 
-}  // namespace
-
-extern "C" int tamgcn_f2_e(const tamgcn_f2_gcn_desc* d, void* stream) {
+// groups == 0: the plain entry point; otherwise the grouped one (common.h: tg_groups_ok, tg_group_stride_ok).
+int f2_e_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
     F2GcnArgs a;
-    if (f2_fill(d, &a, "tamgcn_f2_e")) return -1;
-    tg_launch_lds<f2_e_kernel>(f2_e_lds(256, 32), dim3(d->S * (d->Cout / 16), d->N), dim3(F2_NT), f2_e_lds(d->Cin, d->R), (hipStream_t)stream, a);
-    tamgcn_note_kernel("f2_e_kernel");
-    TG_LAUNCH_CHECK("tamgcn_f2_e");
+    if (f2_fill(d, &a, who)) return -1;
+    const dim3 grid(d->S * (d->Cout / 16), d->N);
+    if (groups) {
+        if (tg_groups_ok(d->N, groups, who) || tg_gcn_group_strides_ok(d, a.vec12, a.vec4, a.vec3, a.vecd, who)) return -1;
+        tg_launch_lds<f2_e_grouped_kernel>(f2_e_lds(256, 32), grid, dim3(F2_NT), f2_e_lds(d->Cin, d->R), (hipStream_t)stream, a, d->N / groups);
+        tamgcn_note_kernel("f2_e_grouped_kernel");
+    } else {
+        tg_launch_lds<f2_e_kernel>(f2_e_lds(256, 32), grid, dim3(F2_NT), f2_e_lds(d->Cin, d->R), (hipStream_t)stream, a);
+        tamgcn_note_kernel("f2_e_kernel");
+    }
+    TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-extern "C" int tamgcn_f2_gcn(const tamgcn_f2_gcn_desc* d, void* stream) {
+int f2_gcn_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
     F2GcnArgs a;
-    if (f2_fill(d, &a, "tamgcn_f2_gcn")) return -1;
-    TG_CHECK(d->sum && d->diff && al16(d->sum) && al16(d->diff), "tamgcn_f2_gcn: null or misaligned output");
-    tg_launch_lds<f2_gcn_kernel>(f2_gcn_lds(256), dim3(ceil_div(d->T, F2_BT) * (d->Cout / F2_CT), d->N), dim3(F2_NT), f2_gcn_lds(d->Cin), (hipStream_t)stream, a);
-    tamgcn_note_kernel("f2_gcn_kernel");
-    TG_LAUNCH_CHECK("tamgcn_f2_gcn");
+    if (f2_fill(d, &a, who)) return -1;
+    TG_CHECK(d->sum && d->diff && al16(d->sum) && al16(d->diff), "%s: null or misaligned output", who);
+    const dim3 grid(ceil_div(d->T, F2_BT) * (d->Cout / F2_CT), d->N);
+    if (groups) {
+        if (tg_groups_ok(d->N, groups, who) || tg_gcn_group_strides_ok(d, a.vec12, a.vec4, a.vec3, a.vecd, who)) return -1;
+        tg_launch_lds<f2_gcn_grouped_kernel>(f2_gcn_lds(256), grid, dim3(F2_NT), f2_gcn_lds(d->Cin), (hipStream_t)stream, a, d->N / groups);
+        tamgcn_note_kernel("f2_gcn_grouped_kernel");
+    } else {
+        tg_launch_lds<f2_gcn_kernel>(f2_gcn_lds(256), grid, dim3(F2_NT), f2_gcn_lds(d->Cin), (hipStream_t)stream, a);
+        tamgcn_note_kernel("f2_gcn_kernel");
+    }
+    TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-extern "C" int tamgcn_f2_gemm(const tamgcn_f2_gemm_desc* d, void* stream) {
-    TG_CHECK(d && d->x && d->w && d->b && d->out, "tamgcn_f2_gemm: null pointer");
-    TG_CHECK(d->V == F2_V, "tamgcn_f2_gemm: V=%d (built for V = 20)", d->V);
+int f2_gemm_launch(const tamgcn_f2_gemm_desc* d, int groups, void* stream, const char* who) {
+    TG_CHECK(d && d->x && d->w && d->b && d->out, "%s: null pointer", who);
+    TG_CHECK(d->V == F2_V, "%s: V=%d (built for V = 20)", who, d->V);
     TG_CHECK(d->N > 0 && d->T > 0 && d->K > 0 && d->K <= 256 && d->M > 0 && d->M % 16 == 0,
-             "tamgcn_f2_gemm: bad shape N=%d T=%d K=%d M=%d (K <= 256, M %% 16 == 0)", d->N, d->T, d->K, d->M);
-    TG_CHECK(d->mode == 0 || d->mode == 1, "tamgcn_f2_gemm: mode=%d", d->mode);
-    TG_CHECK(d->mode != 0 || d->add, "tamgcn_f2_gemm: mode 0 needs the addend");
-    TG_CHECK(al16(d->x) && al16(d->out) && (!d->add || al16(d->add)), "tamgcn_f2_gemm: activations must be 16-byte aligned");
+             "%s: bad shape N=%d T=%d K=%d M=%d (K <= 256, M %% 16 == 0)", who, d->N, d->T, d->K, d->M);
+    TG_CHECK(d->mode == 0 || d->mode == 1, "%s: mode=%d", who, d->mode);
+    TG_CHECK(d->mode != 0 || d->add, "%s: mode 0 needs the addend", who);
+    TG_CHECK(al16(d->x) && al16(d->out) && (!d->add || al16(d->add)), "%s: activations must be 16-byte aligned", who);
     F2GemmArgs a;
     a.N = d->N; a.K = d->K; a.M = d->M; a.T = d->T; a.mode = d->mode; a.relu_rows = d->relu_rows;
     a.vec = d->K % 16 == 0 && al16(d->w);
     a.x = d->x; a.w = d->w; a.b = d->b; a.add = d->add; a.out = d->out;
-    tg_launch_lds<f2_gemm_kernel>(f2_gemm_lds(256), dim3(ceil_div(d->T, F2_BT) * (d->M / 16), d->N), dim3(F2_NT), f2_gemm_lds(d->K), (hipStream_t)stream, a);
-    tamgcn_note_kernel("f2_gemm_kernel");
-    TG_LAUNCH_CHECK("tamgcn_f2_gemm");
+    const dim3 grid(ceil_div(d->T, F2_BT) * (d->M / 16), d->N);
+    if (groups) {
+        if (tg_groups_ok(d->N, groups, who)) return -1;
+        if (tg_group_stride_ok(a.vec, (long long)d->M * d->K, who, "w")) return -1;
+        tg_launch_lds<f2_gemm_grouped_kernel>(f2_gemm_lds(256), grid, dim3(F2_NT), f2_gemm_lds(d->K), (hipStream_t)stream, a, d->N / groups);
+        tamgcn_note_kernel("f2_gemm_grouped_kernel");
+    } else {
+        tg_launch_lds<f2_gemm_kernel>(f2_gemm_lds(256), grid, dim3(F2_NT), f2_gemm_lds(d->K), (hipStream_t)stream, a);
+        tamgcn_note_kernel("f2_gemm_kernel");
+    }
+    TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-extern "C" int tamgcn_f2_tcn(const tamgcn_f2_tcn_desc* d, void* stream) {
-    TG_CHECK(d && d->h && d->out && d->sp && d->tp, "tamgcn_f2_tcn: null pointer");
-    TG_CHECK(d->V == F2_V, "tamgcn_f2_tcn: V=%d (built for V = 20)", d->V);
+int f2_tcn_launch(const tamgcn_f2_tcn_desc* d, int groups, void* stream, const char* who) {
+    TG_CHECK(d && d->h && d->out && d->sp && d->tp, "%s: null pointer", who);
+    TG_CHECK(d->V == F2_V, "%s: V=%d (built for V = 20)", who, d->V);
     TG_CHECK(d->N > 0 && d->T > 0 && d->Cout > 0 && d->Cout % 16 == 0 && d->stride >= 1 && d->stride <= 2,
-             "tamgcn_f2_tcn: bad shape N=%d T=%d Cout=%d stride=%d", d->N, d->T, d->Cout, d->stride);
+             "%s: bad shape N=%d T=%d Cout=%d stride=%d", who, d->N, d->T, d->Cout, d->stride);
     TG_CHECK(d->nb >= 1 && d->nb <= 4 && d->Cb % 16 == 0 && d->Cb <= 64 && (d->nb + 2) * d->Cb == d->Cout,
-             "tamgcn_f2_tcn: nb=%d Cb=%d Cout=%d (Cb %% 16 == 0, Cb <= 64, (nb + 2) Cb == Cout)", d->nb, d->Cb, d->Cout);
-    TG_CHECK(d->ks >= 1 && d->ks % 2 == 1, "tamgcn_f2_tcn: kernel size %d", d->ks);
+             "%s: nb=%d Cb=%d Cout=%d (Cb %% 16 == 0, Cb <= 64, (nb + 2) Cb == Cout)", who, d->nb, d->Cb, d->Cout);
+    TG_CHECK(d->ks >= 1 && d->ks % 2 == 1, "%s: kernel size %d", who, d->ks);
     for (int b = 0; b < d->nb; ++b) {
-        TG_CHECK(d->wt[b] && d->bt[b] && d->dil[b] >= 1, "tamgcn_f2_tcn: branch %d: null weights or dilation %d", b, d->dil[b]);
-        TG_CHECK((F2_BT - 1) * d->stride + (d->ks - 1) * d->dil[b] + 1 <= F2_HF, "tamgcn_f2_tcn: branch %d: halo of k=%d dilation %d stride %d exceeds %d frames",
-                 b, d->ks, d->dil[b], d->stride, F2_HF);
+        TG_CHECK(d->wt[b] && d->bt[b] && d->dil[b] >= 1, "%s: branch %d: null weights or dilation %d", who, b, d->dil[b]);
+        TG_CHECK((F2_BT - 1) * d->stride + (d->ks - 1) * d->dil[b] + 1 <= F2_HF, "%s: branch %d: halo of k=%d dilation %d stride %d exceeds %d frames",
+                 who, b, d->ks, d->dil[b], d->stride, F2_HF);
     }
-    TG_CHECK(d->res_mode >= 0 && d->res_mode <= 2, "tamgcn_f2_tcn: res_mode=%d", d->res_mode);
-    TG_CHECK(d->res_mode == 0 || d->x, "tamgcn_f2_tcn: residual without the block input");
-    TG_CHECK(d->res_mode != 1 || (d->Cin == d->Cout && d->stride == 1), "tamgcn_f2_tcn: identity residual needs Cin == Cout, stride 1");
-    TG_CHECK(d->res_mode != 2 || (d->wr && d->br && d->Cin > 0 && d->Cin <= 256), "tamgcn_f2_tcn: convolutional residual: weights / Cin=%d", d->Cin);
-    TG_CHECK(al16(d->h) && al16(d->out) && (!d->x || al16(d->x)) && (!d->xpart || al16(d->xpart)), "tamgcn_f2_tcn: activations must be 16-byte aligned");
+    TG_CHECK(d->res_mode >= 0 && d->res_mode <= 2, "%s: res_mode=%d", who, d->res_mode);
+    TG_CHECK(d->res_mode == 0 || d->x, "%s: residual without the block input", who);
+    TG_CHECK(d->res_mode != 1 || (d->Cin == d->Cout && d->stride == 1), "%s: identity residual needs Cin == Cout, stride 1", who);
+    TG_CHECK(d->res_mode != 2 || (d->wr && d->br && d->Cin > 0 && d->Cin <= 256), "%s: convolutional residual: weights / Cin=%d", who, d->Cin);
+    TG_CHECK(al16(d->h) && al16(d->out) && (!d->x || al16(d->x)) && (!d->xpart || al16(d->xpart)), "%s: activations must be 16-byte aligned", who);
     F2TcnArgs a;
     a.N = d->N; a.Cin = d->Cin; a.Cout = d->Cout; a.T = d->T; a.stride = d->stride; a.T2 = (d->T - 1) / d->stride + 1;
     a.Cb = d->Cb; a.nb = d->nb; a.ks = d->ks; a.res_mode = d->res_mode;
@@ -690,9 +742,42 @@ extern "C" int tamgcn_f2_tcn(const tamgcn_f2_tcn_desc* d, void* stream) {
     a.vecr = d->res_mode == 2 && d->Cin % 16 == 0 && al16(d->wr);
     a.h = d->h; a.sp = d->sp; a.tp = d->tp; a.x = d->x; a.wr = d->wr; a.br = d->br; a.out = d->out; a.xpart = d->xpart;
     const size_t lds = f2_tcn_lds(d->Cin, d->Cb, d->res_mode);
-    TG_CHECK(lds <= 160 * 1024, "tamgcn_f2_tcn: %zu bytes of LDS", lds);
-    tg_launch_lds<f2_tcn_kernel>(160 * 1024, dim3(ceil_div(a.T2, F2_BT) * (d->Cout / 16), d->N), dim3(F2_NT), lds, (hipStream_t)stream, a);
-    tamgcn_note_kernel("f2_tcn_kernel");
-    TG_LAUNCH_CHECK("tamgcn_f2_tcn");
+    TG_CHECK(lds <= 160 * 1024, "%s: %zu bytes of LDS", who, lds);
+    const dim3 grid(ceil_div(a.T2, F2_BT) * (d->Cout / 16), d->N);
+    if (groups) {
+        if (tg_groups_ok(d->N, groups, who)) return -1;
+        if (tg_group_stride_ok(a.vect, (long long)d->Cb * d->Cb * d->ks, who, "wt")) return -1;
+        if (tg_group_stride_ok(a.vecr, (long long)d->Cout * d->Cin, who, "wr")) return -1;
+        tg_launch_lds<f2_tcn_grouped_kernel>(160 * 1024, grid, dim3(F2_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tamgcn_note_kernel("f2_tcn_grouped_kernel");
+    } else {
+        tg_launch_lds<f2_tcn_kernel>(160 * 1024, grid, dim3(F2_NT), lds, (hipStream_t)stream, a);
+        tamgcn_note_kernel("f2_tcn_kernel");
+    }
+    TG_LAUNCH_CHECK(who);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int tamgcn_f2_e(const tamgcn_f2_gcn_desc* d, void* stream) { return f2_e_launch(d, 0, stream, "tamgcn_f2_e"); }
+extern "C" int tamgcn_f2_gcn(const tamgcn_f2_gcn_desc* d, void* stream) { return f2_gcn_launch(d, 0, stream, "tamgcn_f2_gcn"); }
+extern "C" int tamgcn_f2_gemm(const tamgcn_f2_gemm_desc* d, void* stream) { return f2_gemm_launch(d, 0, stream, "tamgcn_f2_gemm"); }
+extern "C" int tamgcn_f2_tcn(const tamgcn_f2_tcn_desc* d, void* stream) { return f2_tcn_launch(d, 0, stream, "tamgcn_f2_tcn"); }
+
+static int f2_groups_arg(int groups, const char* who) {
+    TG_CHECK(groups >= 1, "%s: groups=%d", who, groups);
+    return 0;
+}
+extern "C" int tamgcn_f2_e_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream) {
+    return f2_groups_arg(groups, "tamgcn_f2_e_grouped") ? -1 : f2_e_launch(d, groups, stream, "tamgcn_f2_e_grouped");
+}
+extern "C" int tamgcn_f2_gcn_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream) {
+    return f2_groups_arg(groups, "tamgcn_f2_gcn_grouped") ? -1 : f2_gcn_launch(d, groups, stream, "tamgcn_f2_gcn_grouped");
+}
+extern "C" int tamgcn_f2_gemm_grouped(const tamgcn_f2_gemm_desc* d, int groups, void* stream) {
+    return f2_groups_arg(groups, "tamgcn_f2_gemm_grouped") ? -1 : f2_gemm_launch(d, groups, stream, "tamgcn_f2_gemm_grouped");
+}
+extern "C" int tamgcn_f2_tcn_grouped(const tamgcn_f2_tcn_desc* d, int groups, void* stream) {
+    return f2_groups_arg(groups, "tamgcn_f2_tcn_grouped") ? -1 : f2_tcn_launch(d, groups, stream, "tamgcn_f2_tcn_grouped");
 }

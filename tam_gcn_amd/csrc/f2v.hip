@@ -132,9 +132,23 @@ struct FvGcnArgs {
     int ntp;                             // f2v_e: frame phases of the xbar sum (4, or 2 where 4 partial tiles do not fit LDS)
 };
 
+// Grouped launches (include/tamgcn.h, "grouped"): samples [g*npg, (g+1)*npg) use the g-th of the parameter arrays that follow
+// one another densely behind group 0's.  g comes from blockIdx.y alone: the offset bases stay scalar.
+template <int V>
+__device__ __forceinline__ FvGcnArgs fv_group(FvGcnArgs a, int g) {
+    const long long SC = (long long)a.S * a.Cout;
+    a.w12 += g * (long long)a.S * 2 * a.R * a.Cin; a.b12 += g * a.S * 2 * a.R;
+    a.w4 += g * SC * a.R; a.b4 += g * SC;
+    a.A += g * a.S * V * V; a.alpha += g;
+    a.w3 += g * SC * a.Cin; a.b3 += g * SC;
+    a.sy += g * a.Cout; a.ty += g * a.Cout;
+    if (a.res_mode == 2) { a.wd += (long long)g * a.Cout * a.Cin; a.bd += g * a.Cout; }
+    return a;
+}
+
 // ---- E for 16 channels of one (sample, subset): E[c][u][v] at [c][u * VP + v], pad columns zero
 template <int V>
-__global__ __launch_bounds__(FV_NT) void f2v_e_kernel(const FvGcnArgs a) {
+__device__ __forceinline__ void f2v_e_body(const FvGcnArgs& a) {
     using G = FvGeo<V>;
     constexpr int NT = FV_NT, PX = FV_PX, PD = G::PD, VP = G::VP, QF = G::QF, EC = G::EC, ECT = G::ECT;
     constexpr int NB = (64 * V + NT - 1) / NT, NIT = (ECT + 3) / 4;
@@ -296,9 +310,12 @@ __global__ __launch_bounds__(FV_NT) void f2v_e_kernel(const FvGcnArgs a) {
     }
 }
 
+template <int V> __global__ __launch_bounds__(FV_NT) void f2v_e_kernel(const FvGcnArgs a) { f2v_e_body<V>(a); }
+template <int V> __global__ __launch_bounds__(FV_NT) void f2v_e_grouped_kernel(const FvGcnArgs a, int npg) { f2v_e_body<V>(fv_group<V>(a, blockIdx.y / npg)); }
+
 // ---- x3 GEMM + aggregation + BatchNorm + residual for 8 channels x 4 frames; K staged in chunks of FV_KC rows
 template <int V>
-__global__ __launch_bounds__(FV_NT) void f2v_gcn_kernel(const FvGcnArgs a) {
+__device__ __forceinline__ void f2v_gcn_body(const FvGcnArgs& a) {
     using G = FvGeo<V>;
     constexpr int PB = G::PB, CT = FV_CT, ES = G::ES, EC = G::EC, VP = G::VP, NCT = G::NCT, QF = G::QF;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -395,6 +412,9 @@ __global__ __launch_bounds__(FV_NT) void f2v_gcn_kernel(const FvGcnArgs a) {
     (void)QF;
 }
 
+template <int V> __global__ __launch_bounds__(FV_NT) void f2v_gcn_kernel(const FvGcnArgs a) { f2v_gcn_body<V>(a); }
+template <int V> __global__ __launch_bounds__(FV_NT) void f2v_gcn_grouped_kernel(const FvGcnArgs a, int npg) { f2v_gcn_body<V>(fv_group<V>(a, blockIdx.y / npg)); }
+
 // ---------------------------------------------------------------------------------------------------------------------
 // 16 rows x 4 frames of a pointwise product with the block's epilogues; x, add and out have frames of VP floats
 // ---------------------------------------------------------------------------------------------------------------------
@@ -405,7 +425,7 @@ struct FvGemmArgs {
 };
 
 template <int V>
-__global__ __launch_bounds__(FV_NT) void f2v_gemm_kernel(const FvGemmArgs a) {
+__device__ __forceinline__ void f2v_gemm_body(const FvGemmArgs& a) {
     using G = FvGeo<V>;
     constexpr int NT = FV_NT, PB = G::PB, NCT = G::NCT, VP = G::VP, QT = FV_BT * G::QF;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -455,6 +475,15 @@ __global__ __launch_bounds__(FV_NT) void f2v_gemm_kernel(const FvGemmArgs a) {
     }
 }
 
+template <int V> __global__ __launch_bounds__(FV_NT) void f2v_gemm_kernel(const FvGemmArgs a) { f2v_gemm_body<V>(a); }
+template <int V> __global__ __launch_bounds__(FV_NT) void f2v_gemm_grouped_kernel(const FvGemmArgs a, int npg) {
+    FvGemmArgs b = a;
+    const int g = blockIdx.y / npg;
+    b.w += (long long)g * a.M * a.K;
+    b.b += g * a.M;
+    f2v_gemm_body<V>(b);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // MS-TCN after its entry convs + the block's residual and ReLU: 16 output channels x 4 output frames.  h has frames of VP
 // floats; the block input x and the output are contiguous (N, C, T, V).
@@ -471,7 +500,7 @@ struct FvTcnArgs {
 };
 
 template <int V>
-__global__ __launch_bounds__(FV_NT) void f2v_tcn_kernel(const FvTcnArgs a) {
+__device__ __forceinline__ void f2v_tcn_body(const FvTcnArgs& a, const int g) {
     using G = FvGeo<V>;
     constexpr int NT = FV_NT, PB = G::PB, PH = G::PH, NCT = G::NCT, VP = G::VP, QF = G::QF, QT = FV_BT * G::QF;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -493,7 +522,7 @@ __global__ __launch_bounds__(FV_NT) void f2v_tcn_kernel(const FvTcnArgs a) {
     if (a.res_mode == 2) {
         fv_stage<V, false>(Us, a.x + (long long)n * a.Cin * TV + (long long)t0 * a.stride * V, TV, a.Cin, Kp, bt, a.stride, tid);
         __syncthreads();
-        fv_gemm16<NCT>(acc, a.wr + (long long)(c0 + j) * a.Cin, a.Cin, a.vecr != 0, wave, Kp >> 4, 4, kq,
+        fv_gemm16<NCT>(acc, a.wr + (long long)g * a.Cout * a.Cin + (long long)(c0 + j) * a.Cin, a.Cin, a.vecr != 0, wave, Kp >> 4, 4, kq,
                        [&](int k, int ct) { return Us[k * PB + ct * 16 + j]; });
         if (temporal) __syncthreads();                             // (block-uniform) the region is staged again below
     }
@@ -529,7 +558,7 @@ __global__ __launch_bounds__(FV_NT) void f2v_tcn_kernel(const FvTcnArgs a) {
             boff[ct] = tl * a.stride * VP + v;
         }
         const int K = a.Cb * a.ks;
-        fv_gemm16<NCT>(acc, a.wt[branch] + (long long)(cb0 + j) * K, K, a.vect != 0, wave, (K + 15) >> 4, 4, kq, [&](int k, int ct) {
+        fv_gemm16<NCT>(acc, a.wt[branch] + (long long)g * a.Cb * K + (long long)(cb0 + j) * K, K, a.vect != 0, wave, (K + 15) >> 4, 4, kq, [&](int k, int ct) {
             const int kk = k < K ? k : 0;                          // (the A element is zero there)
             const int ci = kk / a.ks, tap = kk - ci * a.ks;
             return Us[ci * PH + tap * d * VP + boff[ct]];
@@ -554,7 +583,7 @@ __global__ __launch_bounds__(FV_NT) void f2v_tcn_kernel(const FvTcnArgs a) {
         const int c = c0 + row, cb = cb0 + row, tq = t0 + tl, ts = tq * a.stride;
         f32x4 val;
         if (temporal) {
-            const float b = a.bt[branch][cb];
+            const float b = a.bt[branch][g * a.Cb + cb];
             val = (f32x4){b, b, b, b};
         } else if (branch == a.nb) {                               // MaxPool2d((3,1), stride, pad 1) of the ReLU'd entry output, then its BatchNorm
             const float* hp = a.h + ((long long)n * a.Cout + c) * TVP + v;
@@ -569,7 +598,7 @@ __global__ __launch_bounds__(FV_NT) void f2v_tcn_kernel(const FvTcnArgs a) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) m[i] = fmaxf(m[i], q[i]);
             }
-            const float sp = a.sp[cb], tp = a.tp[cb];
+            const float sp = a.sp[g * a.Cb + cb], tp = a.tp[g * a.Cb + cb];
 #pragma unroll
             for (int i = 0; i < 4; ++i) val[i] = fmaf(sp, m[i], tp);
         } else {                                                   // plain branch: computed with the entry convs (rows >= Ch of h)
@@ -582,7 +611,7 @@ __global__ __launch_bounds__(FV_NT) void f2v_tcn_kernel(const FvTcnArgs a) {
             for (int i = 0; i < 4; ++i)
                 if (v + i < V) val[i] += xr[i];
         } else if (a.res_mode == 2) {
-            const float b = a.br[c];
+            const float b = a.br[g * a.Cout + c];
 #pragma unroll
             for (int i = 0; i < 4; ++i) val[i] += b;
         }
@@ -607,6 +636,9 @@ __global__ __launch_bounds__(FV_NT) void f2v_tcn_kernel(const FvTcnArgs a) {
         *reinterpret_cast<float4*>(a.xpart + (((long long)n * ntt + tt) * a.Cout + c0 + row) * VP + v4) = o;
     }
 }
+
+template <int V> __global__ __launch_bounds__(FV_NT) void f2v_tcn_kernel(const FvTcnArgs a) { f2v_tcn_body<V>(a, 0); }
+template <int V> __global__ __launch_bounds__(FV_NT) void f2v_tcn_grouped_kernel(const FvTcnArgs a, int npg) { f2v_tcn_body<V>(a, blockIdx.y / npg); }
 
 // ---- host -----------------------------------------------------------------------------------------------------------
 constexpr int FV_V = 25;
@@ -654,71 +686,92 @@ int fv_fill(const tamgcn_f2_gcn_desc* d, FvGcnArgs* a, const char* who) {
     return 0;
 }
 
-}  // namespace
-
-extern "C" int tamgcn_f2v_e(const tamgcn_f2_gcn_desc* d, void* stream) {
+// groups == 0: the plain entry point; otherwise the grouped one (common.h: tg_groups_ok, tg_group_stride_ok).
+int fv_e_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
     FvGcnArgs a;
-    if (fv_fill(d, &a, "tamgcn_f2v_e")) return -1;
+    if (fv_fill(d, &a, who)) return -1;
     a.ntp = fv_e_lds(d->Cin, d->R, 4) <= FV_LDS_MAX ? 4 : 2;
     const size_t lds = fv_e_lds(d->Cin, d->R, a.ntp);
-    TG_CHECK(lds <= FV_LDS_MAX, "tamgcn_f2v_e: %zu bytes of LDS", lds);
-    tg_launch_lds<f2v_e_kernel<FV_V>>(FV_LDS_MAX, dim3(d->S * (d->Cout / 16), d->N), dim3(FV_NT), lds, (hipStream_t)stream, a);
-    tamgcn_note_kernel("f2v_e_kernel");
-    TG_LAUNCH_CHECK("tamgcn_f2v_e");
+    TG_CHECK(lds <= FV_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
+    const dim3 grid(d->S * (d->Cout / 16), d->N);
+    if (groups) {
+        if (tg_groups_ok(d->N, groups, who) || tg_gcn_group_strides_ok(d, a.vec12, a.vec4, a.vec3, a.vecd, who)) return -1;
+        tg_launch_lds<f2v_e_grouped_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tamgcn_note_kernel("f2v_e_grouped_kernel");
+    } else {
+        tg_launch_lds<f2v_e_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tamgcn_note_kernel("f2v_e_kernel");
+    }
+    TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-extern "C" int tamgcn_f2v_gcn(const tamgcn_f2_gcn_desc* d, void* stream) {
+int fv_gcn_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
     FvGcnArgs a;
-    if (fv_fill(d, &a, "tamgcn_f2v_gcn")) return -1;
-    TG_CHECK(d->sum && d->diff && al16(d->sum) && al16(d->diff), "tamgcn_f2v_gcn: null or misaligned output");
+    if (fv_fill(d, &a, who)) return -1;
+    TG_CHECK(d->sum && d->diff && al16(d->sum) && al16(d->diff), "%s: null or misaligned output", who);
     const size_t lds = fv_gcn_lds(d->Cin);
-    TG_CHECK(lds <= FV_LDS_MAX, "tamgcn_f2v_gcn: %zu bytes of LDS", lds);
-    tg_launch_lds<f2v_gcn_kernel<FV_V>>(FV_LDS_MAX, dim3(ceil_div(d->T, FV_BT) * (d->Cout / FV_CT), d->N), dim3(FV_NT), lds, (hipStream_t)stream, a);
-    tamgcn_note_kernel("f2v_gcn_kernel");
-    TG_LAUNCH_CHECK("tamgcn_f2v_gcn");
+    TG_CHECK(lds <= FV_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
+    const dim3 grid(ceil_div(d->T, FV_BT) * (d->Cout / FV_CT), d->N);
+    if (groups) {
+        if (tg_groups_ok(d->N, groups, who) || tg_gcn_group_strides_ok(d, a.vec12, a.vec4, a.vec3, a.vecd, who)) return -1;
+        tg_launch_lds<f2v_gcn_grouped_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tamgcn_note_kernel("f2v_gcn_grouped_kernel");
+    } else {
+        tg_launch_lds<f2v_gcn_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tamgcn_note_kernel("f2v_gcn_kernel");
+    }
+    TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-extern "C" int tamgcn_f2v_gemm(const tamgcn_f2_gemm_desc* d, void* stream) {
-    TG_CHECK(d && d->x && d->w && d->b && d->out, "tamgcn_f2v_gemm: null pointer");
-    TG_CHECK(d->V == FV_V, "tamgcn_f2v_gemm: V=%d (built for V = 25)", d->V);
+int fv_gemm_launch(const tamgcn_f2_gemm_desc* d, int groups, void* stream, const char* who) {
+    TG_CHECK(d && d->x && d->w && d->b && d->out, "%s: null pointer", who);
+    TG_CHECK(d->V == FV_V, "%s: V=%d (built for V = 25)", who, d->V);
     TG_CHECK(d->N > 0 && d->T > 0 && d->K > 0 && d->K <= 256 && d->M > 0 && d->M % 16 == 0,
-             "tamgcn_f2v_gemm: bad shape N=%d T=%d K=%d M=%d (K <= 256, M %% 16 == 0)", d->N, d->T, d->K, d->M);
-    TG_CHECK(d->mode == 0 || d->mode == 1, "tamgcn_f2v_gemm: mode=%d", d->mode);
-    TG_CHECK(d->mode != 0 || d->add, "tamgcn_f2v_gemm: mode 0 needs the addend");
-    TG_CHECK(al16(d->x) && al16(d->out) && (!d->add || al16(d->add)), "tamgcn_f2v_gemm: activations must be 16-byte aligned");
+             "%s: bad shape N=%d T=%d K=%d M=%d (K <= 256, M %% 16 == 0)", who, d->N, d->T, d->K, d->M);
+    TG_CHECK(d->mode == 0 || d->mode == 1, "%s: mode=%d", who, d->mode);
+    TG_CHECK(d->mode != 0 || d->add, "%s: mode 0 needs the addend", who);
+    TG_CHECK(al16(d->x) && al16(d->out) && (!d->add || al16(d->add)), "%s: activations must be 16-byte aligned", who);
     FvGemmArgs a;
     a.N = d->N; a.K = d->K; a.M = d->M; a.T = d->T; a.mode = d->mode; a.relu_rows = d->relu_rows;
     a.vec = d->K % 16 == 0 && al16(d->w);
     a.x = d->x; a.w = d->w; a.b = d->b; a.add = d->add; a.out = d->out;
     const size_t lds = fv_gemm_lds(d->K);
-    TG_CHECK(lds <= FV_LDS_MAX, "tamgcn_f2v_gemm: %zu bytes of LDS", lds);
-    tg_launch_lds<f2v_gemm_kernel<FV_V>>(FV_LDS_MAX, dim3(ceil_div(d->T, FV_BT) * (d->M / 16), d->N), dim3(FV_NT), lds, (hipStream_t)stream, a);
-    tamgcn_note_kernel("f2v_gemm_kernel");
-    TG_LAUNCH_CHECK("tamgcn_f2v_gemm");
+    TG_CHECK(lds <= FV_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
+    const dim3 grid(ceil_div(d->T, FV_BT) * (d->M / 16), d->N);
+    if (groups) {
+        if (tg_groups_ok(d->N, groups, who)) return -1;
+        if (tg_group_stride_ok(a.vec, (long long)d->M * d->K, who, "w")) return -1;
+        tg_launch_lds<f2v_gemm_grouped_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tamgcn_note_kernel("f2v_gemm_grouped_kernel");
+    } else {
+        tg_launch_lds<f2v_gemm_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tamgcn_note_kernel("f2v_gemm_kernel");
+    }
+    TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-extern "C" int tamgcn_f2v_tcn(const tamgcn_f2_tcn_desc* d, void* stream) {
-    TG_CHECK(d && d->h && d->out && d->sp && d->tp, "tamgcn_f2v_tcn: null pointer");
-    TG_CHECK(d->V == FV_V, "tamgcn_f2v_tcn: V=%d (built for V = 25)", d->V);
+int fv_tcn_launch(const tamgcn_f2_tcn_desc* d, int groups, void* stream, const char* who) {
+    TG_CHECK(d && d->h && d->out && d->sp && d->tp, "%s: null pointer", who);
+    TG_CHECK(d->V == FV_V, "%s: V=%d (built for V = 25)", who, d->V);
     TG_CHECK(d->N > 0 && d->T > 0 && d->Cout > 0 && d->Cout % 16 == 0 && d->stride >= 1 && d->stride <= 2,
-             "tamgcn_f2v_tcn: bad shape N=%d T=%d Cout=%d stride=%d", d->N, d->T, d->Cout, d->stride);
+             "%s: bad shape N=%d T=%d Cout=%d stride=%d", who, d->N, d->T, d->Cout, d->stride);
     TG_CHECK(d->nb >= 1 && d->nb <= 4 && d->Cb % 16 == 0 && d->Cb <= 64 && (d->nb + 2) * d->Cb == d->Cout,
-             "tamgcn_f2v_tcn: nb=%d Cb=%d Cout=%d (Cb %% 16 == 0, Cb <= 64, (nb + 2) Cb == Cout)", d->nb, d->Cb, d->Cout);
-    TG_CHECK(d->ks >= 1 && d->ks % 2 == 1, "tamgcn_f2v_tcn: kernel size %d", d->ks);
+             "%s: nb=%d Cb=%d Cout=%d (Cb %% 16 == 0, Cb <= 64, (nb + 2) Cb == Cout)", who, d->nb, d->Cb, d->Cout);
+    TG_CHECK(d->ks >= 1 && d->ks % 2 == 1, "%s: kernel size %d", who, d->ks);
     for (int b = 0; b < d->nb; ++b) {
-        TG_CHECK(d->wt[b] && d->bt[b] && d->dil[b] >= 1, "tamgcn_f2v_tcn: branch %d: null weights or dilation %d", b, d->dil[b]);
-        TG_CHECK((FV_BT - 1) * d->stride + (d->ks - 1) * d->dil[b] + 1 <= FV_HF, "tamgcn_f2v_tcn: branch %d: halo of k=%d dilation %d stride %d exceeds %d frames",
-                 b, d->ks, d->dil[b], d->stride, FV_HF);
+        TG_CHECK(d->wt[b] && d->bt[b] && d->dil[b] >= 1, "%s: branch %d: null weights or dilation %d", who, b, d->dil[b]);
+        TG_CHECK((FV_BT - 1) * d->stride + (d->ks - 1) * d->dil[b] + 1 <= FV_HF, "%s: branch %d: halo of k=%d dilation %d stride %d exceeds %d frames",
+                 who, b, d->ks, d->dil[b], d->stride, FV_HF);
     }
-    TG_CHECK(d->res_mode >= 0 && d->res_mode <= 2, "tamgcn_f2v_tcn: res_mode=%d", d->res_mode);
-    TG_CHECK(d->res_mode == 0 || d->x, "tamgcn_f2v_tcn: residual without the block input");
-    TG_CHECK(d->res_mode != 1 || (d->Cin == d->Cout && d->stride == 1), "tamgcn_f2v_tcn: identity residual needs Cin == Cout, stride 1");
-    TG_CHECK(d->res_mode != 2 || (d->wr && d->br && d->Cin > 0 && d->Cin <= 256), "tamgcn_f2v_tcn: convolutional residual: weights / Cin=%d", d->Cin);
+    TG_CHECK(d->res_mode >= 0 && d->res_mode <= 2, "%s: res_mode=%d", who, d->res_mode);
+    TG_CHECK(d->res_mode == 0 || d->x, "%s: residual without the block input", who);
+    TG_CHECK(d->res_mode != 1 || (d->Cin == d->Cout && d->stride == 1), "%s: identity residual needs Cin == Cout, stride 1", who);
+    TG_CHECK(d->res_mode != 2 || (d->wr && d->br && d->Cin > 0 && d->Cin <= 256), "%s: convolutional residual: weights / Cin=%d", who, d->Cin);
     TG_CHECK(al16(d->h) && al4(d->out) && (!d->x || al4(d->x)) && (!d->xpart || al16(d->xpart)),
-             "tamgcn_f2v_tcn: h and xpart must be 16-byte, x and out 4-byte aligned");
+             "%s: h and xpart must be 16-byte, x and out 4-byte aligned", who);
     FvTcnArgs a;
     a.N = d->N; a.Cin = d->Cin; a.Cout = d->Cout; a.T = d->T; a.stride = d->stride; a.T2 = (d->T - 1) / d->stride + 1;
     a.Cb = d->Cb; a.nb = d->nb; a.ks = d->ks; a.res_mode = d->res_mode;
@@ -733,9 +786,42 @@ extern "C" int tamgcn_f2v_tcn(const tamgcn_f2_tcn_desc* d, void* stream) {
     a.vecr = d->res_mode == 2 && d->Cin % 16 == 0 && al16(d->wr);
     a.h = d->h; a.sp = d->sp; a.tp = d->tp; a.x = d->x; a.wr = d->wr; a.br = d->br; a.out = d->out; a.xpart = d->xpart;
     const size_t lds = fv_tcn_lds(d->Cin, d->Cb, d->res_mode);
-    TG_CHECK(lds <= FV_LDS_MAX, "tamgcn_f2v_tcn: %zu bytes of LDS", lds);
-    tg_launch_lds<f2v_tcn_kernel<FV_V>>(FV_LDS_MAX, dim3(ceil_div(a.T2, FV_BT) * (d->Cout / 16), d->N), dim3(FV_NT), lds, (hipStream_t)stream, a);
-    tamgcn_note_kernel("f2v_tcn_kernel");
-    TG_LAUNCH_CHECK("tamgcn_f2v_tcn");
+    TG_CHECK(lds <= FV_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
+    const dim3 grid(ceil_div(a.T2, FV_BT) * (d->Cout / 16), d->N);
+    if (groups) {
+        if (tg_groups_ok(d->N, groups, who)) return -1;
+        if (tg_group_stride_ok(a.vect, (long long)d->Cb * d->Cb * d->ks, who, "wt")) return -1;
+        if (tg_group_stride_ok(a.vecr, (long long)d->Cout * d->Cin, who, "wr")) return -1;
+        tg_launch_lds<f2v_tcn_grouped_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tamgcn_note_kernel("f2v_tcn_grouped_kernel");
+    } else {
+        tg_launch_lds<f2v_tcn_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tamgcn_note_kernel("f2v_tcn_kernel");
+    }
+    TG_LAUNCH_CHECK(who);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int tamgcn_f2v_e(const tamgcn_f2_gcn_desc* d, void* stream) { return fv_e_launch(d, 0, stream, "tamgcn_f2v_e"); }
+extern "C" int tamgcn_f2v_gcn(const tamgcn_f2_gcn_desc* d, void* stream) { return fv_gcn_launch(d, 0, stream, "tamgcn_f2v_gcn"); }
+extern "C" int tamgcn_f2v_gemm(const tamgcn_f2_gemm_desc* d, void* stream) { return fv_gemm_launch(d, 0, stream, "tamgcn_f2v_gemm"); }
+extern "C" int tamgcn_f2v_tcn(const tamgcn_f2_tcn_desc* d, void* stream) { return fv_tcn_launch(d, 0, stream, "tamgcn_f2v_tcn"); }
+
+static int fv_groups_arg(int groups, const char* who) {
+    TG_CHECK(groups >= 1, "%s: groups=%d", who, groups);
+    return 0;
+}
+extern "C" int tamgcn_f2v_e_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream) {
+    return fv_groups_arg(groups, "tamgcn_f2v_e_grouped") ? -1 : fv_e_launch(d, groups, stream, "tamgcn_f2v_e_grouped");
+}
+extern "C" int tamgcn_f2v_gcn_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream) {
+    return fv_groups_arg(groups, "tamgcn_f2v_gcn_grouped") ? -1 : fv_gcn_launch(d, groups, stream, "tamgcn_f2v_gcn_grouped");
+}
+extern "C" int tamgcn_f2v_gemm_grouped(const tamgcn_f2_gemm_desc* d, int groups, void* stream) {
+    return fv_groups_arg(groups, "tamgcn_f2v_gemm_grouped") ? -1 : fv_gemm_launch(d, groups, stream, "tamgcn_f2v_gemm_grouped");
+}
+extern "C" int tamgcn_f2v_tcn_grouped(const tamgcn_f2_tcn_desc* d, int groups, void* stream) {
+    return fv_groups_arg(groups, "tamgcn_f2v_tcn_grouped") ? -1 : fv_tcn_launch(d, groups, stream, "tamgcn_f2v_tcn_grouped");
 }

@@ -61,6 +61,37 @@ __global__ __launch_bounds__(SH_NT) void stem_apply_kernel(const float* x, const
     }
 }
 
+// A multi-stream ensemble's stems in one launch: out[(g*N + n)*M + m, c, t, v] = c1_g[j] * stream_{modes[g]}(x)[n, c, t, v, m] + c0_g[j].
+// The stream arithmetic is feeder.hip's stream_derive_kernel's, the affine is stem_apply_kernel's fma: bit-equal to that pair.
+// One workgroup per (group, n, c) row of x; the frame after the last one is never read.
+__global__ __launch_bounds__(SH_NT) void stem_streams_eval_kernel(const float* __restrict__ x, const int* __restrict__ parent, const int* __restrict__ modes,
+                                                                  const float* __restrict__ coef, int N, int C, int T, int V, int M, float* __restrict__ out) {
+    const int row = blockIdx.x, g = blockIdx.y, n = row / C, c = row - n * C;
+    const int TV = T * V, VM = V * M, len = TV * M, J = C * V * M;
+    const int mode = modes[g];
+    const float* cg = coef + (long long)g * 3 * J;
+    const float* xr0 = x + (long long)row * len;
+    for (int i = threadIdx.x; i < len; i += SH_NT) {
+        const int tv = i / M, m = i - tv * M;
+        const int t = tv / V, v = tv - t * V;
+        const int vm = v * M + m;
+        const float* xr = xr0 + t * VM;
+        const float cur = xr[vm];
+        float d = cur;
+        if (mode != 0) {
+            const int pv = parent[v] * M + m;
+            if (mode == 1) d = cur - xr[pv];
+            else if (t == T - 1) d = 0.f;
+            else {
+                const float* xn = xr + VM;                  // frame t + 1
+                d = mode == 2 ? xn[vm] - cur : (xn[vm] - xn[pv]) - (cur - xr[pv]);
+            }
+        }
+        const int j = (m * V + v) * C + c;
+        out[((((long long)g * N + n) * M + m) * C + c) * TV + tv] = fmaf(cg[j], d, cg[2 * J + j]);
+    }
+}
+
 // pooled[n][c] = mean over (m, t, v) of x[(n*M+m), c, t, v]; one wave per (n, c)
 __global__ __launch_bounds__(SH_NT) void pool_fwd_kernel(const float* x, int N, int C, int L, int M, float* pooled) {
     const int row = blockIdx.x * (SH_NT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -91,6 +122,19 @@ __global__ __launch_bounds__(SH_NT) void fc_fwd_kernel(const float* pooled, cons
         for (int c = lane; c < C; c += 64) s = fmaf(pooled[(long long)n * C + c], W[(long long)k * C + c], s);
         s = wave_sum64(s);
         if (lane == 0) logits[(long long)n * K + k] = s + (b ? b[k] : 0.f);
+    }
+}
+
+// the same for G heads in one launch: row blockIdx.x of group blockIdx.y; scores [G][N][K]
+__global__ __launch_bounds__(SH_NT) void fc_grouped_kernel(const float* pooled, const float* W, const float* b, int N, int C, int K, float* scores) {
+    const int g = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long n = (long long)g * N + blockIdx.x;
+    const float* Wg = W + (long long)g * K * C;
+    for (int k = wave; k < K; k += SH_NT / 64) {
+        float s = 0.f;
+        for (int c = lane; c < C; c += 64) s = fmaf(pooled[n * C + c], Wg[(long long)k * C + c], s);
+        s = wave_sum64(s);
+        if (lane == 0) scores[n * K + k] = s + (b ? b[g * K + k] : 0.f);
     }
 }
 
@@ -246,6 +290,24 @@ extern "C" int tamgcn_stem_apply(const float* x, const float* dout, const float*
                        dout ? 1 : 0);
     tamgcn_note_kernel("stem_apply_kernel");
     TG_LAUNCH_CHECK("tamgcn_stem_apply");
+    return 0;
+}
+
+extern "C" int tamgcn_stem_streams_eval(const float* x, const int* parent, const int* modes, const float* coef, int G, int N, int C, int T, int V, int M,
+                                        float* out, void* stream) {
+    TG_CHECK(x && parent && modes && coef && out && G > 0 && G <= 65535 && sh_dims_ok(N, C, T, V, M), "tamgcn_stem_streams_eval: bad args");
+    TG_CHECK((long long)T * V * M < (1LL << 20) && (long long)N * C < (1LL << 31), "tamgcn_stem_streams_eval: a row of T*V*M = %lld floats (limit 2^20)", (long long)T * V * M);
+    hipLaunchKernelGGL(stem_streams_eval_kernel, dim3((unsigned)(N * C), (unsigned)G), dim3(SH_NT), 0, (hipStream_t)stream, x, parent, modes, coef, N, C, T, V, M, out);
+    tamgcn_note_kernel("stem_streams_eval_kernel");
+    TG_LAUNCH_CHECK("tamgcn_stem_streams_eval");
+    return 0;
+}
+
+extern "C" int tamgcn_head_fc_grouped(const float* pooled, const float* W, const float* b, int G, int N, int C, int K, float* scores, void* stream) {
+    TG_CHECK(pooled && W && scores && G > 0 && G <= 65535 && N > 0 && C > 0 && K > 0, "tamgcn_head_fc_grouped: bad args");
+    hipLaunchKernelGGL(fc_grouped_kernel, dim3((unsigned)N, (unsigned)G), dim3(SH_NT), 0, (hipStream_t)stream, pooled, W, b, N, C, K, scores);
+    tamgcn_note_kernel("fc_grouped_kernel");
+    TG_LAUNCH_CHECK("tamgcn_head_fc_grouped");
     return 0;
 }
 

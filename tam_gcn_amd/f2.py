@@ -15,7 +15,11 @@ an optimiser step, load_state_dict or a train-mode forward).
 `Model.forward` routes here by itself in eval mode without autograd for batches of at most F2_MAX_CLIPS clip-persons
 (TAMGCN_F2=0 switches the routing off); `inference.GraphedForward` captures whichever path `Model.forward` takes.
 There is no CPU path and no fallback inside: unsupported geometry raises `Unsupported` BEFORE anything is launched and the
-caller (Model.forward) then takes the general eval path."""
+caller (Model.forward) then takes the general eval path.
+
+`GroupedEval(models)` runs G models of ONE geometry (a multi-stream ensemble: inference.StreamEnsemble) as one launch
+sequence: the grouped entry points (tamgcn_f2_*_grouped, include/tamgcn.h "grouped") take each model's folded tensors
+stacked on a leading group axis, the samples of group g are rows [g n, (g+1) n) of every activation."""
 import ctypes as C
 import os
 from typing import List, Optional, Tuple
@@ -26,7 +30,7 @@ from torch import Tensor
 from . import _lib
 from . import functional as Fn
 
-__all__ = ['FusedEval', 'Unsupported', 'F2_MAX_CLIPS', 'enabled']
+__all__ = ['FusedEval', 'GroupedEval', 'Unsupported', 'F2_MAX_CLIPS', 'enabled']
 
 F2_MAX_CLIPS = int(os.environ.get('TAMGCN_F2_MAX_CLIPS', '32'))      # clip-persons (N*M) up to which Model.forward routes here
 
@@ -212,45 +216,7 @@ def _opt(t):
 
 @torch.library.custom_op('tamgcn::tcn_gcn_unit_eval', mutates_args=())
 def tcn_gcn_unit_eval(x: Tensor, xpart: Optional[Tensor], params: List[Tensor], geom: List[int]) -> Tuple[Tensor, Tensor]:
-    lib = _lib.load()
-    if not x.is_cuda or x.dtype != torch.float32:
-        raise RuntimeError('tamgcn::tcn_gcn_unit_eval: expected a float32 HIP (cuda) tensor; there is no CPU path')
-    x = x.contiguous()
-    (W12, B12, W3, B3, W4, B4, PA, alpha, sy, ty, Wd, bd, Wo, bo, We, be, sp, tp, Wr, br), rest = params[:20], params[20:]
-    R, gmode, Cb, nb, ks, stride, rmode = geom[:7]
-    dils = geom[7:7 + nb]
-    N, Cin, T, V = x.shape
-    Cout = W3.shape[0] // 3
-    dev = x.device
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    E = torch.empty(N, 3, Cout, V, V, device=dev)
-    ws = torch.empty(4, N, Cout, T, V, device=dev)               # y + res, res - y, g, h
-    sm, df, g, h = ws[0], ws[1], ws[2], ws[3]
-    d = _lib.F2GcnDesc(N=N, Cin=Cin, Cout=Cout, T=T, V=V, S=3, R=R, res_mode=gmode,
-                       x=x.data_ptr(), w12=W12.data_ptr(), b12=B12.data_ptr(), w4=W4.data_ptr(), b4=B4.data_ptr(),
-                       A=PA.data_ptr(), alpha=alpha.data_ptr(), w3=W3.data_ptr(), b3=B3.data_ptr(),
-                       sy=sy.data_ptr(), ty=ty.data_ptr(), wd=_opt(Wd), bd=_opt(bd),
-                       E=E.data_ptr(), sum=sm.data_ptr(), diff=df.data_ptr(), xpart=_opt(xpart))
-    _lib.check(lib.tamgcn_f2_e(C.byref(d), st), 'tamgcn_f2_e')
-    _lib.check(lib.tamgcn_f2_gcn(C.byref(d), st), 'tamgcn_f2_gcn')
-    q = _lib.F2GemmDesc(N=N, K=Cout, M=Cout, T=T, V=V, mode=0, relu_rows=0, x=df.data_ptr(), w=Wo.data_ptr(), b=bo.data_ptr(),
-                        add=sm.data_ptr(), out=g.data_ptr())
-    _lib.check(lib.tamgcn_f2_gemm(C.byref(q), st), 'tamgcn_f2_gemm')
-    q = _lib.F2GemmDesc(N=N, K=Cout, M=Cout, T=T, V=V, mode=1, relu_rows=(nb + 1) * Cb, x=g.data_ptr(), w=We.data_ptr(),
-                        b=be.data_ptr(), add=None, out=h.data_ptr())
-    _lib.check(lib.tamgcn_f2_gemm(C.byref(q), st), 'tamgcn_f2_gemm')
-    T2 = (T - 1) // stride + 1
-    out = torch.empty(N, Cout, T2, V, device=dev)
-    xp = torch.empty(N, (T2 + 3) // 4, Cout, V, device=dev)      # per-tile frame sums: the next block's xbar
-    t = _lib.F2TcnDesc(N=N, Cin=Wr.shape[1] if rmode == 2 else Cin, Cout=Cout, T=T, V=V, stride=stride, Cb=Cb, nb=nb, ks=ks,
-                       res_mode=rmode, h=h.data_ptr(), sp=sp.data_ptr(), tp=tp.data_ptr(), x=x.data_ptr(), wr=_opt(Wr), br=_opt(br),
-                       out=out.data_ptr(), xpart=xp.data_ptr())
-    for i in range(nb):
-        t.dil[i] = dils[i]
-        t.wt[i] = rest[2 * i].data_ptr()
-        t.bt[i] = rest[2 * i + 1].data_ptr()
-    _lib.check(lib.tamgcn_f2_tcn(C.byref(t), st), 'tamgcn_f2_tcn')
-    return out, xp
+    return _unit('f2', x, xpart, params, geom, None)
 
 
 @tcn_gcn_unit_eval.register_fake
@@ -259,3 +225,225 @@ def _(x, xpart, params, geom):
     Cout = params[2].shape[0] // 3
     T2 = (T - 1) // geom[5] + 1
     return x.new_empty(N, Cout, T2, V), x.new_empty(N, (T2 + 3) // 4, Cout, V)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The grouped block: `groups` models of one geometry in the same five launches (include/tamgcn.h, "grouped").
+#   x      (groups*n, Cin, T, V): rows [g n, (g+1) n) are group g's samples; xpart likewise
+#   params the list above with EVERY tensor stacked on a new leading group axis (an absent one: no elements)
+#   geom   as above, shared by all groups
+# Group g's slice of the result is bit-equal to tcn_gcn_unit_eval on group g's slice and parameters.
+# ----------------------------------------------------------------------------------------------------------------------
+def _unit(fam, x, xpart, params, geom, groups):
+    """The five launches of one block: the body of all four registered block operators.  fam 'f2' (V = 20) | 'f2v' (V = 25:
+    frames of 28 floats in the family's own buffers, 12 bytes of slack behind the contiguous input and output); groups None:
+    the plain entry points on one model's params, else the grouped ones on params stacked on a leading group axis."""
+    from . import ops
+    lib = _lib.load()
+    sfx = '' if groups is None else '_grouped'
+    name = f'tamgcn::tcn_gcn_unit_eval{"" if fam == "f2" else "_v25"}{sfx}'
+    V_, VP = (20, 20) if fam == 'f2' else (25, 28)
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise RuntimeError(f'{name}: expected a float32 HIP (cuda) tensor; there is no CPU path')
+    if x.dim() != 4 or x.shape[3] != V_:
+        raise RuntimeError(f'{name}: expected (N, C, T, {V_}), got {tuple(x.shape)}')
+    if groups is not None:
+        if groups < 1 or x.shape[0] % groups:
+            raise RuntimeError(f'{name}: {x.shape[0]} samples are not a multiple of groups = {groups}')
+        if any(t.shape[0] != groups for t in params):
+            raise RuntimeError(f'{name}: every tensor of params needs a leading axis of groups = {groups}')
+    ga = () if groups is None else (groups,)                     # the grouped entry points take it after the descriptor
+    lead = 0 if groups is None else 1
+    x = x.contiguous() if fam == 'f2' else ops.with_slack(x.contiguous())
+    params = [t.contiguous() for t in params]
+    (W12, B12, W3, B3, W4, B4, PA, alpha, sy, ty, Wd, bd, Wo, bo, We, be, sp, tp, Wr, br), rest = params[:20], params[20:]
+    R, gmode, Cb, nb, ks, stride, rmode = geom[:7]
+    dils = geom[7:7 + nb]
+    N, Cin, T, _ = x.shape
+    Cout = W3.shape[lead] // 3
+    dev = x.device
+    if xpart is not None:
+        if tuple(xpart.shape) != (N, (T + 3) // 4, Cin, VP):
+            raise RuntimeError(f'{name}: xpart {tuple(xpart.shape)}, expected {(N, (T + 3) // 4, Cin, VP)}')
+        xpart = xpart.contiguous()
+    fn = {k: getattr(lib, f'tamgcn_{fam}_{k}{sfx}') for k in ('e', 'gcn', 'gemm', 'tcn')}
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    E = torch.empty(N, 3, Cout, V_, VP, device=dev)
+    ws = torch.empty(4, N, Cout, T, VP, device=dev)              # y + res, res - y, g, h
+    sm, df, g, h = ws[0], ws[1], ws[2], ws[3]
+    d = _lib.F2GcnDesc(N=N, Cin=Cin, Cout=Cout, T=T, V=V_, S=3, R=R, res_mode=gmode,
+                       x=x.data_ptr(), w12=W12.data_ptr(), b12=B12.data_ptr(), w4=W4.data_ptr(), b4=B4.data_ptr(),
+                       A=PA.data_ptr(), alpha=alpha.data_ptr(), w3=W3.data_ptr(), b3=B3.data_ptr(),
+                       sy=sy.data_ptr(), ty=ty.data_ptr(), wd=_opt(Wd), bd=_opt(bd),
+                       E=E.data_ptr(), sum=sm.data_ptr(), diff=df.data_ptr(), xpart=_opt(xpart))
+    _lib.check(fn['e'](C.byref(d), *ga, st), f'tamgcn_{fam}_e{sfx}')
+    _lib.check(fn['gcn'](C.byref(d), *ga, st), f'tamgcn_{fam}_gcn{sfx}')
+    q = _lib.F2GemmDesc(N=N, K=Cout, M=Cout, T=T, V=V_, mode=0, relu_rows=0, x=df.data_ptr(), w=Wo.data_ptr(), b=bo.data_ptr(),
+                        add=sm.data_ptr(), out=g.data_ptr())
+    _lib.check(fn['gemm'](C.byref(q), *ga, st), f'tamgcn_{fam}_gemm{sfx}')
+    q = _lib.F2GemmDesc(N=N, K=Cout, M=Cout, T=T, V=V_, mode=1, relu_rows=(nb + 1) * Cb, x=g.data_ptr(), w=We.data_ptr(),
+                        b=be.data_ptr(), add=None, out=h.data_ptr())
+    _lib.check(fn['gemm'](C.byref(q), *ga, st), f'tamgcn_{fam}_gemm{sfx}')
+    T2 = (T - 1) // stride + 1
+    out = torch.empty(N, Cout, T2, V_, device=dev) if fam == 'f2' else ops.empty(N, Cout, T2, V_, like=x)
+    xp = torch.empty(N, (T2 + 3) // 4, Cout, VP, device=dev)     # per-tile frame sums: the next block's xbar
+    t = _lib.F2TcnDesc(N=N, Cin=Wr.shape[lead + 1] if rmode == 2 else Cin, Cout=Cout, T=T, V=V_, stride=stride, Cb=Cb, nb=nb, ks=ks,
+                       res_mode=rmode, h=h.data_ptr(), sp=sp.data_ptr(), tp=tp.data_ptr(), x=x.data_ptr(), wr=_opt(Wr), br=_opt(br),
+                       out=out.data_ptr(), xpart=xp.data_ptr())
+    for i in range(nb):
+        t.dil[i] = dils[i]
+        t.wt[i] = rest[2 * i].data_ptr()
+        t.bt[i] = rest[2 * i + 1].data_ptr()
+    _lib.check(fn['tcn'](C.byref(t), *ga, st), f'tamgcn_{fam}_tcn{sfx}')
+    return out, xp
+
+
+@torch.library.custom_op('tamgcn::tcn_gcn_unit_eval_grouped', mutates_args=())
+def tcn_gcn_unit_eval_grouped(x: Tensor, xpart: Optional[Tensor], params: List[Tensor], geom: List[int], groups: int) -> Tuple[Tensor, Tensor]:
+    return _unit('f2', x, xpart, params, geom, groups)
+
+
+@tcn_gcn_unit_eval_grouped.register_fake
+def _(x, xpart, params, geom, groups):
+    N, _, T, V = x.shape
+    Cout = params[2].shape[1] // 3
+    T2 = (T - 1) // geom[5] + 1
+    return x.new_empty(N, Cout, T2, V), x.new_empty(N, (T2 + 3) // 4, Cout, V)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# G models as one launch sequence
+# ----------------------------------------------------------------------------------------------------------------------
+def stack_blocks(per_model):
+    """per_model: G lists of _Block (one per TCN_GCN_unit) of ONE geometry -> per block (stacked params, geom).
+    ValueError naming the first field in which a model differs from model 0."""
+    out = []
+    for i, blks in enumerate(zip(*per_model), 1):
+        b0 = blks[0]
+        for g, b in enumerate(blks[1:], 1):
+            for field in ('Cin', 'Cout', 'geom'):
+                if getattr(b, field) != getattr(b0, field):
+                    raise ValueError(f'grouped eval: model {g} differs from model 0 in l{i}.{field}: '
+                                     f'{getattr(b, field)} != {getattr(b0, field)}')
+            if [tuple(t.shape) for t in b.params] != [tuple(t.shape) for t in b0.params]:
+                raise ValueError(f'grouped eval: model {g} differs from model 0 in the parameter shapes of l{i}')
+        out.append(([torch.stack([b.params[j] for b in blks]) for j in range(len(b0.params))], list(b0.geom)))
+    return out
+
+
+def _model_fields(m):
+    """The geometry all models of a group must share, as (name, value) pairs; the block geometry is compared after folding."""
+    V = getattr(m, 'num_point', None)
+    cin = m.l1.gcn1.in_c
+    return [('num_point', V), ('num_class', getattr(m, 'num_class', None)), ('in_channels', cin),
+            ('num_person', m.data_bn.num_features // (cin * V) if V else None)]
+
+
+class GroupedEval:
+    """G models of one geometry (V = 20: the f2 kernels, V = 25: f2v) as ONE launch sequence: a fused stem
+    (tamgcn_stem_streams_eval), five grouped launches per block, one pool and one grouped fc -- 54 launches whatever G is.
+
+        eng = GroupedEval(models)                       # all in eval() mode, on one device
+        scores = eng(x, parent, modes)                  # x (N, C, T, V, M) JOINT clips; modes int32 [G] on the device
+                                                        # -> (G, N, K): model g on stream modes[g] of x
+
+    Every model keeps its own FusedEval(V) for the folding and the state key: a model whose state changed is folded again and
+    only its slice of the stacked tensors is rewritten."""
+
+    def __init__(self, models):
+        models = list(models)
+        if not models:
+            raise ValueError('GroupedEval: no models')
+        for g, m in enumerate(models):
+            if m.training:
+                raise ValueError(f'GroupedEval: model {g} is in train mode; put every model in eval() mode first')
+        devs = [next(m.parameters()).device for m in models]
+        for g, d in enumerate(devs):
+            if d != devs[0]:
+                raise ValueError(f'GroupedEval: model {g} is on {d}, model 0 on {devs[0]}')
+        f0 = _model_fields(models[0])
+        for g, m in enumerate(models[1:], 1):
+            for (name, a), (_, b) in zip(f0, _model_fields(m)):
+                if a != b:
+                    raise ValueError(f'GroupedEval: model {g} differs from model 0 in {name}: {b} != {a}')
+        V = f0[0][1]
+        if V == 20:
+            cls, self.FAMILY = FusedEval, 'f2'
+        elif V == 25:
+            from .f2v import FusedEvalV
+            cls, self.FAMILY = FusedEvalV, 'f2v'
+        else:
+            raise Unsupported(f'{V} joints (the small-batch kernels are built for V = 20 and V = 25)')
+        self.V, self.M, self.K = V, f0[3][1], f0[1][1]
+        self.models = models
+        self.engines = [cls(m) for m in models]
+        self._seen = [None] * len(models)                          # the _blocks list of each engine the stacks were built from
+        self._stacked = self._coef = self._fcw = self._fcb = None
+
+    def keep_alive(self):
+        """What a captured graph reads through raw pointers (inference.GraphedForward keeps it)."""
+        return [self._stacked, self._coef, self._fcw, self._fcb]
+
+    def _stem_coef(self, m, like):
+        bn = Fn.BN(m.data_bn)
+        return Fn._eval_cached(m.data_bn, 'stem', [bn], lambda: Fn._eval_coefs([(bn, 0)], bn.C, like))[0]
+
+    def _packed(self, device):
+        per_model = [e._packed(device) for e in self.engines]      # folds again whichever model's state key changed
+        with torch.no_grad():
+            if self._stacked is None:
+                self._stacked = stack_blocks(per_model)            # geometry checks: before anything is launched
+                like = per_model[0][0].sy
+                self._coef = torch.stack([self._stem_coef(m, like) for m in self.models]).contiguous()
+                self._fcw = torch.stack([m.fc.weight.detach() for m in self.models]).contiguous()
+                self._fcb = torch.stack([m.fc.bias.detach() for m in self.models]).contiguous()
+            else:
+                for g, blks in enumerate(per_model):
+                    if blks is self._seen[g]:
+                        continue
+                    for i, (b, (stk, geom)) in enumerate(zip(blks, self._stacked), 1):
+                        if list(b.geom) != geom or [tuple(t.shape) for t in b.params] != [tuple(t.shape[1:]) for t in stk]:
+                            raise ValueError(f'grouped eval: model {g} no longer has the geometry of its group in l{i}')
+                        for dst, src in zip(stk, b.params):
+                            if src.numel():
+                                dst[g].copy_(src)
+                    m = self.models[g]
+                    self._coef[g].copy_(self._stem_coef(m, self._coef))
+                    self._fcw[g].copy_(m.fc.weight.detach())
+                    self._fcb[g].copy_(m.fc.bias.detach())
+            self._seen = per_model
+        return self._stacked
+
+    def check_input(self, x):
+        """-> x as (N, C, T, V, M); the guards of FusedEval.blocks, before anything is launched."""
+        for g, m in enumerate(self.models):
+            if m.training:
+                raise RuntimeError(f'GroupedEval: model {g} went back to train() mode')
+        if torch.is_grad_enabled() and any(p.requires_grad for m in self.models for p in m.parameters()):
+            raise RuntimeError('GroupedEval is an inference path: call it under torch.no_grad()')
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise RuntimeError('GroupedEval: expected a float32 HIP (cuda) tensor; there is no CPU path')
+        if x.dim() == 3:
+            N, T, VC = x.shape
+            x = x.view(N, T, self.V, -1).permute(0, 3, 1, 2).contiguous().unsqueeze(-1)
+        if x.dim() != 5 or x.shape[3] != self.V or x.shape[4] != self.M:
+            raise Unsupported(f'input {tuple(x.shape)}: expected (N, C, T, {self.V}, {self.M})')
+        return x.contiguous()
+
+    def __call__(self, x, parent, modes):
+        x = self.check_input(x)
+        return self.run(x, parent, modes, self._packed(x.device))
+
+    def run(self, x, parent, modes, stacked):
+        """x already checked (check_input), stacked = self._packed(x.device): the launches alone."""
+        from . import ops
+        G = len(self.models)
+        h = ops.stem_streams_eval(x, parent, modes, self._coef)
+        xp = None
+        blk = torch.ops.tamgcn.tcn_gcn_unit_eval_grouped if self.FAMILY == 'f2' else torch.ops.tamgcn.tcn_gcn_unit_eval_v25_grouped
+        for params, geom in stacked:
+            h, xp = blk(h, xp, params, geom, G)
+        pooled = ops.head_pool_fwd(h, self.M)                      # (G*N, C): the single model's per-row arithmetic
+        return ops.head_fc_grouped(pooled, self._fcw, self._fcb, G)
+
+    forward = __call__

@@ -12,15 +12,13 @@ workspaces and the frame sums, which live inside the operator, have frames of 28
 frames (N * M * T; an NTU clip is 300 frames and two persons, so the bound is in frames and not in clips; TAMGCN_F2V_MAX_FRAMES
 overrides it, TAMGCN_F2=0 switches both families off).  No CPU path, no fallback inside: `Unsupported` is raised before
 anything is launched."""
-import ctypes as C
 import os
 from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
 
-from . import _lib, ops
-from .f2 import FusedEval, Unsupported, enabled, _opt
+from .f2 import FusedEval, Unsupported, enabled, _unit
 
 __all__ = ['FusedEvalV', 'Unsupported', 'F2V_MAX_FRAMES', 'enabled']
 
@@ -44,56 +42,26 @@ class FusedEvalV(FusedEval):
 # ----------------------------------------------------------------------------------------------------------------------
 @torch.library.custom_op('tamgcn::tcn_gcn_unit_eval_v25', mutates_args=())
 def tcn_gcn_unit_eval_v25(x: Tensor, xpart: Optional[Tensor], params: List[Tensor], geom: List[int]) -> Tuple[Tensor, Tensor]:
-    lib = _lib.load()
-    if not x.is_cuda or x.dtype != torch.float32:
-        raise RuntimeError('tamgcn::tcn_gcn_unit_eval_v25: expected a float32 HIP (cuda) tensor; there is no CPU path')
-    if x.dim() != 4 or x.shape[3] != V:
-        raise RuntimeError(f'tamgcn::tcn_gcn_unit_eval_v25: expected (N, C, T, {V}), got {tuple(x.shape)}')
-    x = ops.with_slack(x.contiguous())                           # the last 16-byte piece of the last frame reads 12 bytes past it
-    (W12, B12, W3, B3, W4, B4, PA, alpha, sy, ty, Wd, bd, Wo, bo, We, be, sp, tp, Wr, br), rest = params[:20], params[20:]
-    R, gmode, Cb, nb, ks, stride, rmode = geom[:7]
-    dils = geom[7:7 + nb]
-    N, Cin, T, _ = x.shape
-    Cout = W3.shape[0] // 3
-    dev = x.device
-    if xpart is not None:
-        if tuple(xpart.shape) != (N, (T + 3) // 4, Cin, VP):
-            raise RuntimeError(f'tamgcn::tcn_gcn_unit_eval_v25: xpart {tuple(xpart.shape)}, expected {(N, (T + 3) // 4, Cin, VP)}')
-        xpart = xpart.contiguous()
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    E = torch.empty(N, 3, Cout, V, VP, device=dev)
-    ws = torch.empty(4, N, Cout, T, VP, device=dev)              # y + res, res - y, g, h
-    sm, df, g, h = ws[0], ws[1], ws[2], ws[3]
-    d = _lib.F2GcnDesc(N=N, Cin=Cin, Cout=Cout, T=T, V=V, S=3, R=R, res_mode=gmode,
-                       x=x.data_ptr(), w12=W12.data_ptr(), b12=B12.data_ptr(), w4=W4.data_ptr(), b4=B4.data_ptr(),
-                       A=PA.data_ptr(), alpha=alpha.data_ptr(), w3=W3.data_ptr(), b3=B3.data_ptr(),
-                       sy=sy.data_ptr(), ty=ty.data_ptr(), wd=_opt(Wd), bd=_opt(bd),
-                       E=E.data_ptr(), sum=sm.data_ptr(), diff=df.data_ptr(), xpart=_opt(xpart))
-    _lib.check(lib.tamgcn_f2v_e(C.byref(d), st), 'tamgcn_f2v_e')
-    _lib.check(lib.tamgcn_f2v_gcn(C.byref(d), st), 'tamgcn_f2v_gcn')
-    q = _lib.F2GemmDesc(N=N, K=Cout, M=Cout, T=T, V=V, mode=0, relu_rows=0, x=df.data_ptr(), w=Wo.data_ptr(), b=bo.data_ptr(),
-                        add=sm.data_ptr(), out=g.data_ptr())
-    _lib.check(lib.tamgcn_f2v_gemm(C.byref(q), st), 'tamgcn_f2v_gemm')
-    q = _lib.F2GemmDesc(N=N, K=Cout, M=Cout, T=T, V=V, mode=1, relu_rows=(nb + 1) * Cb, x=g.data_ptr(), w=We.data_ptr(),
-                        b=be.data_ptr(), add=None, out=h.data_ptr())
-    _lib.check(lib.tamgcn_f2v_gemm(C.byref(q), st), 'tamgcn_f2v_gemm')
-    T2 = (T - 1) // stride + 1
-    out = ops.empty(N, Cout, T2, V, like=x)                      # the next block's input: with the slack its reads need
-    xp = torch.empty(N, (T2 + 3) // 4, Cout, VP, device=dev)     # per-tile frame sums: the next block's xbar
-    t = _lib.F2TcnDesc(N=N, Cin=Wr.shape[1] if rmode == 2 else Cin, Cout=Cout, T=T, V=V, stride=stride, Cb=Cb, nb=nb, ks=ks,
-                       res_mode=rmode, h=h.data_ptr(), sp=sp.data_ptr(), tp=tp.data_ptr(), x=x.data_ptr(), wr=_opt(Wr), br=_opt(br),
-                       out=out.data_ptr(), xpart=xp.data_ptr())
-    for i in range(nb):
-        t.dil[i] = dils[i]
-        t.wt[i] = rest[2 * i].data_ptr()
-        t.bt[i] = rest[2 * i + 1].data_ptr()
-    _lib.check(lib.tamgcn_f2v_tcn(C.byref(t), st), 'tamgcn_f2v_tcn')
-    return out, xp
+    return _unit('f2v', x, xpart, params, geom, None)
 
 
 @tcn_gcn_unit_eval_v25.register_fake
 def _(x, xpart, params, geom):
     N, _, T, V_ = x.shape
     Cout = params[2].shape[0] // 3
+    T2 = (T - 1) // geom[5] + 1
+    return x.new_empty(N, Cout, T2, V_), x.new_empty(N, (T2 + 3) // 4, Cout, VP)
+
+
+# The grouped block at V = 25 (f2.tcn_gcn_unit_eval_grouped's arguments: every tensor of params stacked on a leading group axis).
+@torch.library.custom_op('tamgcn::tcn_gcn_unit_eval_v25_grouped', mutates_args=())
+def tcn_gcn_unit_eval_v25_grouped(x: Tensor, xpart: Optional[Tensor], params: List[Tensor], geom: List[int], groups: int) -> Tuple[Tensor, Tensor]:
+    return _unit('f2v', x, xpart, params, geom, groups)
+
+
+@tcn_gcn_unit_eval_v25_grouped.register_fake
+def _(x, xpart, params, geom, groups):
+    N, _, T, V_ = x.shape
+    Cout = params[2].shape[1] // 3
     T2 = (T - 1) // geom[5] + 1
     return x.new_empty(N, Cout, T2, V_), x.new_empty(N, (T2 + 3) // 4, Cout, VP)

@@ -10,10 +10,21 @@ eager -> 2.8 ms, tools/infer_bench.py).
 
 The output tensor is the graph's static buffer: it is overwritten by the next call with the same shape (clone it to keep
 it).  Parameter VALUES may change between calls (the graph reads them through their pointers; the eval path's folded
-BatchNorm coefficients are keyed on parameter versions, so re-capture with .reset() after loading a new state dict)."""
-import torch
+BatchNorm coefficients are keyed on parameter versions, so re-capture with .reset() after loading a new state dict).
 
-__all__ = ['GraphedForward']
+A multi-stream ensemble (the published four-stream accuracies: joint, bone, joint-motion and bone-motion models whose scores
+are summed) as ONE call on the joint clips:
+
+    ens = StreamEnsemble([joint, bone, motion, bone_motion])       # eval() models of one architecture
+    with torch.no_grad():
+        fused = ens(x)                                             # (N, K); GraphedForward(ens) captures it
+        fused, pred, scores = ens.predict(x)                       # + arg max (N) and the per-stream scores (G, N, K)"""
+import torch
+from torch import nn
+
+from . import ops
+
+__all__ = ['GraphedForward', 'StreamEnsemble']
 
 
 class GraphedForward:
@@ -35,6 +46,18 @@ class GraphedForward:
         self._graphs.clear()
 
     def _capture(self, x):
+        # A wrapped object that routes differently when its forward is replayed as a graph (StreamEnsemble) is told so for
+        # the warm-up calls AND the capture: the warm-up must take the route the capture takes.
+        told = hasattr(self.model, '_tamgcn_graphed')
+        if told:
+            before, self.model._tamgcn_graphed = self.model._tamgcn_graphed, True
+        try:
+            return self._capture_told(x)
+        finally:
+            if told:
+                self.model._tamgcn_graphed = before
+
+    def _capture_told(self, x):
         fn = getattr(self.model, self.method)
         static_in = x.clone()
         with torch.no_grad():
@@ -72,6 +95,9 @@ class GraphedForward:
             eng = self.model.__dict__.get(slot)
             if eng:
                 keep.append(eng._blocks)
+        hook = getattr(self.model, '_tamgcn_keep_alive', None)   # a wrapped object with folded tensors of its own (StreamEnsemble)
+        if hook is not None:
+            keep.append(hook())
         return g, static_in, out, keep
 
     def __call__(self, x):
@@ -87,3 +113,151 @@ class GraphedForward:
         static_in.copy_(x)
         g.replay()
         return out
+
+
+def default_parent(graph):
+    """0-based bone parent of every joint from a graph's 1-based parent table (tam_gcn_amd.graph.*: 0 marks the root); the
+    root is its own parent, so its bone is 0."""
+    return [v if p == 0 else p - 1 for v, p in enumerate(graph.parents)]
+
+
+class StreamEnsemble(nn.Module):
+    """The fused class scores of G models, model g fed stream `streams[g]` of the JOINT clips x.
+
+    streams   names of ops.STREAM_MODES ('joint', 'bone', 'motion' = 'joint_motion', 'bone_motion'), one per model
+    weights   G floats (default ones), kept in a device tensor: fused = sum_g weights[g] * scores_g (softmax=True: of the
+              softmax-normalised scores), ensemble.fuse's arithmetic
+    parent    int32 [V] tensor or sequence: 0-based bone parent of every joint.  Default: from the models' graph.parents with
+              the root as its own parent.  The reference N-UCLA feeder's bone table is feeder.feeder_nucla_gcn.BONE_PARENT;
+              passing it reproduces that feeder's bone stream.
+
+    x is (N, C, T, V, M) or (N, T, V*C), float32 on the GPU, under torch.no_grad().  forward(x) -> fused (N, K);
+    predict(x) -> (fused, pred int64 (N), scores (G, N, K)).
+
+    Small inputs (G*N*M <= f2.F2_MAX_CLIPS at V = 20, G*N*M*T <= f2v.F2V_MAX_FRAMES at V = 25; TAMGCN_F2 != 0; no forward
+    hooks on any sub-module) run as ONE grouped launch sequence (f2.GroupedEval: 54 launches whatever G is).  Anything else
+    runs each model's own forward on its derived stream (ops.stream_derive) and fuses the scores: the same result to
+    rounding, at any size.
+
+    arrangement (None: by measurement, profiles/stream_ensemble_bench.txt) | 'grouped' | 'streams' | 'serial'.  Launched from
+    Python the grouped sequence is the fastest (54 launches against 216).  Inside a HIP-graph capture (GraphedForward(ens)) the
+    launches cost nothing; there the grouped sequence does NOT beat what was possible before it: with one clip-person per
+    model (N-UCLA batch 1) it ties with the G models' own forwards on G streams (functional.model_stream) inside that
+    arrangement's own spread, only steadier, and beyond (N-UCLA batch 4; NTU batch 1, two persons) the G streams are 7-11 %
+    faster: kernels of different models fill each other's tails, which one grouped launch per stage cannot.  So None takes
+    'streams' for a call made by GraphedForward (its warm-up calls and its capture alike) with N*M > 1, and 'grouped'
+    otherwise.  A capture made by hand (torch.cuda.graph around ens(x)) gets no such switch: pass arrangement= there.  The
+    routes agree bit for bit where the grouped one applies."""
+
+    def __init__(self, models, streams=('joint', 'bone', 'motion', 'bone_motion'), weights=None, softmax=False, parent=None,
+                 arrangement=None):
+        super().__init__()
+        from . import f2
+        models, streams = list(models), list(streams)
+        if len(streams) != len(models):
+            raise ValueError(f'StreamEnsemble: {len(models)} models but {len(streams)} streams')
+        for s in streams:
+            if s not in ops.STREAM_MODES:
+                raise ValueError(f'StreamEnsemble: unknown stream {s!r} (one of {sorted(ops.STREAM_MODES)})')
+        if arrangement not in (None, 'grouped', 'streams', 'serial'):
+            raise ValueError(f'StreamEnsemble: arrangement {arrangement!r} (None, "grouped", "streams" or "serial")')
+        self.arrangement = arrangement
+        self._side = None                                      # G HIP streams, made by the first call that takes 'streams'
+        self._tamgcn_graphed = False                           # set by GraphedForward around its warm-up and capture
+        weights = [1.0] * len(models) if weights is None else [float(w) for w in weights]
+        if len(weights) != len(models):
+            raise ValueError(f'StreamEnsemble: {len(models)} models but {len(weights)} weights')
+        try:
+            self._eng = f2.GroupedEval(models)                 # ValueError: train mode, devices, differing geometry
+        except f2.Unsupported:
+            self._eng = None                                   # outside both families: every call takes the per-model route
+            if any(m.training for m in models):
+                raise ValueError('StreamEnsemble: put every model in eval() mode first')
+        V = models[0].num_point
+        if parent is None:
+            parent = default_parent(models[0].graph)
+        parent = [int(p) for p in (parent.tolist() if torch.is_tensor(parent) else parent)]
+        if len(parent) != V or any(p < 0 or p >= V for p in parent):
+            raise ValueError(f'StreamEnsemble: parent must hold {V} joint indices in [0, {V})')
+        dev = next(models[0].parameters()).device
+        self.models = nn.ModuleList(models)
+        self.streams, self.softmax = streams, bool(softmax)
+        self.register_buffer('weights', torch.tensor(weights, dtype=torch.float32, device=dev), persistent=False)
+        self.register_buffer('parent', torch.tensor(parent, dtype=torch.int32, device=dev), persistent=False)
+        self.register_buffer('modes', torch.tensor([ops.STREAM_MODES[s] for s in streams], dtype=torch.int32, device=dev), persistent=False)
+        self.train(False)
+
+    def _tamgcn_keep_alive(self):
+        keep = [] if self._eng is None else self._eng.keep_alive()
+        for m in self.models:
+            for slot in ('_tamgcn_f2', '_tamgcn_f2v'):
+                eng = m.__dict__.get(slot)
+                if eng:
+                    keep.append(eng._blocks)
+        return keep
+
+    def _grouped(self, x5):
+        """(the grouped engine, its stacked folded tensors) if this call is one for it, else (None, None)."""
+        from . import f2, f2v
+        eng = self._eng
+        none = (None, None)
+        if eng is None or not f2.enabled():
+            return none
+        G, (N, _, T, V, M) = len(self.models), x5.shape
+        if V != eng.V or M != eng.M:
+            return none
+        if (G * N * M > f2.F2_MAX_CLIPS) if V == 20 else (G * N * M * T > f2v.F2V_MAX_FRAMES):
+            return none
+        for mod in self.modules():
+            if mod._forward_hooks or mod._forward_pre_hooks:
+                return none
+        try:
+            return eng, eng._packed(x5.device)                 # folding and geometry checks, before anything is launched:
+        except f2.Unsupported:                                 # the one walk over the models' state keys of this call
+            self._eng = None
+            return none
+
+    def predict(self, x):
+        if torch.is_grad_enabled():
+            raise RuntimeError('StreamEnsemble is an inference path: call it under torch.no_grad()')
+        if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32:
+            raise RuntimeError('StreamEnsemble: expected a float32 HIP (cuda) tensor; there is no CPU path')
+        if any(m.training for m in self.models):
+            raise RuntimeError('StreamEnsemble: a model went back to train() mode')
+        V = self.models[0].num_point
+        if x.dim() == 3:
+            N, T, VC = x.shape
+            x = x.view(N, T, V, -1).permute(0, 3, 1, 2).unsqueeze(-1)
+        if x.dim() != 5 or x.shape[3] != V:
+            raise RuntimeError(f'StreamEnsemble: expected (N, C, T, {V}, M) or (N, T, {V}*C), got {tuple(x.shape)}')
+        x = x.contiguous()
+        arr = self.arrangement or ('streams' if self._tamgcn_graphed and x.shape[0] * x.shape[4] > 1 else 'grouped')
+        eng, stacked = self._grouped(x) if arr == 'grouped' else (None, None)
+        if eng is not None:
+            scores = eng.run(x, self.parent, self.modes, stacked)
+        elif arr == 'streams':
+            scores = self._on_streams(x)
+        else:
+            scores = torch.stack([m(ops.stream_derive(x, self.parent, s)) for m, s in zip(self.models, self.streams)])
+        fused, pred, _ = ops.score_fuse(scores, self.weights, self.softmax)
+        return fused, pred, scores
+
+    def _on_streams(self, x):
+        """Each model's own forward on its derived stream, the G of them side by side on G HIP streams."""
+        from . import functional as Fn
+        if self._side is None:                                 # (GraphedForward's warm-up calls come here before its capture)
+            self._side = [torch.cuda.Stream(device=x.device) for _ in self.models]
+        cur = torch.cuda.current_stream(x.device)
+        ys = []
+        for st, m, s in zip(self._side, self.models, self.streams):
+            st.wait_stream(cur)
+            with Fn.model_stream(st):
+                y = m(ops.stream_derive(x, self.parent, s))
+            y.record_stream(cur)
+            ys.append(y)
+        for st in self._side:
+            cur.wait_stream(st)
+        return torch.stack(ys)
+
+    def forward(self, x):
+        return self.predict(x)[0]

@@ -774,6 +774,15 @@ def head_fc_fwd(pooled, W, b):
     return logits
 
 
+def head_fc_grouped(pooled, W, b, G):
+    """pooled (G*N, C), W (G, K, C), b (G, K) -> scores (G, N, K): G heads in one launch (score_fuse's layout)."""
+    GN, C_ = pooled.shape
+    K = W.shape[1]
+    scores = empty(G, GN // G, K, like=pooled)
+    _lib.check(_lib_().tamgcn_head_fc_grouped(_ptr(pooled), _ptr(W), _ptr(b), G, GN // G, C_, K, _ptr(scores), _stream()), 'tamgcn_head_fc_grouped')
+    return scores
+
+
 def head_fc_bwd(dlogits, pooled, W):
     N, C_ = pooled.shape
     K = W.shape[0]
@@ -796,6 +805,19 @@ def stream_derive(x5, parent, mode):
         return x5
     out = torch.empty_like(x5)
     _lib.check(_lib_().tamgcn_stream_derive(_ptr(x5), N, C_, T, V, M, _ptr(parent), m, _ptr(out), _stream()), 'tamgcn_stream_derive')
+    return out
+
+
+def stem_streams_eval(x5, parent, modes, coef):
+    """x5 (N, C, T, V, M) joint clips, parent int32 [V], modes int32 [G] (STREAM_MODES values), coef (G, 3, C*V*M) eval-mode
+    data_bn coefficients per model -> (G*N*M, C, T, V): stream_derive + stem_apply of every group in one launch."""
+    N, C_, T, V, M = x5.shape
+    G = modes.numel()
+    if tuple(coef.shape) != (G, 3, C_ * V * M) or parent.numel() != V or parent.dtype != torch.int32 or modes.dtype != torch.int32:
+        raise RuntimeError(f'tam_gcn_amd: stem_streams_eval: coef {tuple(coef.shape)} / parent / modes do not fit x {tuple(x5.shape)}, G = {G}')
+    out = empty(G * N * M, C_, T, V, like=x5)
+    _lib.check(_lib_().tamgcn_stem_streams_eval(_ptr(x5), _ptr(parent), _ptr(modes), _ptr(coef), G, N, C_, T, V, M, _ptr(out), _stream()),
+               'tamgcn_stem_streams_eval')
     return out
 
 

@@ -5,7 +5,14 @@ the inference-only callers (cross-modal attention, ensemble eval, visualisation)
 Batches of at most TAMGCN_F2_MAX_CLIPS clips (ucla) / TAMGCN_F2V_MAX_FRAMES clip-persons x frames (ntu) take the small-batch
 kernel family (tam_gcn_amd/f2.py, f2v.py); TAMGCN_F2=0 puts them on the general eval path for comparison.
 --ab R: the family against the general path of the same process, alternating, R timings each (median [min .. max]); the
-family is forced on whatever the routing bound says (that bound is what this mode is for)."""
+family is forced on whatever the routing bound says (that bound is what this mode is for).
+--ensemble G [--ab R]: a G-stream ensemble (joint, bone, motion, bone-motion, ... models of one architecture, fused scores) for
+one joint batch, every arrangement under HIP-graph replay, alternating within this process, R timings each (default 7):
+    (a) serial    stream_derive x (G - 1), the G models' own forwards one after another, score_fuse -- one graph
+    (b) streams   the same with the G models on G streams inside the graph (functional.model_stream)
+    (c) grouped   inference.StreamEnsemble(arrangement='grouped'): one grouped launch sequence
+then GraphedForward(StreamEnsemble(...)) with its default arrangement, and (a) and (c) launched from Python (eager): both
+carry the host cost of G parameter-state keys per call."""
 import os, statistics, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -13,7 +20,7 @@ from tam_gcn_amd.models.ctrgcn import Model
 dev = torch.device('cuda:0')
 torch.manual_seed(0)
 args = sys.argv[1:]
-T, graph, ab = 64, 'ucla', 0
+T, graph, ab, ens_g = 64, 'ucla', 0, 0
 while args and args[0].startswith('--'):
     if args[0] == '--t':
         T = int(args[1])
@@ -21,6 +28,8 @@ while args and args[0].startswith('--'):
         graph = args[1]
     elif args[0] == '--ab':
         ab = int(args[1])
+    elif args[0] == '--ensemble':
+        ens_g = int(args[1])
     else:
         sys.exit(__doc__)
     args = args[2:]
@@ -59,6 +68,85 @@ def capture(x):
     return g, y
 
 
+def ensemble_bench(G, batches, R):
+    import copy
+    from tam_gcn_amd import ops, functional as Fn
+    from tam_gcn_amd.inference import GraphedForward, StreamEnsemble
+    names = ['joint', 'bone', 'motion', 'bone_motion']
+    streams = [names[g % 4] for g in range(G)]
+    models = [m]
+    gen = torch.Generator().manual_seed(1)
+    for g in range(1, G):                                  # the same architecture, every parameter its own
+        mg = copy.deepcopy(m)
+        with torch.no_grad():
+            for p in mg.parameters():
+                p.mul_((1 + 0.02 * (2 * torch.rand(p.shape, generator=gen) - 1)).to(dev))
+        models.append(mg.eval())
+    ens = StreamEnsemble(models, streams, arrangement='grouped')
+    auto = StreamEnsemble(models, streams)
+    side = [torch.cuda.Stream(device=dev) for _ in range(G)]
+
+    def serial(x):
+        ys = [mg(ops.stream_derive(x, ens.parent, s)) for mg, s in zip(models, streams)]
+        return ops.score_fuse(torch.stack(ys), ens.weights, False)[0]
+
+    def on_streams(x):
+        cur = torch.cuda.current_stream(dev)
+        ys = []
+        for st, mg, s in zip(side, models, streams):
+            st.wait_stream(cur)
+            with Fn.model_stream(st):
+                ys.append(mg(ops.stream_derive(x, ens.parent, s)))
+        for st in side:
+            cur.wait_stream(st)
+        return ops.score_fuse(torch.stack(ys), ens.weights, False)[0]
+
+    def graphed(fn, x):
+        s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                fn(x)
+        torch.cuda.current_stream().wait_stream(s); torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            y = fn(x)
+        g.replay(); torch.cuda.synchronize()
+        return g, y
+
+    print(f'ensemble of {G} ({", ".join(streams)}), graph = {graph} (V = {V}, M = {P}), T = {T}; {R} alternating timings of {n} calls: '
+          'median [min .. max]', flush=True)
+    for B in batches:
+        x = torch.rand(B, 3, T, V, P, device=dev) * 2 - 1
+        with torch.no_grad():
+            gf = GraphedForward(auto)                       # what a user gets: the default arrangement under GraphedForward
+            ya = gf(x)
+            arr = {'(a) serial, graph ': graphed(serial, x), '(b) streams, graph': graphed(on_streams, x), '(c) grouped, graph': graphed(ens, x),
+                   'GraphedForward(StreamEnsemble), default arrangement': (next(iter(gf._graphs.values()))[0], ya)}
+            ref = arr['(a) serial, graph '][1]
+            for k, (g, y) in arr.items():
+                d = float((y - ref).abs().max()) / float(ref.abs().max())
+                assert d <= 1e-4, (k, d)
+            times = {k: [] for k in list(arr) + ['(a) serial, eager ', '(c) grouped, eager', 'StreamEnsemble default, eager']}
+            for _ in range(R):
+                for k, (g, _) in arr.items():
+                    times[k].append(timed(g.replay))
+                times['(a) serial, eager '].append(timed(lambda: serial(x)))
+                times['(c) grouped, eager'].append(timed(lambda: ens(x)))
+                times['StreamEnsemble default, eager'].append(timed(lambda: auto(x)))
+        for k, v in times.items():
+            print(f'batch {B:3d} x {P} x {T}  {k}: {statistics.median(v) * 1e3:7.3f} ms [{min(v) * 1e3:7.3f} .. {max(v) * 1e3:7.3f}]', flush=True)
+        a, b, c = (times[k] for k in list(arr)[:3])
+        best, which = min((statistics.median(a), 'a'), (statistics.median(b), 'b'))
+        spread = max(max(a) - min(a), max(b) - min(b), max(c) - min(c))
+        gain = best - statistics.median(c)
+        print(f'      (c) against the better of (a), (b) = ({which}): {statistics.median(c) / best:5.2f}x of its time, '
+              f'{gain * 1e3:+.3f} ms; largest [min .. max] spread of the three {spread * 1e3:.3f} ms: (c) '
+              + ('WINS by more than the spread' if gain > spread else 'does NOT win (not below the better one by more than the spread)'), flush=True)
+
+
+if ens_g:
+    ensemble_bench(ens_g, [int(v) for v in args] or (1, 4), ab or 7)
+    sys.exit(0)
 print(f'graph = {graph} (V = {V}, M = {P}), T = {T}, TAMGCN_F2 = {os.environ.get("TAMGCN_F2", "1")}', flush=True)
 for B in ([int(v) for v in args] or (1, 16, 256)):
     x = torch.rand(B, 3, T, V, P, device=dev) * 2 - 1
