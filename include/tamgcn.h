@@ -345,7 +345,7 @@ int tamgcn_maxpool_fwd(const tamgcn_src* src, int N, int C, int T_in, int V, int
 int tamgcn_maxpool_post_fwd(const tamgcn_src* src, int N, int C, int T_in, int V, int stride,
                             float* y, int yctot, int ycoff, int T_out, const float* coef, const float* add, int relu, void* stream);
 /* d src_value routed to the first arg-max of each window, times relu mask (value > 0);
- * gy goes through its own prologue; result written at channel dcoff of d (N, dctot, T_in, V),
+ * gy goes through its own prologue (gy->act != 0 is honoured, on the staged kernel); result written at channel dcoff of d (N, dctot, T_in, V),
  * partials (sum d, sum d*src.x1) at the same channel of [2][dctot][nparts]. */
 int tamgcn_maxpool_bwd(const tamgcn_src* gy, const tamgcn_src* src, const float* src_save, int N, int C, int T_in, int T_out, int V,
                        int stride, float* d, int dctot, int dcoff, float* part, void* stream);

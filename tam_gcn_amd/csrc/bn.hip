@@ -134,6 +134,8 @@ extern "C" int tamgcn_bn_fwd_finalize_multi(const tamgcn_bn_fwd_desc* descs, int
             TG_CHECK(!d.training || (d.part && d.nparts > 0 && d.count > 0), "tamgcn_bn_fwd_finalize_multi: descriptor %d: training needs partial sums", i0 + i);
             TG_CHECK(d.training || (d.running_mean && d.running_var), "tamgcn_bn_fwd_finalize_multi: descriptor %d: eval needs running stats", i0 + i);
             TG_CHECK(d.coef_coff + d.C <= d.coef_ctot, "tamgcn_bn_fwd_finalize_multi: descriptor %d: coef slice out of range", i0 + i);
+            TG_CHECK(!d.training || (d.part_coff >= 0 && d.part_coff + d.C <= d.part_ctot),
+                     "tamgcn_bn_fwd_finalize_multi: descriptor %d: partial-sum slice out of range", i0 + i);
             m.d[i] = d;
             if (d.C > maxc) maxc = d.C;
         }
@@ -174,6 +176,7 @@ extern "C" int tamgcn_bn_fwd_finalize(const float* part, int part_ctot, int part
     TG_CHECK(!training || (part && nparts > 0 && count > 0), "tamgcn_bn_fwd_finalize: training needs partial sums");
     TG_CHECK(training || (running_mean && running_var), "tamgcn_bn_fwd_finalize: eval needs running stats");
     TG_CHECK(coef_coff + C <= coef_ctot, "tamgcn_bn_fwd_finalize: coef slice out of range");
+    TG_CHECK(!training || (part_coff >= 0 && part_coff + C <= part_ctot), "tamgcn_bn_fwd_finalize: partial-sum slice out of range");
     hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream,
                        part, part_ctot, part_coff, nparts, count, gamma, beta, running_mean, running_var,
                        num_batches_tracked, momentum, eps, training, coef, save, coef_ctot, coef_coff);

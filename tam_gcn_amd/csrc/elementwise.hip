@@ -693,7 +693,10 @@ extern "C" int tamgcn_maxpool_bwd(const tamgcn_src* gy, const tamgcn_src* src, c
     const bool al16 = ((((uintptr_t)gy->x1 | (uintptr_t)(gy->x2 ? gy->x2 : gy->x1) | (uintptr_t)src->x1 | (uintptr_t)d) & 15) == 0);
     static int vec_env = -1;
     if (vec_env < 0) { const char* e = getenv("TAMGCN_POOL_VEC"); vec_env = e ? atoi(e) : 1; }     // 0: the staged kernel (A/B)
-    if (vec_env && (V & 3) == 0 && (stride == 1 || stride == 2) && al16 && !src->x2 && T_out == (T_in - 1) / stride + 1) {
+    // the vector and flat kernels apply gy's coefficients only: a gy with an activation (no caller in the models) takes the staged kernel,
+    // whose src_value() applies it, so that the result does not depend on V % 4, alignment or stride
+    const bool gy_lin = gy->act == 0;
+    if (vec_env && gy_lin && (V & 3) == 0 && (stride == 1 || stride == 2) && al16 && !src->x2 && T_out == (T_in - 1) / stride + 1) {
         if (stride == 1)
             hipLaunchKernelGGL(maxpool_bwd_vec_kernel<1>, row_grid(geo), dim3(EW_THREADS), 0, (hipStream_t)stream,
                                geo, make_src(*gy), make_src(*src), src_save, C, T_in, T_out, V, d, dctot, dcoff, N, part);
@@ -704,7 +707,7 @@ extern "C" int tamgcn_maxpool_bwd(const tamgcn_src* gy, const tamgcn_src* src, c
         TG_LAUNCH_CHECK("tamgcn_maxpool_bwd");
         return 0;
     }
-    if (vec_env && stride == 1 && !src->x2 && T_out == T_in && (long long)T_in * V < (1LL << 30)) {
+    if (vec_env && gy_lin && stride == 1 && !src->x2 && T_out == T_in && (long long)T_in * V < (1LL << 30)) {
         hipLaunchKernelGGL(maxpool_bwd_flat_kernel, row_grid(geo), dim3(EW_THREADS), 0, (hipStream_t)stream,
                            geo, make_src(*gy), make_src(*src), src_save, C, T_in, V, d, dctot, dcoff, N, part);
         tamgcn_note_kernel("maxpool_bwd_flat_kernel");
@@ -717,7 +720,7 @@ extern "C" int tamgcn_maxpool_bwd(const tamgcn_src* gy, const tamgcn_src* src, c
     else
         hipLaunchKernelGGL(maxpool_bwd_kernel<0>, row_grid(geo), dim3(EW_THREADS), 0, (hipStream_t)stream,
                            geo, make_src(*gy), make_src(*src), src_save, C, T_in, T_out, V, stride, d, dctot, dcoff, N, part);
-    tamgcn_note_kernel("maxpool_bwd_kernel");
+    tamgcn_note_kernel("maxpool_bwd_kernel<%d>", lds <= 64 * 1024 ? 1 : 0);
     TG_LAUNCH_CHECK("tamgcn_maxpool_bwd");
     return 0;
 }

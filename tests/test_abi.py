@@ -75,3 +75,25 @@ def test_abi_rejects_bad_arguments_without_touching_the_gpu():
     one = C.c_float(0.0)
     d.src.x1 = C.addressof(one); d.w = C.addressof(one); d.y = C.addressof(one)
     assert lib.tamgcn_conv(C.byref(d), None) < 0 and b'bad dims' in lib.tamgcn_last_error()
+
+
+def test_bn_fwd_finalize_rejects_a_partial_sum_slice_out_of_range():
+    """Training reads part[s][part_coff + c][i]: a slice that does not fit in part_ctot channels is refused on the host, by the
+    single and the multi form, as the backward forms already do; eval reads no partial sums and takes any."""
+    import ctypes as C
+    from tam_gcn_amd import build, _lib
+    build.build()
+    lib = _lib.load()
+    one = (C.c_float * 64)()
+    p = C.addressof(one)
+    for part_coff, part_ctot in ((3, 4), (-1, 4)):
+        rc = lib.tamgcn_bn_fwd_finalize(p, part_ctot, part_coff, 1, 1.0, None, None, None, None, None, 0.1, 1e-5, 1, p, p, 8, 0, 2, None)
+        assert rc < 0 and b'tamgcn_bn_fwd_finalize: partial-sum slice out of range' in lib.tamgcn_last_error(), lib.tamgcn_last_error()
+        d = _lib.BnFwdDesc()
+        d.part, d.part_ctot, d.part_coff, d.nparts, d.count, d.training = p, part_ctot, part_coff, 1, 1.0, 1
+        d.coef, d.save, d.coef_ctot, d.coef_coff, d.C = p, p, 8, 0, 2
+        rc = lib.tamgcn_bn_fwd_finalize_multi(C.byref(d), 1, None)
+        assert rc < 0 and b'tamgcn_bn_fwd_finalize_multi: descriptor 0: partial-sum slice out of range' in lib.tamgcn_last_error()
+    # the coef check still comes first and keeps its text
+    rc = lib.tamgcn_bn_fwd_finalize(p, 4, 0, 1, 1.0, None, None, None, None, None, 0.1, 1e-5, 1, p, p, 1, 0, 2, None)
+    assert rc < 0 and b'coef slice out of range' in lib.tamgcn_last_error()

@@ -190,6 +190,7 @@ def test_conv_prologue_slices_mask_aux():
 
 
 def test_bn_finalize_fwd_bwd():
+    import ew_ref as R
     from tam_gcn_amd import ops
     from tam_gcn_amd.ops import S
     N, C_, T, V = 3, 24, 7, 20
@@ -213,12 +214,22 @@ def test_bn_finalize_fwd_bwd():
     close(yg, y, 1e-4, 1e-5)
     close(rmd, rm, 1e-5, 1e-6); close(rvd, rv, 1e-5, 1e-6)
     assert int(nbt) == 1
+    # the finaliser against its fp64 evaluation on the partial sums it was given, to fp32 rounding (tests/ew_ref.py)
+    fd = dict(C=C_, part=part.cpu(), count=N * T * V, training=1, gamma=g.detach(), beta=b.detach(), running_mean=rm0, running_var=rv0,
+              momentum=0.1, eps=1e-5)
+    cf, sv = coef.cpu(), save.cpu()
+    R.bn_check('bn_fwd_finalize', dict(c1=cf[0], c2=cf[1], c0=cf[2], mean=sv[0], invstd=sv[1], running_mean=rmd.cpu(), running_var=rvd.cpu()),
+               R.bn_fwd(fd))
     cd = cot.to(d)
     _, bpart = ops.add_act_bwd(cd, None, 0, xd, save, None, None, want_dz=False)
+    R.verify('add_act_bwd', 'add_act_bwd', dict(dout=cot, relu=0, a_pre=x.detach(), a_save=sv, want_dz=0), dict(s0=bpart[0].cpu(), s1=bpart[1].cpu()))
     coefb = torch.empty(3, C_, device=d)
     dg = torch.empty(C_, device=d); db = torch.empty(C_, device=d); dbias = torch.empty(C_, device=d)
     ops.bn_bwd_finalize(bpart, 0, N * T * V, g.detach().to(d), save, 0, True, dg, db, dbias, coefb, 0, C_)
     close(dg, g.grad, 1e-4, 1e-4); close(db, b.grad, 1e-4, 1e-4)
+    cb = coefb.cpu()
+    R.bn_check('bn_bwd_finalize', dict(c1=cb[0], c2=cb[1], c0=cb[2], dgamma=dg.cpu(), dbeta=db.cpu(), dbias_conv=dbias.cpu()),
+               R.bn_bwd(dict(C=C_, part=bpart.cpu(), count=N * T * V, training=1, gamma=g.detach(), save=sv)))
     dx = ops.apply(S(cd, xd, coefb), C_)
     close(dx, x.grad, 1e-3, 1e-5)
     assert float(dbias.abs().max()) < 1e-3
@@ -307,6 +318,7 @@ def test_ctrgc_fused_fwd_bwd(shape):
 
 
 def test_elementwise_kernels():
+    import ew_ref as R
     from tam_gcn_amd import ops
     from tam_gcn_amd.ops import S
     N, C_, T, V = 2, 20, 13, 20
@@ -323,8 +335,9 @@ def test_elementwise_kernels():
     e_dsum = dg * (g > 0)
     e_doz = e_dsum * (1 - torch.tanh(ap(co, o)) ** 2)
     close(dsum, e_dsum, 1e-5, 1e-5); close(doz, e_doz, 1e-4, 1e-5)
-    close(part[0].sum(-1), e_doz.sum((0, 2, 3)), 1e-3, 1e-3)
-    close(part[1].sum(-1), (e_doz * (o - osave[0].cpu()[None, :, None, None])).sum((0, 2, 3)), 1e-3, 1e-3)
+    # every output against fp64, the moments slot by slot (tests/ew_ref.py; tests/test_gpu_ew_forms.py walks the kernel forms)
+    R.verify('gcn_tail_bwd', 'gcn_tail_bwd', dict(C=C_, dg=dg, g=gg.cpu(), o=dict(x1=o, coef=co), o_save=osave.cpu()),
+             dict(dsum=dsum.cpu(), doz=doz.cpu(), s0=part[0].cpu(), s1=part[1].cpu()))
     # max-pool fwd/bwd, stride 1 and 2, vs autograd
     for s in (1, 2):
         h = rnd((N, C_, T, V), 7).requires_grad_(True)
@@ -341,12 +354,15 @@ def test_elementwise_kernels():
         src = S(h.detach().to(d), coef=ch.to(d), act=1)
         part = ops.maxpool_fwd(src, C_, s, yb, 4, stats=True)
         close(yb[:, 4:], mp, 1e-5, 1e-6)
-        close(part[0, 4:].sum(-1), mp.sum((0, 2, 3)), 1e-3, 1e-3)
+        hs = dict(x1=h.detach(), coef=ch, act=1)
+        R.verify(f'maxpool_fwd s={s}', 'maxpool_fwd', dict(C=C_, src=hs, stride=s, stats=1),
+                 dict(y=yb[:, 4:].cpu(), s0=part[0, 4:].cpu(), s1=part[1, 4:].cpu()))
         dd = torch.zeros(N, C_ + 2, T, V, device=d)
         hsave = rnd((2, C_), 12).to(d)
         bp = ops.maxpool_bwd(S(cot.to(d)), src, hsave, C_, s, dd, 2)
         close(dd[:, 2:], hb.grad, 1e-5, 1e-6, f'maxpool bwd s={s}')
-        close(bp[1, 2:].sum(-1), (hb.grad * (h.detach() - hsave[0].cpu()[None, :, None, None])).sum((0, 2, 3)), 1e-3, 1e-3)
+        R.verify(f'maxpool_bwd s={s}', 'maxpool_bwd', dict(C=C_, src=hs, gy=dict(x1=cot), stride=s, src_save=hsave.cpu()),
+                 dict(d=dd[:, 2:].cpu(), s0=bp[0, 2:].cpu(), s1=bp[1, 2:].cpu()))
 
 
 @pytest.mark.parametrize('mode,bar', [('0', 2e-6), ('1', 3e-5)])
