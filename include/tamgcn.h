@@ -405,6 +405,37 @@ int tamgcn_ce_bwd(const float* g, const float* dloss, int N, int K, float* dlogi
 int tamgcn_score_fuse(const float* scores, const float* weights, int S, int N, int K, int softmax,
                       const long long* labels, float* fused, long long* pred, int* class_stats, void* stream);
 
+/* ---- the evaluation epoch's bookkeeping on the device (reference processor/recognition_rgb.py:71-101; the per-class accuracy,
+ *      confusion matrix and alpha sweep of ensemble/ensemble_ctrgcn_resnet_eval.py:217-234, :267, :421-438) ----
+ * _eval_accumulate  adds ONE batch to a state the caller owns in device memory and zeroes before the first batch; one launch of
+ *          one workgroup on `stream`, no synchronisation, capturable.  logits (B, K) fp32, labels (B) int64, index (B) int64 | NULL.
+ *          Only the first `valid` rows count: valid_dev (int32 on the device, read by the kernel, so a graph replay can change
+ *          it) if not NULL, else the host value; clamped to [0, B].  Rows n >= valid are neither read nor stored.
+ *            counts int64 [4 + TAMGCN_EVAL_MAX_TOPK]  [0] batches with a kept row, [1] kept rows, [2] bad labels, [3] bad indices,
+ *                                   [4 + i] rows that hit top-topk[i]
+ *            sums fp64 [2]          [0] sum of the batch-mean losses, [1] sum of the per-row losses
+ *            confusion int32 (K, K) row = label, column = prediction
+ *            scores fp32 (num_samples, K) | NULL   row index[n] (index NULL: row base + n) = logits[n] for every n < valid; a
+ *                                   row outside [0, num_samples) stores nothing and is counted in counts[3]
+ *          A row is KEPT when its label is in [0, K).  Label -100 is skipped silently; any other label outside [0, K) is
+ *          counted in counts[2] and makes this batch's mean loss NaN -- tamgcn_ce_fwd's conventions, and its arithmetic: the
+ *          batch mean is the value tamgcn_ce_fwd returns for rows [0, valid), bit for bit (one device body, one summation
+ *          order).  A batch without a kept row adds nothing to counts[0], counts[1] and sums.
+ *          Prediction = first arg max (numpy.argmax).  Row n hits top-k iff #{j : s_j > s_l} + #{j > l : s_j == s_l} < k, l its
+ *          label: `l in argsort(s, stable)[-k:]`, the feeder's top_k with ties in stable order; k >= K always hits.
+ *          topk: nk <= TAMGCN_EVAL_MAX_TOPK host ints.  Integer state is updated with integer atomics, floating-point state
+ *          by one thread; nothing outside the state is written for any label or index value.
+ * _score_sweep  correct[i] (int32 [A], device) = #{n : first arg max_k (a[n][k] + alphas[i] * b[n][k]) == labels[n]} for A <=
+ *          TAMGCN_SWEEP_MAX_ALPHAS host floats in one launch: tamgcn_score_fuse's arithmetic on the score sets (a, b) with
+ *          weights (1, alphas[i]), softmax as there.  a, b (N, K) fp32, labels (N) int64; a label outside [0, K) is never correct. */
+#define TAMGCN_EVAL_MAX_TOPK 4
+#define TAMGCN_SWEEP_MAX_ALPHAS 16
+int tamgcn_eval_accumulate(const float* logits, const long long* labels, const long long* index, int B, int K,
+                           int valid, const int* valid_dev, const int* topk, int nk, long long base, long long num_samples,
+                           long long* counts, double* sums, int* confusion, float* scores, void* stream);
+int tamgcn_score_sweep(const float* a, const float* b, const float* alphas, int A, int N, int K, int softmax,
+                       const long long* labels, int* correct, void* stream);
+
 /* ---- input side: skeleton streams and the feeder's per-sample transform ----------------------
  * _stream_derive  the other three inputs of the 4-stream recipe from a joint batch x (N, C, T, V, M) resident in HBM:
  *                 mode 1 bone        out[.., v, m] = x[.., v, m] - x[.., parent[v], m]   (reference feeder/feeder_nucla_gcn.py:27-28,

@@ -169,6 +169,8 @@ SIGNATURES = {
     'tamgcn_score_fuse': (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     'tamgcn_ce_fwd': (_i, [_p, _p, _i, _i, _p, _p, _p]),
     'tamgcn_ce_bwd': (_i, [_p, _p, _i, _i, _p, _p]),
+    'tamgcn_eval_accumulate': (_i, [_p, _p, _p, _i, _i, _i, _p, C.POINTER(C.c_int), _i, _ll, _ll, _p, _p, _p, _p, _p]),
+    'tamgcn_score_sweep': (_i, [_p, _p, C.POINTER(C.c_float), _i, _i, _i, _i, _p, _p, _p]),
     'tamgcn_stream_derive': (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _p]),
     'tamgcn_feeder_transform': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     'tamgcn_feeder_draw': (_i, [_p, _ll, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),

@@ -6,6 +6,7 @@
 //   stem   x (N, C, T, V, M) --data_bn over j = (m*V + v)*C + c, statistics over (n, t)--> (N*M, C, T, V)
 //   head   x10 (N*M, C, T, V) --mean over (m, t, v)--> pooled (N, C) --fc--> logits (N, K)
 #include "common.h"
+#include "evalbody.h"
 
 namespace {
 
@@ -180,26 +181,14 @@ __global__ __launch_bounds__(SH_NT) void fc_bwd_kernel(const float* dl, const fl
 // skipped (zero gradient, not counted: the mean is over the kept rows, NaN when none is kept, as torch gives).  Any
 // other label outside [0, K) -- torch raises a device assert there -- makes the loss NaN and zeroes that row's gradient;
 // no memory outside the row is touched.  Terms are summed in fp64 in a fixed order.
-constexpr long long CE_IGNORE_INDEX = -100;
+// The label count, the per-row log-sum-exp, the block sum and the mean are evalbody.h's: tamgcn_eval_accumulate shares them.
+static_assert(SH_NT == CE_NT, "ce_fwd_kernel runs evalbody.h's one-workgroup bodies");
 __global__ __launch_bounds__(SH_NT) void ce_fwd_kernel(const float* logits, const long long* labels, int N, int K, float* loss, float* g) {
     __shared__ double red[SH_NT];
     __shared__ int cnt[SH_NT];
     __shared__ int bad[SH_NT];
-    int kept = 0, nbad = 0;
-    for (int n = threadIdx.x; n < N; n += SH_NT) {
-        const long long y = labels[n];
-        if (y >= 0 && y < K) ++kept;
-        else if (y != CE_IGNORE_INDEX) ++nbad;
-    }
-    cnt[threadIdx.x] = kept;
-    bad[threadIdx.x] = nbad;
-    __syncthreads();
-    for (int o = SH_NT / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) { cnt[threadIdx.x] += cnt[threadIdx.x + o]; bad[threadIdx.x] += bad[threadIdx.x + o]; }
-        __syncthreads();
-    }
-    kept = cnt[0];
-    nbad = bad[0];
+    const CeCount c = ce_count_labels(labels, N, K, cnt, bad);
+    const int kept = c.kept, nbad = c.nbad;
     const float invk = kept > 0 ? 1.f / (float)kept : 0.f;
     double acc = 0.0;
     for (int n = threadIdx.x; n < N; n += SH_NT) {
@@ -209,22 +198,14 @@ __global__ __launch_bounds__(SH_NT) void ce_fwd_kernel(const float* logits, cons
             for (int k = 0; k < K; ++k) g[(long long)n * K + k] = 0.f;
             continue;
         }
-        float m = l[0];
-        for (int k = 1; k < K; ++k) m = fmaxf(m, l[k]);
-        float s = 0.f;
-        for (int k = 0; k < K; ++k) s += expf(l[k] - m);
-        const float lse = m + logf(s);
-        const float inv = 1.f / s;
+        const CeRow r = ce_row_lse(l, K);
+        const float m = r.m, lse = r.lse;
+        const float inv = 1.f / r.s;
         for (int k = 0; k < K; ++k) g[(long long)n * K + k] = (expf(l[k] - m) * inv - (k == y ? 1.f : 0.f)) * invk;
         acc += (double)(lse - l[y]);
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = SH_NT / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (nbad || kept == 0) ? __builtin_nanf("") : (float)(red[0] / (double)kept);
+    const double total = ce_block_sum(acc, red);
+    if (threadIdx.x == 0) loss[0] = ce_mean(total, kept, nbad);
 }
 
 __global__ __launch_bounds__(SH_NT) void ce_bwd_kernel(const float* g, const float* dloss, int total, float scale, float* dlogits) {
@@ -243,17 +224,10 @@ __global__ __launch_bounds__(SH_NT) void score_fuse_kernel(const float* scores, 
     for (int k = 0; k < K; ++k) f[k] = 0.f;
     for (int s = 0; s < S; ++s) {
         const float* x = scores + ((long long)s * N + n) * K;
-        float mx = 0.f, inv = 1.f;
-        if (softmax) {
-            mx = x[0];
-            for (int k = 1; k < K; ++k) mx = fmaxf(mx, x[k]);
-            float den = 0.f;
-            for (int k = 0; k < K; ++k) den += expf(x[k] - mx);
-            inv = 1.f / den;
-        }
+        float mx, inv;
+        fuse_softmax_stats(x, K, softmax, mx, inv);
         const float ws = w[s];
-        // separate multiply and add (no fma contraction): numpy evaluates score_a + (alpha * score_b) with both roundings
-        for (int k = 0; k < K; ++k) f[k] = __fadd_rn(f[k], __fmul_rn(ws, softmax ? expf(x[k] - mx) * inv : x[k]));
+        for (int k = 0; k < K; ++k) f[k] = fuse_add(f[k], ws, x, k, softmax, mx, inv);      // evalbody.h: two roundings, as numpy
     }
     int best = 0;
     for (int k = 1; k < K; ++k) if (f[k] > f[best]) best = k;

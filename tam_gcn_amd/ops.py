@@ -905,6 +905,69 @@ def score_fuse(scores, weights, softmax, labels=None):
     return fused, pred, stats
 
 
+EVAL_MAX_TOPK = 4             # include/tamgcn.h TAMGCN_EVAL_MAX_TOPK
+EVAL_COUNTS = 4 + EVAL_MAX_TOPK
+SWEEP_MAX_ALPHAS = 16         # TAMGCN_SWEEP_MAX_ALPHAS
+
+
+def eval_accumulate(logits, labels, counts, sums, confusion, topk, index=None, valid=None, scores=None, base=0):
+    """One batch into an evaluation state (tamgcn_eval_accumulate, include/tamgcn.h has the state's layout and the rules).
+    logits (B, K) fp32, labels (B) int64, index (B) int64 | None, valid int | 0-d / 1-element int32 tensor on the device |
+    None (= B), topk a sequence of <= EVAL_MAX_TOPK ints.  One launch on the current stream, no synchronisation."""
+    _want(logits, 'logits', torch.float32)
+    if logits.dim() != 2:
+        raise RuntimeError(f'tam_gcn_amd: eval_accumulate: logits must be (B, K), got {tuple(logits.shape)}')
+    B, K = logits.shape
+    _want(labels, 'labels', torch.int64, (B,))
+    if index is not None:
+        _want(index, 'index', torch.int64, (B,))
+    _want(counts, 'counts', torch.int64, (EVAL_COUNTS,))
+    _want(sums, 'sums', torch.float64, (2,))
+    _want(confusion, 'confusion', torch.int32, (K, K))
+    num_samples = 0
+    if scores is not None:
+        _want(scores, 'scores', torch.float32)
+        if scores.dim() != 2 or scores.shape[1] != K:
+            raise RuntimeError(f'tam_gcn_amd: eval_accumulate: scores must be (num_samples, {K}), got {tuple(scores.shape)}')
+        num_samples = scores.shape[0]
+    vdev, vhost = None, B
+    if isinstance(valid, torch.Tensor):
+        _want(valid, 'valid', torch.int32)
+        if valid.numel() != 1:
+            raise RuntimeError('tam_gcn_amd: eval_accumulate: valid must hold one int32')
+        vdev = valid
+    elif valid is not None:
+        vhost = int(valid)
+        if not 0 <= vhost <= B:
+            raise RuntimeError(f'tam_gcn_amd: eval_accumulate: valid = {vhost} outside [0, {B}]')
+    topk = [int(k) for k in topk]
+    if len(topk) > EVAL_MAX_TOPK:
+        raise RuntimeError(f'tam_gcn_amd: eval_accumulate: at most {EVAL_MAX_TOPK} top-k entries, got {len(topk)}')
+    tk = (C.c_int * max(1, len(topk)))(*topk)
+    _lib.check(_lib_().tamgcn_eval_accumulate(_ptr(logits), _ptr(labels), _ptr(index), B, K, vhost, _ptr(vdev), tk, len(topk), int(base),
+                                              num_samples, _ptr(counts), _ptr(sums), _ptr(confusion), _ptr(scores), _stream()),
+               'tamgcn_eval_accumulate')
+
+
+def score_sweep(a, b, alphas, labels, softmax):
+    """a, b (N, K) fp32, alphas <= SWEEP_MAX_ALPHAS floats, labels (N) int64 -> correct int32 [A] on the device:
+    correct[i] = #{n : first arg max of tamgcn_score_fuse's (a, b) fused with weights (1, alphas[i]) == labels[n]}."""
+    _want(a, 'a', torch.float32)
+    _want(b, 'b', torch.float32, tuple(a.shape))
+    if a.dim() != 2:
+        raise RuntimeError(f'tam_gcn_amd: score_sweep: scores must be (N, K), got {tuple(a.shape)}')
+    N, K = a.shape
+    _want(labels, 'labels', torch.int64, (N,))
+    alphas = [float(x) for x in alphas]
+    if not 1 <= len(alphas) <= SWEEP_MAX_ALPHAS:
+        raise RuntimeError(f'tam_gcn_amd: score_sweep: 1 .. {SWEEP_MAX_ALPHAS} alphas per launch, got {len(alphas)}')
+    correct = torch.empty(len(alphas), device=a.device, dtype=torch.int32)
+    al = (C.c_float * len(alphas))(*alphas)
+    _lib.check(_lib_().tamgcn_score_sweep(_ptr(a), _ptr(b), al, len(alphas), N, K, int(bool(softmax)), _ptr(labels), _ptr(correct), _stream()),
+               'tamgcn_score_sweep')
+    return correct
+
+
 def ce_bwd(g, dloss):
     N, K = g.shape
     dl = torch.empty_like(g)
