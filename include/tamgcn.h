@@ -68,7 +68,8 @@ int         tamgcn_set_split_mode(int mode);
 
 /* bytes of LDS the CTRGC kernels need for (S subsets, V joints, R rel-channels): the fused LDS-resident workgroup for
  * V = 20, the streaming family (tamgcn_ctrgc_tiled_*) for V in {25, 32, 64};
- * <0 if the shape is unsupported.  Lets the host fail early and loudly. */
+ * <0 if the shape is unsupported.  Lets the host fail early and loudly.  Every other 2 <= V <= 32 runs on the
+ * run-time-V family: tamgcn_vgen_supported / tamgcn_vgen_lds_bytes. */
 int         tamgcn_ctrgc_lds_bytes(int S, int V, int R);
 
 /* ------------------------------------------------------------------------
@@ -274,6 +275,28 @@ int tamgcn_ctrgc_tiled_agg_bwd(const tamgcn_ctrgc_desc* d, const tamgcn_src* dy,
 int tamgcn_ctrgc_tiled_de_acc(const tamgcn_ctrgc_desc* d, const tamgcn_src* dy, const float* x3, float* dE, void* stream);
 int tamgcn_ctrgc_tiled_de_tail(const tamgcn_ctrgc_desc* d, const float* dE, float* dA_part, float* dw4_part, float* db4_part,
                                float* dalpha_part, float* dpq, void* stream);
+
+/* ---- CTRGC for any skeleton of 2 <= V <= 32 joints (a user's own graph: COCO 17, OpenPose 18, hands 21, ...) --------
+ * The kernels of the V = 25 route with V as a run-time argument (csrc/vgen.hip): joints padded to 16 or 32 inside the
+ * kernels' LDS images, never in HBM.  Same arithmetic, tensors and partial layouts as the entry points they stand beside:
+ *   _vgen_build_e    as tamgcn_ctrgc_build_e          E (N, S, Cout, V, V), workgroup = (n, s)
+ *   _vgen_agg_fwd    as tamgcn_ctrgc_tiled_agg_fwd    x3 (N, S*Cout, T, V) from tamgcn_conv
+ *   _vgen_agg_bwd    as tamgcn_ctrgc_tiled_agg_bwd
+ *   _vgen_de_acc     as tamgcn_ctrgc_tiled_de_acc
+ *   _vgen_de_tail    as tamgcn_ctrgc_bwd_de_tail      (channel groups, dpq [groups][S*2*R][N][V])
+ * S in {1, 3}, Cout % 16 == 0, R a multiple of 4 up to 32.  V = 20, 25 and 32 are accepted too (the library's own
+ * routing keeps their dedicated kernels).  x3, E and dy are read in 16-byte pieces from dword-aligned rows: keep 12
+ * readable bytes behind each of them.
+ * tamgcn_vgen_supported: 1 for 2 <= V <= 32, else 0.  tamgcn_vgen_lds_bytes: the family's largest dynamic-LDS request
+ * for (S, V, R), < 0 outside its range. */
+int tamgcn_vgen_supported(int V);
+int tamgcn_vgen_lds_bytes(int S, int V, int R);
+int tamgcn_vgen_build_e(const tamgcn_ctrgc_desc* d, float* E, void* stream);
+int tamgcn_vgen_agg_fwd(const tamgcn_ctrgc_desc* d, const float* x3, const float* E, float* y, float* stats_part, void* stream);
+int tamgcn_vgen_agg_bwd(const tamgcn_ctrgc_desc* d, const tamgcn_src* dy, const float* E, float* dx3, float* db3_part, void* stream);
+int tamgcn_vgen_de_acc(const tamgcn_ctrgc_desc* d, const tamgcn_src* dy, const float* x3, float* dE, void* stream);
+int tamgcn_vgen_de_tail(const tamgcn_ctrgc_desc* d, const float* dE, float* dA_part, float* dw4_part, float* db4_part,
+                        float* dalpha_part, float* dpq, int groups, void* stream);
 
 /* ------------------------------------------------------------------------
  * Element-wise block epilogues and their backward reductions.

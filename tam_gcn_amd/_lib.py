@@ -150,6 +150,13 @@ SIGNATURES = {
     'tamgcn_ctrgc_tiled_agg_bwd': (_i, [C.POINTER(CtrgcDesc), _SP, _p, _p, _p, _p]),
     'tamgcn_ctrgc_tiled_de_acc': (_i, [C.POINTER(CtrgcDesc), _SP, _p, _p, _p]),
     'tamgcn_ctrgc_tiled_de_tail': (_i, [C.POINTER(CtrgcDesc), _p, _p, _p, _p, _p, _p, _p]),
+    'tamgcn_vgen_supported': (_i, [_i]),
+    'tamgcn_vgen_lds_bytes': (_i, [_i, _i, _i]),
+    'tamgcn_vgen_build_e': (_i, [C.POINTER(CtrgcDesc), _p, _p]),
+    'tamgcn_vgen_agg_fwd': (_i, [C.POINTER(CtrgcDesc), _p, _p, _p, _p, _p]),
+    'tamgcn_vgen_agg_bwd': (_i, [C.POINTER(CtrgcDesc), _SP, _p, _p, _p, _p]),
+    'tamgcn_vgen_de_acc': (_i, [C.POINTER(CtrgcDesc), _SP, _p, _p, _p]),
+    'tamgcn_vgen_de_tail': (_i, [C.POINTER(CtrgcDesc), _p, _p, _p, _p, _p, _p, _i, _p]),
     'tamgcn_ew_nparts': (_i, [_i, _i, _i, _i]),
     'tamgcn_gcn_tail_fwd': (_i, [_SP, _SP, _SP, _i, _i, _i, _i, _p, _p]),
     'tamgcn_gcn_tail_bwd': (_i, [_p, _p, _SP, _p, _i, _i, _i, _i, _p, _p, _p, _p]),

@@ -467,7 +467,9 @@ def ctrgc_route(V):
     """'fused'  V = 20: LDS-resident E tiles, x3 GEMM + VALU aggregation in one kernel;
     'stream' V = 25: x3 = W3 x through the pointwise GEMM (kept in HBM), aggregation / dE accumulation on MFMA with the joints padded
              to 32 in LDS, E and the dE tail from the per-(n, subset) kernels of the fused family;
-    'tiled'  V in {32, 64}: the same with tiled E / tail kernels (E of one channel is 48 KB at V = 64)."""
+    'tiled'  V in {32, 64}: the same with tiled E / tail kernels (E of one channel is 48 KB at V = 64);
+    'vgen'   every other 2 <= V <= 32 (a user's skeleton): the stream route's kernels with V as a run-time argument
+             (csrc/vgen.hip), joints padded to 16 or 32 in LDS."""
     k = _lib_().tamgcn_ctrgc_tiled_supported(int(V))
     if k == 1:
         return 'tiled'
@@ -475,11 +477,13 @@ def ctrgc_route(V):
         return 'stream'
     if V == 20:
         return 'fused'
-    raise RuntimeError(f'tam_gcn_amd: CTRGC is built for V in {{20, 25, 32, 64}} joints, got V = {V}')
+    if _lib_().tamgcn_vgen_supported(int(V)) == 1:
+        return 'vgen'
+    raise RuntimeError(f'tam_gcn_amd: CTRGC is built for 2 <= V <= 32 joints and V = 64, got V = {V}')
 
 
 def ctrgc_tiled(V):
-    """True when CTRGC runs as x3 GEMM + MFMA aggregation kernels (routes 'tiled' and 'stream')."""
+    """True when CTRGC runs as x3 GEMM + MFMA aggregation kernels (routes 'tiled', 'stream' and 'vgen')."""
     return ctrgc_route(V) != 'fused'
 
 
@@ -490,11 +494,21 @@ def ctrgc_build_E(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R):
         raise RuntimeError(f'tam_gcn_amd: CTRGC with R = {R} rel-channels is not built (multiples of 4 up to 32: in_channels <= 256 + 7)')
     d = _ctrgc_desc(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R)
     E = empty(N, S, Cout, V, V, like=x.x1)
-    if ctrgc_route(V) == 'tiled':
+    route = ctrgc_route(V)
+    if route == 'tiled':
         _lib.check(_lib_().tamgcn_ctrgc_tiled_build_e(C.byref(d), _ptr(E), _stream()), 'tamgcn_ctrgc_tiled_build_e')
+    elif route == 'vgen':
+        _lib.check(_lib_().tamgcn_vgen_build_e(C.byref(d), _ptr(E), _stream()), 'tamgcn_vgen_build_e')
     else:
         _lib.check(_lib_().tamgcn_ctrgc_build_e(C.byref(d), _ptr(E), _stream()), 'tamgcn_ctrgc_build_e')
     return E
+
+
+def _agg_entry(V, which):
+    """The streaming entry point (agg_fwd / agg_bwd / de_acc) of V's route and its name: the templated kernels of the
+    'stream' and 'tiled' routes, the run-time-V ones of 'vgen'."""
+    name = ('tamgcn_vgen_' if ctrgc_route(V) == 'vgen' else 'tamgcn_ctrgc_tiled_') + which
+    return getattr(_lib_(), name), name
 
 
 def _x3_gemm(x, w3, b3, Cin, Cout, S):
@@ -515,14 +529,14 @@ def ctrgc_fwd(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, stats, keep_x3=F
         x3 = _x3_gemm(x, w3, b3, Cin, Cout, S)
         chunks = n_chunks(N, S * Cout * T * V)
         parts = []
+        agg, name = _agg_entry(V, 'agg_fwd')
         for n0, n1 in chunks:                              # one launch unless x3 has >= 2^31 elements
             d.N = n1 - n0
             pc = None
             if stats:
                 pc = part if len(chunks) == 1 else empty(2, Cout, n1 - n0, like=x.x1)
                 parts.append(pc)
-            _lib.check(_lib_().tamgcn_ctrgc_tiled_agg_fwd(C.byref(d), _ptr(x3[n0:n1]), _ptr(E[n0:n1]), _ptr(y[n0:n1]), _ptr(pc), _stream()),
-                       'tamgcn_ctrgc_tiled_agg_fwd')
+            _lib.check(agg(C.byref(d), _ptr(x3[n0:n1]), _ptr(E[n0:n1]), _ptr(y[n0:n1]), _ptr(pc), _stream()), name)
         if stats and len(chunks) > 1:
             part = torch.cat(parts, dim=2)
         return y, part, (x3 if keep_x3 else None)
@@ -544,11 +558,11 @@ def ctrgc_bwd_dx3(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, E=None, 
     if ctrgc_tiled(V):
         if E is None:
             E = ctrgc_build_E(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R)
+        agg, name = _agg_entry(V, 'agg_bwd')
         for n0, n1 in n_chunks(N, S * Cout * T * V):
             d.N = n1 - n0
             dyc = _slice_src(dy, n0, n1).c()
-            _lib.check(_lib_().tamgcn_ctrgc_tiled_agg_bwd(C.byref(d), C.byref(dyc), _ptr(E[n0:n1]), _ptr(dx3[n0:n1]), _ptr(db3_part[n0:n1]),
-                                                          _stream()), 'tamgcn_ctrgc_tiled_agg_bwd')
+            _lib.check(agg(C.byref(d), C.byref(dyc), _ptr(E[n0:n1]), _ptr(dx3[n0:n1]), _ptr(db3_part[n0:n1]), _stream()), name)
     else:
         if E is None:
             E = ctrgc_build_E(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R)
@@ -566,11 +580,11 @@ def ctrgc_bwd_de_acc(dy, x3, Cout, S):
     d.N, d.Cout, d.S, d.T, d.V = N, Cout, S, T, V
     dE = empty(N, S, Cout, V, V, like=x3)
     if ctrgc_route(V) != 'fused':
+        acc, name = _agg_entry(V, 'de_acc')
         for n0, n1 in n_chunks(N, S * Cout * T * V):
             d.N = n1 - n0
             dyc = _slice_src(dy, n0, n1).c()
-            _lib.check(_lib_().tamgcn_ctrgc_tiled_de_acc(C.byref(d), C.byref(dyc), _ptr(x3[n0:n1]), _ptr(dE[n0:n1]), _stream()),
-                       'tamgcn_ctrgc_tiled_de_acc')
+            _lib.check(acc(C.byref(d), C.byref(dyc), _ptr(x3[n0:n1]), _ptr(dE[n0:n1]), _stream()), name)
     else:
         dyc = dy.c()
         _lib.check(_lib_().tamgcn_ctrgc_bwd_de_acc(C.byref(d), C.byref(dyc), _ptr(x3), _ptr(dE), _stream()),
@@ -611,8 +625,9 @@ def ctrgc_bwd_de_tail(dE, pq, w4, b4, alpha, R, per_subset=False, groups=1):
     db4_part = empty(N, S, Cout, like=like)
     dal_part = empty(N * S * G, 1, like=like)
     dpq = empty(G, S * 2 * R, N, V, like=like)
-    _lib.check(_lib_().tamgcn_ctrgc_bwd_de_tail(C.byref(d), _ptr(dE), _ptr(dA_part), _ptr(dw4_part), _ptr(db4_part),
-                                                _ptr(dal_part), _ptr(dpq), G, _stream()), 'tamgcn_ctrgc_bwd_de_tail')
+    name = 'tamgcn_vgen_de_tail' if ctrgc_route(V) == 'vgen' else 'tamgcn_ctrgc_bwd_de_tail'
+    _lib.check(getattr(_lib_(), name)(C.byref(d), _ptr(dE), _ptr(dA_part), _ptr(dw4_part), _ptr(db4_part),
+                                      _ptr(dal_part), _ptr(dpq), G, _stream()), name)
     dpq = dpq[0] if G == 1 else reduce_sum(dpq, G, immediate=True)       # every group holds a partial dp / dq of its channels
     return (reduce_sum(dA_part, N * G), reduce_sum(dw4_part, N, chunks=[(Cout, R, 1, 1)] * S if ps else None),
             reduce_sum(db4_part, N, chunks=[(Cout,)] * S if ps else None), reduce_sum(dal_part, N * S * G), dpq)
