@@ -333,8 +333,9 @@ int tamgcn_gcn_mid_bwd(const float* dsum, const float* ddiff, const float* y_pre
  *             mask = the forward's source with its prologue (channel mask.coff + b*Cb + k); stats_part: (sum y,
  *             sum y * (mask.x1 - center[channel])), the entry BatchNorm's backward moments.  pool is ignored (the pooled
  *             branch's gradient is tamgcn_maxpool_bwd).
- * Built for Cb = 16 or a multiple of 32, KT in {3, 5}, (KT-1)*dil even, V <= 32 or V % 16 == 0: tamgcn_tconv_supported()
- * says whether a shape is; w_b = [Cb][Cb][KT] as nn.Conv2d stores it. */
+ * Built for Cb = 16, 32 or a multiple of 64, KT in {3, 5}, (KT-1)*dil even, V <= 32 or V % 16 == 0, stride 1 or 2:
+ * tamgcn_tconv_supported() says whether a shape is (Cb = 96 is not: the weight gradient alone takes any multiple of 32);
+ * w_b = [Cb][Cb][KT] as nn.Conv2d stores it. */
 #define TAMGCN_TCONV_MAXB 6
 typedef struct tamgcn_tconv_desc {
     tamgcn_src src;
