@@ -518,6 +518,8 @@ int tamgcn_feeder_transform_indexed(const double* raw, const long long* offsets,
  * the offset_conv branch), :93-146 (MultiScale_TemporalConv), :281-283 (residual + ReLU of TCN_GCN_unit).
  *   _f2_e     E (N, S, Cout, V, V) = alpha (W4 tanh(p_u - q_v) + b4) + A with p, q = W12 mean_t(x) + b12  (conv1 / conv2 commute
  *             with the mean over T: SURVEY.md §8a);  reads x, w12, b12, w4, b4, A, alpha; writes d->E
+ *             R: every 1 <= R <= 32 is served, not only the stock 8 / 16 / 32 (the p/q product rounds its 16-row tiles of the
+ *             2R rows UP: R = 12, 20, 28 have a half-empty last tile); outside 1..32 the descriptor is refused
  *   _f2_gcn   z = sum_s E_s (W3_s x + b3_s);  y = sy z + ty;  res = 0 | x | wd x + bd (res_mode 0 | 1 | 2);
  *             writes sum = y + res and diff = res - y, both (N, Cout, T, V); reads d->E
  *   _f2_gemm  out (N, M, T, V) = epilogue(W x + b), W [M][K] row-major, x (N, K, T, V):

@@ -149,9 +149,11 @@ __device__ __forceinline__ void f2_e_body(const F2GcnArgs& a) {
     const long long TV = (long long)a.T * V;
     // Everything that does not depend on x is requested now and used after the xbar phase: the kernel is a chain of dependent
     // round trips on 12..48 workgroups, not a bandwidth problem
-    const int nrt = R2p / 16, nparts = 4 / nrt;                // pq product: 1 x 4, 2 x 2 or 4 x 1 (row tiles x K parts) over the waves
+    // pq product: 1 x 4, 2 x 2, 3 x 1 or 4 x 1 (row tiles x K parts) over the waves.  The row tiles round UP (2R = 24: two tiles,
+    // the second half empty); with three the fourth wave (ppart == nparts) multiplies zeros into a partial tile nobody sums
+    const int nrt = (R2p + 15) / 16, nparts = 4 / nrt;
     const int prt = wave % nrt, ppart = wave / nrt;
-    const float* a12 = prt * 16 + j < R2 ? a.w12 + ((long long)s * R2 + prt * 16 + j) * a.Cin : nullptr;
+    const float* a12 = ppart < nparts && prt * 16 + j < R2 ? a.w12 + ((long long)s * R2 + prt * 16 + j) * a.Cin : nullptr;
     float a12g[F2_G][4];
     f2_load_group(a12, a.Cin, a.vec12 != 0, ppart, nparts, kq, a12g);
     float b12r[5];

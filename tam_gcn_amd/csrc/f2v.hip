@@ -163,9 +163,10 @@ __device__ __forceinline__ void f2v_e_body(const FvGcnArgs& a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kq = lane >> 4;
     const long long TV = (long long)a.T * V;
     const int NTP = a.ntp;
-    const int nrt = R2p / 16, nparts = 4 / nrt;                // pq product: (row tiles x K parts) over the waves
+    // pq product: (row tiles x K parts) over the waves; the row tiles round UP, a wave past the K parts multiplies zeros (f2.hip)
+    const int nrt = (R2p + 15) / 16, nparts = 4 / nrt;
     const int prt = wave % nrt, ppart = wave / nrt;
-    const float* a12 = prt * 16 + j < R2 ? a.w12 + ((long long)s * R2 + prt * 16 + j) * a.Cin : nullptr;
+    const float* a12 = ppart < nparts && prt * 16 + j < R2 ? a.w12 + ((long long)s * R2 + prt * 16 + j) * a.Cin : nullptr;
     float b12r[NB];
 #pragma unroll
     for (int i = 0; i < NB; ++i) b12r[i] = tid + i * NT < R2 * V ? a.b12[s * R2 + (tid + i * NT) / V] : 0.f;

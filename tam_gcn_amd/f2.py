@@ -67,7 +67,7 @@ class _Block:
         Q = blk._pack_tcn(tt)
         if P.S != 3:
             raise Unsupported(f'{P.S} subsets (the f2 kernels are built for 3)')
-        if P.R > 32 or P.Cin > 256 or P.Cout % 16:
+        if not 1 <= P.R <= 32 or P.Cin > 256 or P.Cout % 16:       # every R in 1..32 is served (include/tamgcn.h, _f2_e)
             raise Unsupported(f'unit_gcn({P.Cin}, {P.Cout}) with {P.R} relation channels')
         if Q.Cb % 16 or Q.Cb > 64 or (Q.nb + 2) * Q.Cb != Q.Cout or Q.nb > 4 or len(set(Q.ks)) != 1:
             raise Unsupported(f'MultiScale_TemporalConv with {Q.nb} temporal branches of {Q.Cb} channels, kernels {Q.ks}')

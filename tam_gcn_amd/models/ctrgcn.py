@@ -269,6 +269,8 @@ class CTRGC(nn.Module):
             self.mid_channels = in_channels // mid_reduction
         # the refinement kernels (csrc/ctrgc.hip, ctrgc_de.hip) are built for R = 4, 8, ..., 32 rel-channels: every width the
         # reference's models use (in_channels 3 / 9 -> 8; 64 / 128 / 256 -> 8 / 16 / 32).  Say so HERE, not at the first forward
+        # (the small-batch eval kernels, csrc/f2.hip / f2v.hip, serve every R in 1..32 -- include/tamgcn.h, the guard of
+        # f2._Block -- so every R admitted here, 12, 20, 24 and 28 included, runs there as well: tests/test_gpu_f2_stages.py)
         if self.rel_channels < 4 or self.rel_channels > 32 or self.rel_channels % 4:
             raise NotImplementedError(
                 f'tam_gcn_amd CTRGC: rel_channels = in_channels // rel_reduction = {self.rel_channels} is not built '

@@ -2,9 +2,11 @@
 reference's inference callers run: ensemble/ensemble_ctrgcn_resnet_eval.py:147-183, models/resnet_gcn_attention.py:82-85,
 visual.py:53-55 (model(data) in eval mode on a handful of clips).
 
-Bars: every block, fed the fp64 oracle's own input for that block (teacher-forced), within 2e-5 of max|ref| (exact fp32
-MFMA, BatchNorm folded in fp32); logits within 1e-3 of the reference's golden eval logits (test_gpu_model.py's eval section
-runs through this path too, the batches there are small) and within 2e-5 of the general eval path."""
+Bars: every block, fed the fp64 oracle's own input for that block (teacher-forced), within 4 x 8.56e-7 of max|ref| (8.56e-7:
+the worst block of the three shapes on the MI355X once the per-stage ledger, test_gpu_f2_stages.py, was green; 4 x because a
+block holds ~1e6 ReLU inputs and a summation-order change moves the worst element; exact fp32 MFMA, BatchNorm folded in
+fp32); logits within 1e-3 of the reference's golden eval logits (test_gpu_model.py's eval section runs through this path
+too, the batches there are small) and within 2e-5 of the general eval path."""
 import numpy as np
 import pytest
 import torch
@@ -57,7 +59,7 @@ def test_every_block_against_the_fp64_oracle(shape, golden_models):
         got = eng._block(b, xin.float().to(DEV).contiguous()).double().cpu()
         assert got.shape == ref.shape, (i, got.shape, ref.shape)
         err = float((got - ref).abs().max() / ref.abs().max())
-        assert err <= 2e-5, f'l{i}: {err:.3e} of max|ref|'
+        assert err <= 4 * 8.56e-7, f'l{i}: {err:.3e} of max|ref|'      # measured worst: 8.56e-7 (l10 of t13_ragged)
     with torch.no_grad():
         logits = eng(x.to(DEV)).double().cpu()
     ref = O.model_forward(x.double(), sd64, 20, training=False)

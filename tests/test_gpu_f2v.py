@@ -1,10 +1,11 @@
 """-m gpu: the small-batch eval-mode kernel family for 25-joint (NTU-RGB+D) models (csrc/f2v.hip, tam_gcn_amd/f2v.py).
 
 Bars (the V = 20 family's, tests/test_gpu_f2.py): every block, fed the fp64 oracle's own input for that block
-(teacher-forced), within 2e-5 of max|ref|; logits within 1e-4 max|ref| of the fp64 oracle with the same argmax; logits within
+(teacher-forced), within 4 x 1.21e-6 of max|ref| (1.21e-6: the worst block this file printed on the MI355X once the per-stage
+ledger, test_gpu_f2_stages.py, was green); logits within 1e-4 max|ref| of the fp64 oracle with the same argmax; logits within
 1e-3 of the reference's golden eval logits; logits and features within 2e-5 (relative) of the general eval path.  An fp32
-torch evaluation of the same blocks stays below 5.5e-7 (logits 2.7e-6) on the three shapes: the bars are 30x the
-reference's own rounding.  `pytest -s` prints the measured ratios."""
+torch evaluation of the same blocks stays below 5.5e-7 (logits 2.7e-6) on the three shapes: the logits bars are 30x the
+reference's own rounding, the block bar 9x.  `pytest -s` prints the measured ratios."""
 import ctypes as C
 import os
 
@@ -82,7 +83,7 @@ def test_every_block_against_the_fp64_oracle(shape, golden_models):
         errs.append(_rel(got, ref))
     print(f'\n{shape}: block error / max|ref|: ' + ' '.join(f'l{i}={e:.2e}' for i, e in enumerate(errs, 1)))
     for i, e in enumerate(errs, 1):
-        assert e <= 2e-5, f'l{i}: {e:.3e} of max|ref|'
+        assert e <= 4 * 1.21e-6, f'l{i}: {e:.3e} of max|ref|'          # measured worst: 1.21e-6 (l9 of t30)
     with torch.no_grad():
         logits = eng(x.to(DEV)).double().cpu()
     ref = O.model_forward(x.double(), sd64, 25, training=False)
