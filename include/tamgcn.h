@@ -568,22 +568,27 @@ typedef struct tamgcn_f2_tcn_desc {
 } tamgcn_f2_tcn_desc;
 int tamgcn_f2_tcn(const tamgcn_f2_tcn_desc* d, void* stream);
 
-/* ---- f2v: the same four stages for NTU-RGB+D's V = 25, S = 3 (tam_gcn_amd/csrc/f2v.hip, tam_gcn_amd/f2v.py): the f2 descriptors
- * and the algebra above, unchanged, with d->V == 25.  What differs is where the frames lie.  Only the BLOCK's input and output
- * are contiguous (N, C, T, 25); every buffer that lives between the launches of one block has frames (rows of joints) of
- * VP = 28 floats, so that each is 16-byte aligned whatever T is:
- *   _f2v_e     reads d->x (N, Cin, T, 25) contiguous, or d->xpart (N, ceil(T/4), Cin, 28);  writes d->E (N, S, Cout, 25, 28):
- *              E[c][u][v] at u*28 + v, columns 25..27 zero
- *   _f2v_gcn   reads d->x contiguous and d->E;  writes d->sum, d->diff (N, Cout, T, 28), columns 25..27 zero
- *   _f2v_gemm  x, add, out: (N, K | M, T, 28).  Columns 25..27 of out get the epilogue of whatever x and add hold there
+/* ---- f2v: the same four stages for skeletons whose joint count V is NOT a multiple of four, S = 3 (tam_gcn_amd/csrc/f2v.hip,
+ * tam_gcn_amd/f2v.py): the f2 descriptors and the algebra above, unchanged.  Served joint counts d->V: 17 (COCO / YOLO-pose
+ * keypoints), 18 (OpenPose), 25 (NTU-RGB+D) -- the list FV_JOINTS of f2v.hip; every other d->V is refused on the host before
+ * any launch.  What differs from f2 is where the frames lie.  Only the BLOCK's input and output are contiguous (N, C, T, V);
+ * every buffer that lives between the launches of one block has frames (rows of joints) of VP = (V + 3) & ~3 floats (20 at V =
+ * 17 and 18, 28 at V = 25), so that each is 16-byte aligned whatever T is:
+ *   _f2v_e     reads d->x (N, Cin, T, V) contiguous, or d->xpart (N, ceil(T/4), Cin, VP);  writes d->E (N, S, Cout, V, VP):
+ *              E[c][u][v] at u*VP + v, columns V..VP-1 zero
+ *   _f2v_gcn   reads d->x contiguous and d->E;  writes d->sum, d->diff (N, Cout, T, VP), columns V..VP-1 zero
+ *   _f2v_gemm  x, add, out: (N, K | M, T, VP).  Columns V..VP-1 of out get the epilogue of whatever x and add hold there
  *              (finite when those are); no kernel lets them reach a joint
- *   _f2v_tcn   d->h (N, Cout, T, 28);  d->x contiguous (N, Cin, T, 25);  d->out contiguous (N, Cout, T_out, 25);
- *              d->xpart (N, ceil(T_out/4), Cout, 28): sums of out over each FOUR-frame tile (as f2), columns 25..27 zero
+ *   _f2v_tcn   d->h (N, Cout, T, VP);  d->x contiguous (N, Cin, T, V);  d->out contiguous (N, Cout, T_out, V);
+ *              d->xpart (N, ceil(T_out/4), Cout, VP): sums of out over each FOUR-frame tile (as f2), columns V..VP-1 zero
+ * Columns V..VP-1 of E, sum, diff and xpart are exactly zero whatever the inputs' pad columns hold (those are never trusted).
  * Alignment: x and out 4 bytes, everything else 16.  The contiguous input is read in 16-byte pieces from dword-aligned
- * addresses; the last piece of a frame reaches 12 bytes past it, so 12 readable bytes must follow x (tam_gcn_amd.ops.empty /
- * with_slack); what is read there is discarded.  Each entry point computes its LDS request and refuses one above 160 KB
- * (none arises for Cin, K <= 256, R <= 32, Cb <= 64).  Deterministic: two runs are bit-equal.
- * Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed. */
+ * addresses; the last piece of a frame reaches VP - V floats (at most 12 bytes) past it, so 12 readable bytes must follow x
+ * (tam_gcn_amd.ops.empty / with_slack); what is read there is discarded.  Each entry point computes its LDS request from the
+ * geometry of d->V and refuses one above 160 KB (none arises for Cin, K <= 256, R <= 32, Cb <= 64).  Deterministic: two runs
+ * are bit-equal.
+ * Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed.  V = 17 and 18 were added
+ * the same way: more accepted values of d->V, no symbol, descriptor or layout changed. */
 int tamgcn_f2v_e(const tamgcn_f2_gcn_desc* d, void* stream);
 int tamgcn_f2v_gcn(const tamgcn_f2_gcn_desc* d, void* stream);
 int tamgcn_f2v_gemm(const tamgcn_f2_gemm_desc* d, void* stream);
@@ -592,7 +597,7 @@ int tamgcn_f2v_tcn(const tamgcn_f2_tcn_desc* d, void* stream);
 /* ---- grouped: the four stages of both families for `groups` models of ONE geometry in one launch (a multi-stream ensemble:
  * tam_gcn_amd.inference.StreamEnsemble).  The descriptors above, unchanged, plus `int groups`:
  *   samples      d->N is the TOTAL number of clip-persons, N % groups == 0; samples [g N/groups, (g+1) N/groups) belong to group g
- *   activations  x, E, sum, diff, h, out, xpart (and the 28-float frames of f2v): the layouts above, indexed by the total sample
+ *   activations  x, E, sum, diff, h, out, xpart (and the VP-float frames of f2v): the layouts above, indexed by the total sample
  *   parameters   every parameter pointer of the descriptor is group 0's; group g's array follows densely at g times the array's
  *                own size as the descriptor's dimensions give it:  w12 S*2R*Cin,  b12 S*2R,  w4 S*Cout*R,  b4 S*Cout,  A S*V*V,
  *                alpha 1,  w3 S*Cout*Cin,  b3 S*Cout,  sy, ty Cout,  wd Cout*Cin,  bd Cout;  gemm w M*K, b M;  tcn wt[b] Cb*Cb*ks,

@@ -1,6 +1,8 @@
 // f2v: the small-batch eval-mode TCN_GCN_unit (f2.hip's family: same four stages, same algebra, include/tamgcn.h) for
-// skeletons whose joint count is NOT a multiple of four -- NTU-RGB+D's V = 25.  A sibling with its own geometry, as
-// ctrgc_tiled.hip is to ctrgc.hip, because three things of the V = 20 kernels do not carry over:
+// skeletons whose joint count is NOT a multiple of four -- NTU-RGB+D's V = 25, COCO's 17, OpenPose's 18.  A sibling with its
+// own geometry, as ctrgc_tiled.hip is to ctrgc.hip, because three things of the V = 20 kernels do not carry over (told below
+// in the numbers of V = 25, VP = 28; FvGeo<V> has them for every V: at 17 and 18 VP = 20, a frame is five 16-byte pieces, a
+// tile 80 columns = 5 MFMA tiles, and V = 18 keeps TWO lanes of a frame's last piece where 17 and 25 keep one):
 //
 //   alignment   a (n, c) row of T*25 floats starts on a 16-byte boundary only by accident (300 -> 150 -> 75 frames).  Only the
 //               block's input and output keep that contiguous (N, C, T, V) form.  Everything the family allocates for itself
@@ -17,7 +19,8 @@
 //               other through ONE region (152 KB at Cin = 256).  The host computes every request and refuses above 160 KB.
 //
 // Arithmetic: v_mfma_f32_16x16x4_f32 (exact fp32), the K blocks of a product dealt round-robin to the waves, the partial tiles
-// summed through LDS in a fixed order: two runs are bit-equal.  Templated on V; instantiated for V = 25, S = 3.
+// summed through LDS in a fixed order: two runs are bit-equal.  Templated on V; instantiated for every V of FV_JOINTS (the host
+// half at the end of the file: 17 = COCO / YOLO-pose, 18 = OpenPose, 25 = NTU-RGB+D), S = 3.
 #include "common.h"
 
 namespace {
@@ -642,32 +645,42 @@ template <int V> __global__ __launch_bounds__(FV_NT) void f2v_tcn_kernel(const F
 template <int V> __global__ __launch_bounds__(FV_NT) void f2v_tcn_grouped_kernel(const FvTcnArgs a, int npg) { f2v_tcn_body<V>(a, blockIdx.y / npg); }
 
 // ---- host -----------------------------------------------------------------------------------------------------------
-constexpr int FV_V = 25;
+// The joint counts the family is instantiated for: THE list (tam_gcn_amd/f2v.py mirrors it as JOINTS).  Serving another
+// skeleton with V % 4 != 0 is one more X(..) here -- after reading FvGeo's asserts and fv_stage's LAST for that V.
+#define FV_JOINTS(X) X(17) X(18) X(25)
+
+constexpr int FV_V = 25;                               // the widest geometry of the list: what FV_LDS_MAX has to hold (asserted below)
 constexpr size_t FV_LDS_MAX = 160 * 1024;
-using GV = FvGeo<FV_V>;
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
-size_t fv_e_lds(int Cin, int R, int ntp) {
+#define FV_JOINT_TXT(v) " V = " #v ","
+#define FV_BUILT_FOR "this family is built for" FV_JOINTS(FV_JOINT_TXT) " S = 3"
+
+// Everything of the host half that depends on the geometry: the LDS requests and the launches, per served V.
+template <int V> struct FvHost {
+using GV = FvGeo<V>;
+
+static constexpr size_t fv_e_lds(int Cin, int R, int ntp) {
     const int Kp = (Cin + 15) & ~15, R2p = 2 * R < 16 ? 16 : 2 * R, Rp = (R + 15) & ~15;
     const size_t d = (size_t)Rp * GV::PD, xp = (size_t)ntp * Kp * GV::VP;
     return sizeof(float) * ((size_t)Kp * FV_PX + (size_t)R2p * FV_PX + 64 * FV_PX + (d > xp ? d : xp));
 }
-size_t fv_gcn_lds(int Cin) {
+static constexpr size_t fv_gcn_lds(int Cin) {
     const int Kp = (Cin + 15) & ~15;
     return sizeof(float) * ((size_t)(Kp < FV_KC ? Kp : FV_KC) * GV::PB + 2 * 32 * GV::PB + 3 * GV::ES);
 }
-size_t fv_gemm_lds(int K) { return sizeof(float) * ((size_t)((K + 15) & ~15) * GV::PB + 4 * 16 * GV::PB); }
-size_t fv_tcn_lds(int Cin, int Cb, int res_mode) {
+static constexpr size_t fv_gemm_lds(int K) { return sizeof(float) * ((size_t)((K + 15) & ~15) * GV::PB + 4 * 16 * GV::PB); }
+static constexpr size_t fv_tcn_lds(int Cin, int Cb, int res_mode) {
     const size_t xs = (size_t)(res_mode == 2 ? (Cin + 15) & ~15 : 0) * GV::PB, hs = (size_t)Cb * GV::PH;
     return sizeof(float) * ((size_t)5 * 16 * GV::PB + (xs > hs ? xs : hs));
 }
 
-int fv_fill(const tamgcn_f2_gcn_desc* d, FvGcnArgs* a, const char* who) {
+static int fv_fill(const tamgcn_f2_gcn_desc* d, FvGcnArgs* a, const char* who) {
     TG_CHECK(d && d->x && d->w12 && d->b12 && d->w4 && d->b4 && d->A && d->alpha && d->w3 && d->b3 && d->sy && d->ty && d->E,
              "%s: null pointer", who);
-    TG_CHECK(d->V == FV_V && d->S == 3, "%s: V=%d S=%d (this family is built for V = 25, S = 3)", who, d->V, d->S);
+    TG_CHECK(d->V == V && d->S == 3, "%s: V=%d S=%d (" FV_BUILT_FOR ")", who, d->V, d->S);
     TG_CHECK(d->N > 0 && d->T > 0 && d->Cin > 0 && d->Cin <= 256 && d->Cout > 0 && d->Cout % 16 == 0,
              "%s: bad shape N=%d T=%d Cin=%d Cout=%d (Cin <= 256, Cout %% 16 == 0)", who, d->N, d->T, d->Cin, d->Cout);
     TG_CHECK(d->R >= 1 && d->R <= 32, "%s: R=%d outside 1..32", who, d->R);
@@ -688,7 +701,7 @@ int fv_fill(const tamgcn_f2_gcn_desc* d, FvGcnArgs* a, const char* who) {
 }
 
 // groups == 0: the plain entry point; otherwise the grouped one (common.h: tg_groups_ok, tg_group_stride_ok).
-int fv_e_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
+static int fv_e_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
     FvGcnArgs a;
     if (fv_fill(d, &a, who)) return -1;
     a.ntp = fv_e_lds(d->Cin, d->R, 4) <= FV_LDS_MAX ? 4 : 2;
@@ -697,17 +710,17 @@ int fv_e_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const cha
     const dim3 grid(d->S * (d->Cout / 16), d->N);
     if (groups) {
         if (tg_groups_ok(d->N, groups, who) || tg_gcn_group_strides_ok(d, a.vec12, a.vec4, a.vec3, a.vecd, who)) return -1;
-        tg_launch_lds<f2v_e_grouped_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tg_launch_lds<f2v_e_grouped_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
         tamgcn_note_kernel("f2v_e_grouped_kernel");
     } else {
-        tg_launch_lds<f2v_e_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tg_launch_lds<f2v_e_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
         tamgcn_note_kernel("f2v_e_kernel");
     }
     TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-int fv_gcn_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
+static int fv_gcn_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
     FvGcnArgs a;
     if (fv_fill(d, &a, who)) return -1;
     TG_CHECK(d->sum && d->diff && al16(d->sum) && al16(d->diff), "%s: null or misaligned output", who);
@@ -716,19 +729,19 @@ int fv_gcn_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const c
     const dim3 grid(ceil_div(d->T, FV_BT) * (d->Cout / FV_CT), d->N);
     if (groups) {
         if (tg_groups_ok(d->N, groups, who) || tg_gcn_group_strides_ok(d, a.vec12, a.vec4, a.vec3, a.vecd, who)) return -1;
-        tg_launch_lds<f2v_gcn_grouped_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tg_launch_lds<f2v_gcn_grouped_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
         tamgcn_note_kernel("f2v_gcn_grouped_kernel");
     } else {
-        tg_launch_lds<f2v_gcn_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tg_launch_lds<f2v_gcn_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
         tamgcn_note_kernel("f2v_gcn_kernel");
     }
     TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-int fv_gemm_launch(const tamgcn_f2_gemm_desc* d, int groups, void* stream, const char* who) {
+static int fv_gemm_launch(const tamgcn_f2_gemm_desc* d, int groups, void* stream, const char* who) {
     TG_CHECK(d && d->x && d->w && d->b && d->out, "%s: null pointer", who);
-    TG_CHECK(d->V == FV_V, "%s: V=%d (built for V = 25)", who, d->V);
+    TG_CHECK(d->V == V, "%s: V=%d (" FV_BUILT_FOR ")", who, d->V);
     TG_CHECK(d->N > 0 && d->T > 0 && d->K > 0 && d->K <= 256 && d->M > 0 && d->M % 16 == 0,
              "%s: bad shape N=%d T=%d K=%d M=%d (K <= 256, M %% 16 == 0)", who, d->N, d->T, d->K, d->M);
     TG_CHECK(d->mode == 0 || d->mode == 1, "%s: mode=%d", who, d->mode);
@@ -744,19 +757,19 @@ int fv_gemm_launch(const tamgcn_f2_gemm_desc* d, int groups, void* stream, const
     if (groups) {
         if (tg_groups_ok(d->N, groups, who)) return -1;
         if (tg_group_stride_ok(a.vec, (long long)d->M * d->K, who, "w")) return -1;
-        tg_launch_lds<f2v_gemm_grouped_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tg_launch_lds<f2v_gemm_grouped_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
         tamgcn_note_kernel("f2v_gemm_grouped_kernel");
     } else {
-        tg_launch_lds<f2v_gemm_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tg_launch_lds<f2v_gemm_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
         tamgcn_note_kernel("f2v_gemm_kernel");
     }
     TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-int fv_tcn_launch(const tamgcn_f2_tcn_desc* d, int groups, void* stream, const char* who) {
+static int fv_tcn_launch(const tamgcn_f2_tcn_desc* d, int groups, void* stream, const char* who) {
     TG_CHECK(d && d->h && d->out && d->sp && d->tp, "%s: null pointer", who);
-    TG_CHECK(d->V == FV_V, "%s: V=%d (built for V = 25)", who, d->V);
+    TG_CHECK(d->V == V, "%s: V=%d (" FV_BUILT_FOR ")", who, d->V);
     TG_CHECK(d->N > 0 && d->T > 0 && d->Cout > 0 && d->Cout % 16 == 0 && d->stride >= 1 && d->stride <= 2,
              "%s: bad shape N=%d T=%d Cout=%d stride=%d", who, d->N, d->T, d->Cout, d->stride);
     TG_CHECK(d->nb >= 1 && d->nb <= 4 && d->Cb % 16 == 0 && d->Cb <= 64 && (d->nb + 2) * d->Cb == d->Cout,
@@ -793,14 +806,60 @@ int fv_tcn_launch(const tamgcn_f2_tcn_desc* d, int groups, void* stream, const c
         if (tg_groups_ok(d->N, groups, who)) return -1;
         if (tg_group_stride_ok(a.vect, (long long)d->Cb * d->Cb * d->ks, who, "wt")) return -1;
         if (tg_group_stride_ok(a.vecr, (long long)d->Cout * d->Cin, who, "wr")) return -1;
-        tg_launch_lds<f2v_tcn_grouped_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tg_launch_lds<f2v_tcn_grouped_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
         tamgcn_note_kernel("f2v_tcn_grouped_kernel");
     } else {
-        tg_launch_lds<f2v_tcn_kernel<FV_V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tg_launch_lds<f2v_tcn_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
         tamgcn_note_kernel("f2v_tcn_kernel");
     }
     TG_LAUNCH_CHECK(who);
     return 0;
+}
+};  // FvHost
+
+static_assert(FvHost<FV_V>::fv_e_lds(256, 32, 2) <= FV_LDS_MAX && FvHost<FV_V>::fv_gcn_lds(256) <= FV_LDS_MAX &&
+              FvHost<FV_V>::fv_gemm_lds(256) <= FV_LDS_MAX && FvHost<FV_V>::fv_tcn_lds(256, 64, 2) <= FV_LDS_MAX,
+              "the widest served geometry fits the LDS cap at the stock model's widest layers");
+
+// One row of launchers per served joint count; the entry points pick theirs by d->V.  Any other V is refused here, on the
+// host, before a pointer of the descriptor is looked at.
+struct FvRow {
+    int V;
+    int (*e)(const tamgcn_f2_gcn_desc*, int, void*, const char*);
+    int (*gcn)(const tamgcn_f2_gcn_desc*, int, void*, const char*);
+    int (*gemm)(const tamgcn_f2_gemm_desc*, int, void*, const char*);
+    int (*tcn)(const tamgcn_f2_tcn_desc*, int, void*, const char*);
+};
+#define FV_ROW(v) {v, FvHost<v>::fv_e_launch, FvHost<v>::fv_gcn_launch, FvHost<v>::fv_gemm_launch, FvHost<v>::fv_tcn_launch},
+const FvRow FV_ROWS[] = {FV_JOINTS(FV_ROW)};
+
+const FvRow* fv_row(int V) {
+    for (const FvRow& r : FV_ROWS)
+        if (r.V == V) return &r;
+    return nullptr;
+}
+
+template <class D> const FvRow* fv_pick(const D* d, const char* who) {
+    if (!d) { tamgcn_set_error("%s: null pointer", who); return nullptr; }
+    const FvRow* r = fv_row(d->V);
+    if (!r) tamgcn_set_error("%s: V=%d (" FV_BUILT_FOR ")", who, d->V);
+    return r;
+}
+int fv_e_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
+    const FvRow* r = fv_pick(d, who);
+    return r ? r->e(d, groups, stream, who) : -1;
+}
+int fv_gcn_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
+    const FvRow* r = fv_pick(d, who);
+    return r ? r->gcn(d, groups, stream, who) : -1;
+}
+int fv_gemm_launch(const tamgcn_f2_gemm_desc* d, int groups, void* stream, const char* who) {
+    const FvRow* r = fv_pick(d, who);
+    return r ? r->gemm(d, groups, stream, who) : -1;
+}
+int fv_tcn_launch(const tamgcn_f2_tcn_desc* d, int groups, void* stream, const char* who) {
+    const FvRow* r = fv_pick(d, who);
+    return r ? r->tcn(d, groups, stream, who) : -1;
 }
 
 }  // namespace

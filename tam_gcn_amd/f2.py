@@ -116,8 +116,9 @@ def _ptr(t):
 
 
 class FusedEval:
-    """The V = 20 engine.  tam_gcn_amd.f2v.FusedEvalV derives the V = 25 one from it: the folding (_Block), the state key and
-    the re-fold are the same; V, FAMILY and _block (which registered operator runs a block) are what a family sets."""
+    """The V = 20 engine.  tam_gcn_amd.f2v.FusedEvalV derives the V = 25 one from it and FusedEvalJ the one for the other joint
+    counts of f2v.JOINTS: the folding (_Block), the state key and the re-fold are the same; V, FAMILY and _block (which
+    registered operator runs a block) are what a family sets."""
     V = 20
     FAMILY = 'f2'
 
@@ -234,19 +235,23 @@ def _(x, xpart, params, geom):
 #   geom   as above, shared by all groups
 # Group g's slice of the result is bit-equal to tcn_gcn_unit_eval on group g's slice and parameters.
 # ----------------------------------------------------------------------------------------------------------------------
-def _unit(fam, x, xpart, params, geom, groups):
-    """The five launches of one block: the body of all four registered block operators.  fam 'f2' (V = 20) | 'f2v' (V = 25:
-    frames of 28 floats in the family's own buffers, 12 bytes of slack behind the contiguous input and output); groups None:
-    the plain entry points on one model's params, else the grouped ones on params stacked on a leading group axis."""
+def _unit(fam, x, xpart, params, geom, groups, joints=(25,), tag='_v25'):
+    """The five launches of one block: the body of all six registered block operators.  fam 'f2' (V = 20) | 'f2v' (V =
+    x.shape[3], one of `joints`: frames of VP = (V + 3) & ~3 floats in the family's own buffers, 12 bytes of slack behind the
+    contiguous input and output; `tag` names the operator in messages); groups None: the plain entry points on one model's
+    params, else the grouped ones on params stacked on a leading group axis."""
     from . import ops
     lib = _lib.load()
     sfx = '' if groups is None else '_grouped'
-    name = f'tamgcn::tcn_gcn_unit_eval{"" if fam == "f2" else "_v25"}{sfx}'
-    V_, VP = (20, 20) if fam == 'f2' else (25, 28)
+    name = f'tamgcn::tcn_gcn_unit_eval{"" if fam == "f2" else tag}{sfx}'
+    if fam == 'f2':
+        joints = (20,)
     if not x.is_cuda or x.dtype != torch.float32:
         raise RuntimeError(f'{name}: expected a float32 HIP (cuda) tensor; there is no CPU path')
-    if x.dim() != 4 or x.shape[3] != V_:
-        raise RuntimeError(f'{name}: expected (N, C, T, {V_}), got {tuple(x.shape)}')
+    if x.dim() != 4 or x.shape[3] not in joints:
+        raise RuntimeError(f'{name}: expected (N, C, T, {" | ".join(map(str, joints))}), got {tuple(x.shape)}')
+    V_ = x.shape[3]
+    VP = (V_ + 3) & ~3
     if groups is not None:
         if groups < 1 or x.shape[0] % groups:
             raise RuntimeError(f'{name}: {x.shape[0]} samples are not a multiple of groups = {groups}')
@@ -340,7 +345,7 @@ def _model_fields(m):
 
 
 class GroupedEval:
-    """G models of one geometry (V = 20: the f2 kernels, V = 25: f2v) as ONE launch sequence: a fused stem
+    """G models of one geometry (V = 20: the f2 kernels, V in f2v.JOINTS: f2v) as ONE launch sequence: a fused stem
     (tamgcn_stem_streams_eval), five grouped launches per block, one pool and one grouped fc -- 54 launches whatever G is.
 
         eng = GroupedEval(models)                       # all in eval() mode, on one device
@@ -367,13 +372,18 @@ class GroupedEval:
                 if a != b:
                     raise ValueError(f'GroupedEval: model {g} differs from model 0 in {name}: {b} != {a}')
         V = f0[0][1]
+        from . import f2v
         if V == 20:
             cls, self.FAMILY = FusedEval, 'f2'
+            self._blk = torch.ops.tamgcn.tcn_gcn_unit_eval_grouped
         elif V == 25:
-            from .f2v import FusedEvalV
-            cls, self.FAMILY = FusedEvalV, 'f2v'
+            cls, self.FAMILY = f2v.FusedEvalV, 'f2v'
+            self._blk = torch.ops.tamgcn.tcn_gcn_unit_eval_v25_grouped
+        elif V in f2v.JOINTS:
+            cls, self.FAMILY = f2v.FusedEvalJ, 'f2v'
+            self._blk = torch.ops.tamgcn.tcn_gcn_unit_eval_vj_grouped
         else:
-            raise Unsupported(f'{V} joints (the small-batch kernels are built for V = 20 and V = 25)')
+            raise Unsupported(f'{V} joints (the small-batch kernels are built for V = 20 and V in {f2v.JOINTS})')
         self.V, self.M, self.K = V, f0[3][1], f0[1][1]
         self.models = models
         self.engines = [cls(m) for m in models]
@@ -440,9 +450,8 @@ class GroupedEval:
         G = len(self.models)
         h = ops.stem_streams_eval(x, parent, modes, self._coef)
         xp = None
-        blk = torch.ops.tamgcn.tcn_gcn_unit_eval_grouped if self.FAMILY == 'f2' else torch.ops.tamgcn.tcn_gcn_unit_eval_v25_grouped
         for params, geom in stacked:
-            h, xp = blk(h, xp, params, geom, G)
+            h, xp = self._blk(h, xp, params, geom, G)
         pooled = ops.head_pool_fwd(h, self.M)                      # (G*N, C): the single model's per-row arithmetic
         return ops.head_fc_grouped(pooled, self._fcw, self._fcb, G)
 

@@ -26,6 +26,9 @@ from . import ops
 
 __all__ = ['GraphedForward', 'StreamEnsemble']
 
+# where models.ctrgcn.Model keeps its small-batch engines: f2.FusedEval, f2v.FusedEvalV, f2v.FusedEvalJ (one slot per class)
+ENGINE_SLOTS = ('_tamgcn_f2', '_tamgcn_f2v', '_tamgcn_f2j')
+
 
 class GraphedForward:
     """split (default 1): eval-mode BatchNorm uses the running statistics, so a batch may be cut into `split` slices that run
@@ -91,7 +94,7 @@ class GraphedForward:
         # owned by the per-module caches (functional._eval_cached): an eager forward after a parameter change evicts
         # them.  This entry keeps them alive, so a replay without reset() reads stale coefficients, never freed memory.
         keep = [dict(m.__dict__['_tamgcn_eval_cache']) for m in self.model.modules() if '_tamgcn_eval_cache' in m.__dict__]
-        for slot in ('_tamgcn_f2', '_tamgcn_f2v'):          # small batches: the folded weights of tam_gcn_amd.f2 / f2v, likewise
+        for slot in ENGINE_SLOTS:                            # small batches: the folded weights of tam_gcn_amd.f2 / f2v, likewise
             eng = self.model.__dict__.get(slot)
             if eng:
                 keep.append(eng._blocks)
@@ -134,7 +137,8 @@ class StreamEnsemble(nn.Module):
     x is (N, C, T, V, M) or (N, T, V*C), float32 on the GPU, under torch.no_grad().  forward(x) -> fused (N, K);
     predict(x) -> (fused, pred int64 (N), scores (G, N, K)).
 
-    Small inputs (G*N*M <= f2.F2_MAX_CLIPS at V = 20, G*N*M*T <= f2v.F2V_MAX_FRAMES at V = 25; TAMGCN_F2 != 0; no forward
+    Small inputs (G*N*M <= f2.F2_MAX_CLIPS at V = 20, G*N*M*T <= f2v.F2V_MAX_FRAMES at V = 25 and <= f2v.F2J_MAX_FRAMES at
+    V = 17, 18; TAMGCN_F2 != 0; no forward
     hooks on any sub-module) run as ONE grouped launch sequence (f2.GroupedEval: 54 launches whatever G is).  Anything else
     runs each model's own forward on its derived stream (ops.stream_derive) and fuses the scores: the same result to
     rounding, at any size.
@@ -190,7 +194,7 @@ class StreamEnsemble(nn.Module):
     def _tamgcn_keep_alive(self):
         keep = [] if self._eng is None else self._eng.keep_alive()
         for m in self.models:
-            for slot in ('_tamgcn_f2', '_tamgcn_f2v'):
+            for slot in ENGINE_SLOTS:
                 eng = m.__dict__.get(slot)
                 if eng:
                     keep.append(eng._blocks)
@@ -206,7 +210,7 @@ class StreamEnsemble(nn.Module):
         G, (N, _, T, V, M) = len(self.models), x5.shape
         if V != eng.V or M != eng.M:
             return none
-        if (G * N * M > f2.F2_MAX_CLIPS) if V == 20 else (G * N * M * T > f2v.F2V_MAX_FRAMES):
+        if (G * N * M > f2.F2_MAX_CLIPS) if V == 20 else (G * N * M * T > (f2v.F2V_MAX_FRAMES if V == 25 else f2v.F2J_MAX_FRAMES)):
             return none
         for mod in self.modules():
             if mod._forward_hooks or mod._forward_pre_hooks:

@@ -508,6 +508,19 @@ class Model(nn.Module):
             return None
         return self._small_batch_engine(x, '_tamgcn_f2v', f2v.FusedEvalV)
 
+    def _f2j(self, x):
+        """The same for the other joint counts of the f2v kernels (f2v.JOINTS: 17, 18): at most F2J_MAX_FRAMES clip-persons x
+        frames.  Its own slot: _f2 and _f2v keep returning None for these models."""
+        if self.training or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32:
+            return None
+        from .. import f2v
+        if self.num_point not in f2v.JOINTS or self.num_point == 25:
+            return None
+        frames = x.shape[0] * x.shape[4] * x.shape[2] if x.dim() == 5 else x.shape[0] * x.shape[1]
+        if not f2v.enabled() or frames > f2v.F2J_MAX_FRAMES:
+            return None
+        return self._small_batch_engine(x, '_tamgcn_f2j', f2v.FusedEvalJ)
+
     def _small_batch_engine(self, x, slot, cls):
         from .. import f2
         # the engine calls the block operator directly: forward hooks on any sub-module would not fire.  A model that
@@ -529,7 +542,7 @@ class Model(nn.Module):
 
     def forward(self, x):
         x = _require_hip(x)
-        eng = self._f2(x) or self._f2v(x)
+        eng = self._f2(x) or self._f2v(x) or self._f2j(x)
         if eng is not None:
             return eng(x)
         if isinstance(self.drop_out, nn.Dropout):          # drop_out > 0: pool here, torch's dropout + linear (reference :343-348)
@@ -543,7 +556,7 @@ class Model(nn.Module):
 
     def extract_feature(self, x):
         x = _require_hip(x)
-        eng = self._f2(x) or self._f2v(x)
+        eng = self._f2(x) or self._f2v(x) or self._f2j(x)
         x, N, M = eng.blocks(x) if eng is not None else self._blocks(x)
         _, C, T, V = x.size()
         x = x.view(N, M, C, T, V).permute(0, 2, 3, 4, 1).contiguous()

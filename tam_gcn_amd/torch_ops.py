@@ -17,6 +17,8 @@ backward is itself a registered op:
                                                  batches, BatchNorm folded; registered by tam_gcn_amd/f2.py with the engine that uses it
     tamgcn::tcn_gcn_unit_eval_v25(x, xpart, params, geom) -> (out, xpart)   the same for 25 joints (tam_gcn_amd/f2v.py); xpart there
                                                  has frames of 28 floats
+    tamgcn::tcn_gcn_unit_eval_vj(x, xpart, params, geom) -> (out, xpart)    the same for any joint count of f2v.JOINTS (17, 18, 25);
+                                                 xpart has frames of (V + 3) & ~3 floats.  (_grouped twins of all three: f2.py, f2v.py)
 
 The TRAINING block-level nodes (unit_gcn / MultiScale_TemporalConv / TCN_GCN_unit / st_gcn) stay ``autograd.Function``s: they update
 BatchNorm running statistics in place, keep ~20 intermediate tensors between forward and backward and take their

@@ -1,9 +1,11 @@
 """GPU-box tool: forward-only throughput (eval mode, no_grad) of the N-UCLA or the NTU-RGB+D model at a few batch sizes -- what
 the inference-only callers (cross-modal attention, ensemble eval, visualisation) see.  Eager launches and HIP-graph replay.
-    python tools/infer_bench.py [--graph ucla|ntu] [--t T] [--ab R] [batch ...]     (default ucla, T = 64, batches 1 16 256)
---graph ntu: 25 joints, 2 persons (a batch of B clips is 2B clip-persons).
-Batches of at most TAMGCN_F2_MAX_CLIPS clips (ucla) / TAMGCN_F2V_MAX_FRAMES clip-persons x frames (ntu) take the small-batch
-kernel family (tam_gcn_amd/f2.py, f2v.py); TAMGCN_F2=0 puts them on the general eval path for comparison.
+    python tools/infer_bench.py [--graph ucla|ntu|coco|openpose] [--t T] [--ab R] [batch ...]     (default ucla, T = 64, batches 1 16 256)
+--graph ntu: 25 joints, 2 persons (a batch of B clips is 2B clip-persons); coco: 17 joints, 1 person; openpose: 18 joints, 2
+persons (the skeletons a pose estimator hands over: graph.coco, graph.openpose).
+Batches of at most TAMGCN_F2_MAX_CLIPS clips (ucla) / TAMGCN_F2V_MAX_FRAMES (ntu) / TAMGCN_F2J_MAX_FRAMES (coco, openpose)
+clip-persons x frames take the small-batch kernel family (tam_gcn_amd/f2.py, f2v.py); TAMGCN_F2=0 puts them on the general eval
+path for comparison.
 --ab R: the family against the general path of the same process, alternating, R timings each (median [min .. max]); the
 family is forced on whatever the routing bound says (that bound is what this mode is for).
 --ensemble G [--ab R]: a G-stream ensemble (joint, bone, motion, bone-motion, ... models of one architecture, fused scores) for
@@ -36,6 +38,14 @@ while args and args[0].startswith('--'):
 if graph == 'ntu':
     V, P = 25, 2
     m = Model(num_class=60, num_point=25, num_person=2, graph='graph.ntu_rgb_d.Graph', graph_args=dict(labeling_mode='spatial'))
+elif graph == 'coco':
+    V, P = 17, 1
+    m = Model(num_class=10, num_point=17, num_person=1, graph='tam_gcn_amd.graph.coco.Graph', graph_args=dict(labeling_mode='spatial'))
+elif graph == 'openpose':
+    V, P = 18, 2
+    m = Model(num_class=12, num_point=18, num_person=2, graph='tam_gcn_amd.graph.openpose.Graph', graph_args=dict(labeling_mode='spatial'))
+elif graph != 'ucla':
+    sys.exit(__doc__)
 else:
     V, P = 20, 1
     m = Model(num_class=10, num_point=20, num_person=1, graph='graph.ucla.Graph', graph_args=dict(labeling_mode='spatial'))
@@ -155,6 +165,9 @@ for B in ([int(v) for v in args] or (1, 16, 256)):
             if graph == 'ntu':
                 from tam_gcn_amd import f2v
                 f2v.F2V_MAX_FRAMES = 1 << 40
+            elif graph in ('coco', 'openpose'):
+                from tam_gcn_amd import f2v
+                f2v.F2J_MAX_FRAMES = 1 << 40
             else:
                 from tam_gcn_amd import f2
                 f2.F2_MAX_CLIPS = 1 << 40
