@@ -616,6 +616,40 @@ int tamgcn_f2v_gcn_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream
 int tamgcn_f2v_gemm_grouped(const tamgcn_f2_gemm_desc* d, int groups, void* stream);
 int tamgcn_f2v_tcn_grouped(const tamgcn_f2_tcn_desc* d, int groups, void* stream);
 
+/* ---- f2s: the eval-mode st_gcn block of ST-GCN (reference models/stgcn.py:56-64, :75-99) for small batches: TWO launches per
+ * block (tam_gcn_amd/csrc/f2s.hip, tam_gcn_amd/f2s.py).  The topology is static and shared by all samples and both BatchNorms
+ * fold into the neighbouring weights -- the CALLER folds (bn(y) = s y + t, s = gamma / sqrt(var + eps), t = beta - mean s):
+ *   _f2s_gcn  h[n,c,t,w] = relu( sum_k sum_ci wg[k][c][ci] * ( sum_v x[n,ci,t,v] * Ae[k][v][w] ) + bg[c][w] )
+ *             x (N, Cin, T, V) contiguous, N counting clip-persons;  Ae [K][V][V] = A * edge_importance;  wg [K][Cout][Cin] =
+ *             s1[c] * gcn.conv.weight[k*Cout + c][ci];  bg [Cout][V] -- a TABLE over the joints, because the conv bias is added
+ *             before the joint contraction:  bg[c][w] = s1[c] * sum_k b[k*Cout + c] * sum_v Ae[k][v][w] + t1[c]  (s1, t1 =
+ *             tcn.0);  h (N, Cout, T, V) contiguous.  (The kernel contracts the channels first, then the joints.)
+ *   _f2s_tcn  out[n,c,tau,v] = relu( sum_tap sum_c' wt[c][c'][tap] * h[n,c', tau*stride - (KT-1)/2 + tap, v] + bt[c] + res )
+ *             frames outside [0, T) read as zero;  out (N, Cout, T2, V) contiguous, T2 = (T - 1) / stride + 1;  wt [Cout][Cout][KT]
+ *             (tap innermost: tcn.2.weight scaled by s2[c]), bt [Cout] = s2 b + t2 (s2, t2 = tcn.3);
+ *             res (res_mode): 0 nothing | 1 x[n,c,tau,v] (stride 1, Cin == Cout) |
+ *                             2 sum_ci wr[c][ci] * x[n,ci,tau*stride,v] + br[c]  (residual conv + BatchNorm folded, wr [Cout][Cin])
+ * Geometry: 2 <= V <= 32, 1 <= K <= 3, 1 <= Cin <= 256, Cout % 16 == 0 and 16 <= Cout <= 256, KT == 9, stride 1 | 2, N <= 65535;
+ * anything else is refused on the host before any HIP call.  tamgcn_f2s_supported answers 1 | 0 for a geometry without touching
+ * the device.  v_mfma_f32_16x16x4_f32 (exact fp32), fixed summation order (two runs are bit-equal), no atomics; nothing is read
+ * or written outside the arrays as dimensioned above, whatever their alignment (4 bytes suffice; 16-byte aligned weights whose
+ * rows are a multiple of 4 floats are read in 16-byte pieces).
+ * Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed. */
+typedef struct tamgcn_f2s_gcn_desc {
+    int N, Cin, Cout, T, V, K;
+    const float* x; const float* Ae; const float* wg; const float* bg;
+    float* h;
+} tamgcn_f2s_gcn_desc;
+typedef struct tamgcn_f2s_tcn_desc {
+    int N, Cin, Cout, T, V, KT, stride, res_mode;    /* Cin: channels of x (res_mode 2; otherwise ignored) */
+    const float* h; const float* wt; const float* bt;
+    const float* x; const float* wr; const float* br;    /* x: res_mode 1 | 2, wr / br: res_mode 2; else NULL */
+    float* out;
+} tamgcn_f2s_tcn_desc;
+int tamgcn_f2s_supported(int V, int K, int Cin, int Cout, int KT, int stride);
+int tamgcn_f2s_gcn(const tamgcn_f2s_gcn_desc* d, void* stream);
+int tamgcn_f2s_tcn(const tamgcn_f2s_tcn_desc* d, void* stream);
+
 /* Stem and head of such an ensemble, one launch each:
  *   _stem_streams_eval  x (N, C, T, V, M) joint clips -> out (G*N*M, C, T, V), row g*N*M + n*M + m = model g's eval-mode data_bn
  *                       (coef [G][3][J], J = C*V*M, each in _stem_apply's layout: c1 at [0][j], c0 at [2][j]) of stream modes[g]

@@ -96,6 +96,16 @@ class F2TcnDesc(C.Structure):
                [(k, C.c_void_p) for k in ('sp', 'tp', 'x', 'wr', 'br', 'out', 'xpart')]
 
 
+class F2sGcnDesc(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ('N', 'Cin', 'Cout', 'T', 'V', 'K')] + \
+               [(k, C.c_void_p) for k in ('x', 'Ae', 'wg', 'bg', 'h')]
+
+
+class F2sTcnDesc(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ('N', 'Cin', 'Cout', 'T', 'V', 'KT', 'stride', 'res_mode')] + \
+               [(k, C.c_void_p) for k in ('h', 'wt', 'bt', 'x', 'wr', 'br', 'out')]
+
+
 class OptimDesc(C.Structure):
     _fields_ = [('n', C.c_longlong),
                 ('p', C.c_void_p), ('g', C.c_void_p), ('s0', C.c_void_p), ('s1', C.c_void_p),
@@ -198,6 +208,9 @@ SIGNATURES = {
     'tamgcn_f2v_gcn_grouped': (_i, [C.POINTER(F2GcnDesc), _i, _p]),
     'tamgcn_f2v_gemm_grouped': (_i, [C.POINTER(F2GemmDesc), _i, _p]),
     'tamgcn_f2v_tcn_grouped': (_i, [C.POINTER(F2TcnDesc), _i, _p]),
+    'tamgcn_f2s_supported': (_i, [_i, _i, _i, _i, _i, _i]),
+    'tamgcn_f2s_gcn': (_i, [C.POINTER(F2sGcnDesc), _p]),
+    'tamgcn_f2s_tcn': (_i, [C.POINTER(F2sTcnDesc), _p]),
     'tamgcn_stem_streams_eval': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     'tamgcn_head_fc_grouped': (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     'tamgcn_optim_step': (_i, [C.POINTER(OptimDesc), _p]),

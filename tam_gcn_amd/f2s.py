@@ -1,0 +1,184 @@
+"""Small-batch eval-mode engine for ST-GCN (models.stgcn.Model): every st_gcn block as TWO launches of the f2s kernel family
+(csrc/f2s.hip: tamgcn_f2s_gcn, tamgcn_f2s_tcn; include/tamgcn.h "f2s") instead of the ~10 training-size launches of the
+general eval path (functional.StGcnFn: four zero fills, A * importance, its transpose, an E tensor that repeats one matrix for
+every sample and channel, the CTRGC forward, the k x 1 conv, the residual conv, add_act).
+
+In eval mode the topology is static and both BatchNorms fold into the neighbouring weights, HERE, once per parameter state
+(f2.FusedEval's state key: a cheap version check per call re-folds after an optimiser step, load_state_dict, an in-place
+edge_importance update or a train-mode forward):
+
+    gcn   h = relu( sum_k (Wg_k x) Ae_k + bg )      Ae = A * edge_importance;  Wg = s1 * gcn.conv.weight;
+                                                     bg[c][w] = s1[c] sum_k b[k Cout + c] sum_v Ae[k][v][w] + t1[c]
+                                                     (the conv bias is added BEFORE the joint contraction, so it reaches joint w
+                                                     through the column sums of Ae: a (Cout, V) table, not a (Cout) vector)
+    tcn   out = relu( Wt * h + bt + res )            Wt = s2 * tcn.2.weight, bt = s2 b + t2;  res = 0 | x | Wr x[::stride] + br
+
+    eng = FusedEvalST(model)          # model.eval(); any graph of 2..32 joints, 1..3 subsets
+    logits = eng(x)                   # x (N, C, T, V, M) or (N, T, V*C) on the GPU, under torch.no_grad()
+
+`stgcn.Model.forward` / `extract_feature` route here by themselves in eval mode without autograd for batches of at most
+F2S_MAX_FRAMES clip-persons x frames (N * M * T; TAMGCN_F2S_MAX_FRAMES overrides it, TAMGCN_F2=0 switches the routing off;
+measured: profiles/f2s_infer_bench.txt).  Limits: temporal kernel 9 only, V <= 32, K <= 3, Cout % 16 == 0; there is no
+grouped (multi-stream) pass.  No CPU path, no fallback inside: `Unsupported` is raised before anything is launched."""
+import ctypes as C
+import os
+from typing import List
+
+import torch
+from torch import Tensor
+
+from . import _lib
+from . import functional as Fn
+from .f2 import FusedEval, Unsupported, enabled, _affine, _fold, _opt
+
+__all__ = ['FusedEvalST', 'Unsupported', 'F2S_MAX_FRAMES', 'enabled']
+
+# N*M*T up to which stgcn.Model.forward routes here: the largest measured clip-persons x frames at which the family beats the
+# general eval path both eager and under graph replay at every measured joint count (17, 18, 20, 25); it loses at 1200 (25
+# joints), 1664 (20) and 2048 (17)  (profiles/f2s_infer_bench.txt)
+F2S_MAX_FRAMES = int(os.environ.get('TAMGCN_F2S_MAX_FRAMES', '1024'))
+KT = 9                                                                     # the temporal kernel the kernels are built for
+
+
+class _BlockST:
+    """Folded tensors and geometry of one st_gcn block; Ae (K, V, V) = A * edge_importance of that block."""
+
+    def __init__(self, blk, Ae, device):
+        conv = blk.gcn.conv
+        K, V = int(Ae.shape[0]), int(Ae.shape[-1])
+        Cin, Cout = blk.in_channels, blk.out_channels
+        tconv = blk.tcn[2]
+        kt, stride = int(tconv.kernel_size[0]), int(tconv.stride[0])
+        if kt != KT:
+            raise Unsupported(f'st_gcn with temporal kernel size {kt} (the f2s kernels are built for {KT})')
+        if Cout % 16:
+            raise Unsupported(f'st_gcn({Cin}, {Cout}): output channels must be a multiple of 16')
+        if V > 32:
+            raise Unsupported(f'{V} joints (the f2s kernels serve V <= 32)')
+        if K > 3:
+            raise Unsupported(f'{K} subsets (the f2s kernels serve K <= 3)')
+        if blk.gcn.kernel_size != K or blk.gcn._cfg != (1, 1, 1, 0) or conv.out_channels != K * Cout:
+            raise Unsupported('ConvTemporalGraphical other than the 1 x 1 form over the graph\'s subsets')
+        if not _lib.load().tamgcn_f2s_supported(V, K, Cin, Cout, kt, stride):
+            raise Unsupported(f'st_gcn({Cin}, {Cout}, stride {stride}) on {V} joints, {K} subsets')
+        Ae = Ae.detach().to(device=device, dtype=torch.float32)
+        s1, t1 = _affine(Fn.BN(blk.tcn[0]))
+        w = conv.weight.detach().reshape(K, Cout, Cin)
+        b = conv.bias.detach().reshape(K, Cout) if conv.bias is not None else w.new_zeros(K, Cout)
+        self.Ae = Ae.contiguous()
+        self.Wg = (w * s1[None, :, None]).contiguous()
+        self.bg = (s1[:, None] * (b.t() @ Ae.sum(1)) + t1[:, None]).contiguous()             # (Cout, V)
+        self.Wt, self.bt = _fold(tconv.weight.reshape(Cout, Cout * kt), tconv.bias, Fn.BN(blk.tcn[3]))
+        self.rmode = {'zero': 0, 'identity': 1, 'conv': 2}[blk._rmode]
+        self.Wr = self.br = None
+        if self.rmode == 2:
+            r = blk.residual
+            if r[0].kernel_size != (1, 1):
+                raise Unsupported('residual conv other than 1 x 1')
+            self.Wr, self.br = _fold(r[0].weight.reshape(Cout, Cin), r[0].bias, Fn.BN(r[1]))
+        self.Cin, self.Cout, self.K, self.V, self.stride = Cin, Cout, K, V, stride
+        none = self.bt.new_empty(0)
+        # the registered op's arguments: tensors in this order (an absent one is an empty tensor), geometry as integers
+        self.params = [self.Ae, self.Wg, self.bg, self.Wt, self.bt, none if self.Wr is None else self.Wr, none if self.br is None else self.br]
+        self.geom = [K, kt, stride, self.rmode]
+
+
+class FusedEvalST(FusedEval):
+    """f2.FusedEval's state key and re-fold on models.stgcn.Model: the blocks are model.st_gcn_networks, the operator is
+    tamgcn::st_gcn_eval, the head reads fcn's weight as (num_class, 256)."""
+    FAMILY = 'f2s'
+
+    def __init__(self, model):
+        if model.training:
+            raise ValueError('FusedEvalST: put the model in eval() mode first')
+        if not hasattr(model, 'st_gcn_networks') or not hasattr(model, 'edge_importance'):
+            raise Unsupported('FusedEvalST serves models.stgcn.Model')
+        self.V = model.num_point
+        super().__init__(model)
+
+    def _packed(self, device):
+        key = self._state_key()
+        if self._blocks is None or key != self._key:
+            m = self.model
+            with torch.no_grad():
+                self._blocks = [_BlockST(blk, m.A * imp, device) for blk, imp in zip(m.st_gcn_networks, m.edge_importance)]
+            self._key = self._state_key()
+        return self._blocks
+
+    def _block(self, b, x, st=None, xpart=None, want_xpart=False):
+        return torch.ops.tamgcn.st_gcn_eval(x, b.params, b.geom)
+
+    def blocks(self, x):
+        """(N, C, T, V, M) or (N, T, V*C) -> (N*M, 256, T/4, V), N, M   (reference models/stgcn.py:172-189)"""
+        m = self.model
+        if torch.is_grad_enabled() and any(p.requires_grad for p in m.parameters()):
+            raise RuntimeError('FusedEvalST is an inference path: call it under torch.no_grad()')
+        if m.training:
+            raise RuntimeError('FusedEvalST: the model went back to train() mode')
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise RuntimeError('FusedEvalST: expected a float32 HIP (cuda) tensor; there is no CPU path')
+        if x.dim() == 3:
+            N, T, VC = x.shape
+            x = x.view(N, T, m.num_point, -1).permute(0, 3, 1, 2).contiguous().unsqueeze(-1)
+        N, C_, T, V, M = x.shape
+        if V != self.V:
+            raise Unsupported(f'{V} joints (the model has {self.V})')
+        blocks = self._packed(x.device)
+        h = Fn.StemFn.run(m.data_bn, x.contiguous(), m.data_bn.weight, m.data_bn.bias)
+        for b in blocks:
+            h = self._block(b, h)
+        return h, N, M
+
+    def __call__(self, x):
+        h, N, M = self.blocks(x)
+        m = self.model                                         # eval mode: drop_out is the identity
+        return torch.ops.tamgcn.head(h, m.fcn.weight.view(m.fcn.weight.size(0), -1), m.fcn.bias, M)
+
+    forward = __call__
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The block as a registered operator: pure tensors in, a pure tensor out, a fake implementation for tracing / export.
+#   params: Ae [K][V][V] (A * edge_importance), Wg [K][Cout][Cin], bg [Cout][V], Wt [Cout][Cout*KT] (tap innermost), bt [Cout],
+#           Wr [Cout][Cin], br [Cout] (the residual conv, folded; both empty if there is none)      -- include/tamgcn.h "f2s"
+#   geom:   K, KT, stride, block residual (0 none | 1 identity | 2 conv)
+# x (N, Cin, T, V) -> out (N, Cout, (T - 1) // stride + 1, V).  Two launches.
+# ----------------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op('tamgcn::st_gcn_eval', mutates_args=())
+def st_gcn_eval(x: Tensor, params: List[Tensor], geom: List[int]) -> Tensor:
+    name = 'tamgcn::st_gcn_eval'
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise RuntimeError(f'{name}: expected a float32 HIP (cuda) tensor; there is no CPU path')
+    if x.dim() != 4 or len(params) != 7 or len(geom) != 4:
+        raise RuntimeError(f'{name}: expected x (N, C, T, V), 7 tensors and 4 integers, got {tuple(x.shape)}, {len(params)}, {len(geom)}')
+    lib = _lib.load()
+    K, kt, stride, rmode = geom
+    Ae, Wg, bg, Wt, bt, Wr, br = (t.contiguous() for t in params)
+    N, Cin, T, V = x.shape
+    Cout = bt.shape[0]
+    if not (2 <= V <= 32 and 1 <= K <= 3 and 1 <= Cin <= 256 and 16 <= Cout <= 256 and Cout % 16 == 0 and kt == KT and stride in (1, 2)):
+        raise RuntimeError(f'{name}: V={V} K={K} Cin={Cin} Cout={Cout} KT={kt} stride={stride} is outside the f2s kernels '
+                           '(2 <= V <= 32, K <= 3, Cin <= 256, Cout % 16 == 0, Cout <= 256, KT == 9, stride 1 | 2)')
+    if tuple(Ae.shape) != (K, V, V) or tuple(Wg.shape) != (K, Cout, Cin) or tuple(bg.shape) != (Cout, V) or Wt.numel() != Cout * Cout * kt:
+        raise RuntimeError(f'{name}: parameter shapes {[tuple(t.shape) for t in params]} do not fit x {tuple(x.shape)}, geom {list(geom)}')
+    if rmode == 2 and (tuple(Wr.shape) != (Cout, Cin) or br.numel() != Cout) or rmode == 1 and (Cin != Cout or stride != 1):
+        raise RuntimeError(f'{name}: residual mode {rmode} does not fit Cin={Cin} Cout={Cout} stride={stride}')
+    x = x.contiguous()
+    dev = x.device
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    h = torch.empty(N, Cout, T, V, device=dev)
+    g = _lib.F2sGcnDesc(N=N, Cin=Cin, Cout=Cout, T=T, V=V, K=K, x=x.data_ptr(), Ae=Ae.data_ptr(), wg=Wg.data_ptr(), bg=bg.data_ptr(),
+                        h=h.data_ptr())
+    _lib.check(lib.tamgcn_f2s_gcn(C.byref(g), st), 'tamgcn_f2s_gcn')
+    out = torch.empty(N, Cout, (T - 1) // stride + 1, V, device=dev)
+    t = _lib.F2sTcnDesc(N=N, Cin=Cin, Cout=Cout, T=T, V=V, KT=kt, stride=stride, res_mode=rmode, h=h.data_ptr(), wt=Wt.data_ptr(),
+                        bt=bt.data_ptr(), x=x.data_ptr() if rmode else None, wr=_opt(Wr) if rmode == 2 else None,
+                        br=_opt(br) if rmode == 2 else None, out=out.data_ptr())
+    _lib.check(lib.tamgcn_f2s_tcn(C.byref(t), st), 'tamgcn_f2s_tcn')
+    return out
+
+
+@st_gcn_eval.register_fake
+def _(x, params, geom):
+    N, _, T, V = x.shape
+    return x.new_empty(N, params[4].shape[0], (T - 1) // geom[2] + 1, V)

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import functional as Fn
-from .ctrgcn import import_class, _require_hip
+from .ctrgcn import import_class, _require_hip, Model as _CtrModel
 
 
 def conv_init(conv):
@@ -140,8 +140,25 @@ class Model(nn.Module):
             x, _ = gcn(x, self.A * importance)
         return x, N, M
 
+    def _f2s(self, x):
+        """The small-batch eval engine (tam_gcn_amd.f2s) if this call is one for it, else None: eval mode, no autograd, fp32 on
+        the device, no hooks, at most F2S_MAX_FRAMES clip-persons x frames."""
+        if self.training or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32:
+            return None
+        from .. import f2s
+        frames = x.shape[0] * x.shape[4] * x.shape[2] if x.dim() == 5 else x.shape[0] * x.shape[1]
+        if not f2s.enabled() or frames > f2s.F2S_MAX_FRAMES:
+            return None
+        return self._small_batch_engine(x, '_tamgcn_f2s', f2s.FusedEvalST)
+
+    _small_batch_engine = _CtrModel._small_batch_engine      # hooks check, per-model cache slot, False after Unsupported
+
     def forward(self, x):
-        x, N, M = self._blocks(_require_hip(x))
+        x = _require_hip(x)
+        eng = self._f2s(x)
+        if eng is not None:
+            return eng(x)
+        x, N, M = self._blocks(x)
         if isinstance(self.drop_out, nn.Dropout):
             x = x.view(N, M, x.size(1), -1).mean(3).mean(1)
             x = self.drop_out(x)
@@ -149,7 +166,9 @@ class Model(nn.Module):
         return torch.ops.tamgcn.head(x, self.fcn.weight.view(self.fcn.weight.size(0), -1), self.fcn.bias, M)   # :193-198
 
     def extract_feature(self, x):
-        x, N, M = self._blocks(_require_hip(x))
+        x = _require_hip(x)
+        eng = self._f2s(x)
+        x, N, M = eng.blocks(x) if eng is not None else self._blocks(x)
         _, c, t, v = x.size()
         feature = x.view(N, M, c, t, v).permute(0, 2, 3, 4, 1)
         o = torch.ops.tamgcn.pointwise_conv(x, self.fcn.weight, self.fcn.bias)

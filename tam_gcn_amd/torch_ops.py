@@ -19,6 +19,8 @@ backward is itself a registered op:
                                                  has frames of 28 floats
     tamgcn::tcn_gcn_unit_eval_vj(x, xpart, params, geom) -> (out, xpart)    the same for any joint count of f2v.JOINTS (17, 18, 25);
                                                  xpart has frames of (V + 3) & ~3 floats.  (_grouped twins of all three: f2.py, f2v.py)
+    tamgcn::st_gcn_eval(x, params, geom) -> out  the whole eval-mode st_gcn block of ST-GCN (models/stgcn.py:67-99) for small
+                                                 batches, both BatchNorms folded, two launches; registered by tam_gcn_amd/f2s.py
 
 The TRAINING block-level nodes (unit_gcn / MultiScale_TemporalConv / TCN_GCN_unit / st_gcn) stay ``autograd.Function``s: they update
 BatchNorm running statistics in place, keep ~20 intermediate tensors between forward and backward and take their

@@ -1,6 +1,7 @@
 """GPU-box tool: forward-only throughput (eval mode, no_grad) of the N-UCLA or the NTU-RGB+D model at a few batch sizes -- what
 the inference-only callers (cross-modal attention, ensemble eval, visualisation) see.  Eager launches and HIP-graph replay.
-    python tools/infer_bench.py [--graph ucla|ntu|coco|openpose] [--t T] [--ab R] [batch ...]     (default ucla, T = 64, batches 1 16 256)
+    python tools/infer_bench.py [--model ctrgcn|stgcn] [--graph ucla|ntu|coco|openpose] [--t T] [--ab R] [batch ...]     (default ctrgcn, ucla, T = 64, batches 1 16 256)
+--model stgcn: models.stgcn.Model on the same graphs; its small-batch family is tam_gcn_amd/f2s.py (TAMGCN_F2S_MAX_FRAMES).
 --graph ntu: 25 joints, 2 persons (a batch of B clips is 2B clip-persons); coco: 17 joints, 1 person; openpose: 18 joints, 2
 persons (the skeletons a pose estimator hands over: graph.coco, graph.openpose).
 Batches of at most TAMGCN_F2_MAX_CLIPS clips (ucla) / TAMGCN_F2V_MAX_FRAMES (ntu) / TAMGCN_F2J_MAX_FRAMES (coco, openpose)
@@ -22,7 +23,7 @@ from tam_gcn_amd.models.ctrgcn import Model
 dev = torch.device('cuda:0')
 torch.manual_seed(0)
 args = sys.argv[1:]
-T, graph, ab, ens_g = 64, 'ucla', 0, 0
+T, graph, ab, ens_g, model = 64, 'ucla', 0, 0, 'ctrgcn'
 while args and args[0].startswith('--'):
     if args[0] == '--t':
         T = int(args[1])
@@ -30,11 +31,17 @@ while args and args[0].startswith('--'):
         graph = args[1]
     elif args[0] == '--ab':
         ab = int(args[1])
+    elif args[0] == '--model' and args[1] in ('ctrgcn', 'stgcn'):
+        model = args[1]
     elif args[0] == '--ensemble':
         ens_g = int(args[1])
     else:
         sys.exit(__doc__)
     args = args[2:]
+if model == 'stgcn':
+    if ens_g:
+        sys.exit('--ensemble: there is no grouped pass for ST-GCN')
+    from tam_gcn_amd.models.stgcn import Model
 if graph == 'ntu':
     V, P = 25, 2
     m = Model(num_class=60, num_point=25, num_person=2, graph='graph.ntu_rgb_d.Graph', graph_args=dict(labeling_mode='spatial'))
@@ -157,12 +164,15 @@ def ensemble_bench(G, batches, R):
 if ens_g:
     ensemble_bench(ens_g, [int(v) for v in args] or (1, 4), ab or 7)
     sys.exit(0)
-print(f'graph = {graph} (V = {V}, M = {P}), T = {T}, TAMGCN_F2 = {os.environ.get("TAMGCN_F2", "1")}', flush=True)
+print(('model = stgcn, ' if model == 'stgcn' else '') + f'graph = {graph} (V = {V}, M = {P}), T = {T}, TAMGCN_F2 = {os.environ.get("TAMGCN_F2", "1")}', flush=True)
 for B in ([int(v) for v in args] or (1, 16, 256)):
     x = torch.rand(B, 3, T, V, P, device=dev) * 2 - 1
     with torch.no_grad():
         if ab:
-            if graph == 'ntu':
+            if model == 'stgcn':
+                from tam_gcn_amd import f2s
+                f2s.F2S_MAX_FRAMES = 1 << 40
+            elif graph == 'ntu':
                 from tam_gcn_amd import f2v
                 f2v.F2V_MAX_FRAMES = 1 << 40
             elif graph in ('coco', 'openpose'):
