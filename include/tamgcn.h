@@ -650,6 +650,52 @@ int tamgcn_f2s_supported(int V, int K, int Cin, int Cout, int KT, int stride);
 int tamgcn_f2s_gcn(const tamgcn_f2s_gcn_desc* d, void* stream);
 int tamgcn_f2s_tcn(const tamgcn_f2s_tcn_desc* d, void* stream);
 
+/* ---- f2s backward: the DATA gradient of that block (tam_gcn_amd/csrc/f2s_bwd.hip), again two launches, for gradient saliency
+ * (tam_gcn_amd/saliency.py; reference tools/train_stgcn_group.py:264-356).  In eval mode the block is piecewise linear in x; the
+ * two ReLU masks are read from the forward's own h and out, strictly (> 0, as torch).  No weight gradient; x, the biases and bg
+ * do not enter.  With s = stride, T2 = (T - 1) / s + 1 and gout (N, Cout, T2, V) the gradient of the block's output:
+ *   gz[n,c,tau,v]  = gout[n,c,tau,v] * [out[n,c,tau,v] > 0]                                    (never materialised)
+ *   _f2s_tcn_bwd   dh[n,c',t,v] = [h[n,c',t,v] > 0] * sum_c sum_tap wtb[c'][c][tap] * gz[n,c,tau,v],  tau = (t + (KT-1)/2 - tap) / s;
+ *                  terms with a non-integral tau or tau outside [0, T2) are zero.  wtb [Cout][Cout][KT] = wt[c][c'][tap] transposed
+ *                  in its two channel indices (tap innermost, NOT mirrored: the mirror is in tau).  dh (N, Cout, T, V).
+ *   _f2s_gcn_bwd   dx[n,ci,t,v] = sum_k sum_c wgb[k][ci][c] * ( sum_w Ae[k][v][w] * dh[n,c,t,w] ) + res
+ *                  Ae [K][V][V]: the forward's array;  wgb [K][Cin][Cout] = wg[k][c][ci];  dx (N, Cin, T, V);
+ *                  res (res_mode): 0 nothing | 1 gz[n,ci,t,v] (stride 1, Cin == Cout) |
+ *                                  2 [t % s == 0] * sum_c wrb[ci][c] * gz[n,c,t/s,v],  wrb [Cin][Cout] = wr[c][ci]
+ *                  gout / out: res_mode 1 | 2, wrb: res_mode 2; else NULL.  Rows ci >= Cin of a 16-row tile are neither read from
+ *                  the weights nor stored.
+ * Geometry, alignment, determinism and the refusal on the host: as the forward's.
+ * Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed. */
+typedef struct tamgcn_f2s_tcn_bwd_desc {
+    int N, Cout, T, V, KT, stride;                   /* T: frames of h and dh (the block's input frames) */
+    const float* gout; const float* out; const float* h; const float* wtb;
+    float* dh;
+} tamgcn_f2s_tcn_bwd_desc;
+typedef struct tamgcn_f2s_gcn_bwd_desc {
+    int N, Cin, Cout, T, V, K, stride, res_mode;
+    const float* dh; const float* Ae; const float* wgb;
+    const float* gout; const float* out; const float* wrb;
+    float* dx;
+} tamgcn_f2s_gcn_bwd_desc;
+int tamgcn_f2s_tcn_bwd(const tamgcn_f2s_tcn_bwd_desc* d, void* stream);
+int tamgcn_f2s_gcn_bwd(const tamgcn_f2s_gcn_bwd_desc* d, void* stream);
+
+/* ---- saliency (tam_gcn_amd/csrc/saliency.hip): what follows the backward chain of a saliency pass.
+ *   _saliency_joints      dx0 (N*M, C, T, V): the first block's dx;  coef: the eval-mode data_bn coefficients in _stem_apply's layout,
+ *                         of which only c1 (the first J = C*V*M floats) is read.  dxin[n,c,t,v,m] = c1[(m V + v) C + c] *
+ *                         dx0[n M + m, c, t, v] is the gradient with respect to the model's input;  sal[n][v] = sum_{m,c,t} |dxin|,
+ *                         (N, V), summed in a fixed order (two launches are bit-equal).  dxin: NULL | (N, C, T, V, M) out.
+ *   _saliency_accumulate  adds one batch to an on-device state: for i = 0 .. N-1 in order, with k = labels[i] (int64): a label
+ *                         outside [0, num_class) or a class with count[k] >= per_class is skipped; else count[k] += 1 and, for
+ *                         every part p, sum[k][p] += mean over the joints j of part p of sal[i][j] (taken in fp64).  Part p's
+ *                         joints are part_joints[part_off[p] .. part_off[p+1]) (int32, on the device; part_off is trusted, a
+ *                         joint outside [0, V) is skipped).  count int32 [num_class], sum fp64 [num_class][P].  One workgroup,
+ *                         N <= 4096, P <= 256.  No host synchronisation.
+ * Added in ABI 401 without a version bump: new entry points. */
+int tamgcn_saliency_joints(const float* dx0, const float* coef, int N, int C, int T, int V, int M, float* sal, float* dxin, void* stream);
+int tamgcn_saliency_accumulate(const float* sal, const long long* labels, int N, int V, const int* part_off, const int* part_joints,
+                               int P, int num_class, int per_class, int* count, double* sum, void* stream);
+
 /* Stem and head of such an ensemble, one launch each:
  *   _stem_streams_eval  x (N, C, T, V, M) joint clips -> out (G*N*M, C, T, V), row g*N*M + n*M + m = model g's eval-mode data_bn
  *                       (coef [G][3][J], J = C*V*M, each in _stem_apply's layout: c1 at [0][j], c0 at [2][j]) of stream modes[g]

@@ -106,6 +106,16 @@ class F2sTcnDesc(C.Structure):
                [(k, C.c_void_p) for k in ('h', 'wt', 'bt', 'x', 'wr', 'br', 'out')]
 
 
+class F2sTcnBwdDesc(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ('N', 'Cout', 'T', 'V', 'KT', 'stride')] + \
+               [(k, C.c_void_p) for k in ('gout', 'out', 'h', 'wtb', 'dh')]
+
+
+class F2sGcnBwdDesc(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ('N', 'Cin', 'Cout', 'T', 'V', 'K', 'stride', 'res_mode')] + \
+               [(k, C.c_void_p) for k in ('dh', 'Ae', 'wgb', 'gout', 'out', 'wrb', 'dx')]
+
+
 class OptimDesc(C.Structure):
     _fields_ = [('n', C.c_longlong),
                 ('p', C.c_void_p), ('g', C.c_void_p), ('s0', C.c_void_p), ('s1', C.c_void_p),
@@ -211,6 +221,10 @@ SIGNATURES = {
     'tamgcn_f2s_supported': (_i, [_i, _i, _i, _i, _i, _i]),
     'tamgcn_f2s_gcn': (_i, [C.POINTER(F2sGcnDesc), _p]),
     'tamgcn_f2s_tcn': (_i, [C.POINTER(F2sTcnDesc), _p]),
+    'tamgcn_f2s_tcn_bwd': (_i, [C.POINTER(F2sTcnBwdDesc), _p]),
+    'tamgcn_f2s_gcn_bwd': (_i, [C.POINTER(F2sGcnBwdDesc), _p]),
+    'tamgcn_saliency_joints': (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    'tamgcn_saliency_accumulate': (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p]),
     'tamgcn_stem_streams_eval': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     'tamgcn_head_fc_grouped': (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     'tamgcn_optim_step': (_i, [C.POINTER(OptimDesc), _p]),

@@ -19,10 +19,25 @@ edge_importance update or a train-mode forward):
 `stgcn.Model.forward` / `extract_feature` route here by themselves in eval mode without autograd for batches of at most
 F2S_MAX_FRAMES clip-persons x frames (N * M * T; TAMGCN_F2S_MAX_FRAMES overrides it, TAMGCN_F2=0 switches the routing off;
 measured: profiles/f2s_infer_bench.txt).  Limits: temporal kernel 9 only, V <= 32, K <= 3, Cout % 16 == 0; there is no
-grouped (multi-stream) pass.  No CPU path, no fallback inside: `Unsupported` is raised before anything is launched."""
+grouped (multi-stream) pass.  No CPU path, no fallback inside: `Unsupported` is raised before anything is launched.
+
+The same engine serves gradient saliency (tam_gcn_amd.saliency; reference tools/train_stgcn_group.py:264-356).  In eval mode a
+block is piecewise linear in its input with these static folded weights, so its DATA gradient is again two launches
+(csrc/f2s_bwd.hip: tamgcn_f2s_tcn_bwd, tamgcn_f2s_gcn_bwd; include/tamgcn.h "f2s backward"), masked by the two ReLUs as the
+forward's own h and out record them; no weight gradient is computed and no parameter's .grad is touched:
+
+    tcn_bwd   dh = [h > 0] * ( Wt^T (*) gz ),  gz = gout * [out > 0]       Wtb[c'][c][tap] = Wt[c][c'][tap]
+    gcn_bwd   dx = sum_k Wg_k^T (dh Ae_k^T) + res                           Wgb[k][ci][c] = Wg[k][c][ci];  res = 0 | gz | Wrb gz on the
+                                                                            frames t % stride == 0,  Wrb[ci][c] = Wr[c][ci]
+
+The transposed operands are folded with the others, under the same state key and re-fold.  `FusedEvalST.saliency_pass` runs
+stem, 10 x (gcn, tcn) keeping every (out, h), head, the seed (head_fc_bwd, head_pool_bwd), 10 x (tcn_bwd, gcn_bwd) in reverse
+and tamgcn_saliency_joints, all on the current stream without a host synchronisation.  saliency.input_gradient /
+joint_saliency route here for inputs of at most F2S_BWD_MAX_FRAMES clip-persons x frames (TAMGCN_F2S_BWD_MAX_FRAMES overrides
+it; measured: profiles/f2s_saliency_bench.txt)."""
 import ctypes as C
 import os
-from typing import List
+from typing import List, Tuple
 
 import torch
 from torch import Tensor
@@ -31,12 +46,17 @@ from . import _lib
 from . import functional as Fn
 from .f2 import FusedEval, Unsupported, enabled, _affine, _fold, _opt
 
-__all__ = ['FusedEvalST', 'Unsupported', 'F2S_MAX_FRAMES', 'enabled']
+__all__ = ['FusedEvalST', 'Unsupported', 'F2S_MAX_FRAMES', 'F2S_BWD_MAX_FRAMES', 'enabled']
 
 # N*M*T up to which stgcn.Model.forward routes here: the largest measured clip-persons x frames at which the family beats the
 # general eval path both eager and under graph replay at every measured joint count (17, 18, 20, 25); it loses at 1200 (25
 # joints), 1664 (20) and 2048 (17)  (profiles/f2s_infer_bench.txt)
 F2S_MAX_FRAMES = int(os.environ.get('TAMGCN_F2S_MAX_FRAMES', '1024'))
+# N*M*T up to which saliency.input_gradient / joint_saliency take the family's forward + backward chain instead of autograd
+# through the general path: the largest clip-persons x frames measured at every joint count (17, 20, 25) at which the family's
+# median is below the general path's by more than the spread of the alternating repeats at each of them; at 3072 it loses at
+# 20 joints  (profiles/f2s_saliency_bench.txt)
+F2S_BWD_MAX_FRAMES = int(os.environ.get('TAMGCN_F2S_BWD_MAX_FRAMES', '2048'))
 KT = 9                                                                     # the temporal kernel the kernels are built for
 
 
@@ -81,6 +101,11 @@ class _BlockST:
         # the registered op's arguments: tensors in this order (an absent one is an empty tensor), geometry as integers
         self.params = [self.Ae, self.Wg, self.bg, self.Wt, self.bt, none if self.Wr is None else self.Wr, none if self.br is None else self.br]
         self.geom = [K, kt, stride, self.rmode]
+        # the data gradient's operands (tamgcn::st_gcn_eval_bwd): the same weights with the contraction index innermost
+        self.Wtb = self.Wt.view(Cout, Cout, kt).permute(1, 0, 2).contiguous()
+        self.Wgb = self.Wg.permute(0, 2, 1).contiguous()
+        self.Wrb = None if self.Wr is None else self.Wr.t().contiguous()
+        self.bparams = [self.Ae, self.Wgb, self.Wtb, none if self.Wrb is None else self.Wrb]
 
 
 class FusedEvalST(FusedEval):
@@ -136,6 +161,59 @@ class FusedEvalST(FusedEval):
 
     forward = __call__
 
+    def saliency_pass(self, x, labels=None, dlogits=None, trace=None, want_dxin=True):
+        """(sal (N, V), dxin (N, C, T, V, M) | None, logits (N, K)) for x (N, C, T, V, M): the gradient of sum(dlogits * logits) --
+        dlogits (N, K), or one-hot of labels (N) int64, or one-hot of the arg max of the logits (taken on the device) -- with respect
+        to x, and its magnitude summed per joint.  trace: a list that receives, per block in forward order, dict(gout, out, h, dx).
+        Everything runs on the current stream; nothing synchronises with the host."""
+        from . import ops
+        m = self.model
+        if m.training:
+            raise RuntimeError('FusedEvalST: the model went back to train() mode')
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise RuntimeError('FusedEvalST: expected a float32 HIP (cuda) tensor; there is no CPU path')
+        N, C_, T, V, M = x.shape
+        if V != self.V:
+            raise Unsupported(f'{V} joints (the model has {self.V})')
+        with torch.no_grad():
+            blocks = self._packed(x.device)
+            x = x.contiguous()
+            bn = Fn.BN(m.data_bn)
+            J = C_ * V * M
+            if bn.C != J:
+                raise RuntimeError(f'tam_gcn_amd: data_bn has {bn.C} features, input gives {J}')
+            coef, _ = Fn._eval_cached(m.data_bn, 'stem', [bn], lambda: Fn._eval_coefs([(bn, 0)], J, x))
+            a = ops.stem_apply(x, coef)
+            kept = []
+            for b in blocks:
+                a, h = torch.ops.tamgcn.st_gcn_eval_fwd(a, b.params, b.geom)
+                kept.append((a, h))
+            W = m.fcn.weight.detach().view(m.fcn.weight.size(0), -1).contiguous()
+            pooled = ops.head_pool_fwd(a, M)
+            logits = ops.head_fc_fwd(pooled, W, m.fcn.bias.detach().contiguous())
+            if dlogits is None:
+                lab = logits.argmax(1) if labels is None else labels.to(device=x.device, dtype=torch.int64).view(N)
+                dlogits = torch.zeros_like(logits).scatter_(1, lab.view(N, 1), 1.0)
+            elif tuple(dlogits.shape) != tuple(logits.shape):
+                raise ValueError(f'dlogits must be {tuple(logits.shape)}, got {tuple(dlogits.shape)}')
+            dlogits = dlogits.to(device=x.device, dtype=torch.float32).contiguous()
+            _, _, dpooled = ops.head_fc_bwd(dlogits, pooled, W)
+            g = ops.head_pool_bwd(dpooled, M, a.shape[2], V)
+            steps = [None] * len(blocks)
+            for i in range(len(blocks) - 1, -1, -1):
+                out, h = kept[i]
+                dx = torch.ops.tamgcn.st_gcn_eval_bwd(g, out, h, blocks[i].bparams, blocks[i].geom)
+                steps[i] = dict(gout=g, out=out, h=h, dx=dx)
+                g = dx
+            if trace is not None:
+                trace.extend(steps)
+            sal = torch.empty(N, V, device=x.device)
+            dxin = torch.empty_like(x) if want_dxin else None
+            _lib.check(_lib.load().tamgcn_saliency_joints(g.data_ptr(), coef.data_ptr(), N, C_, T, V, M, sal.data_ptr(),
+                                                       None if dxin is None else dxin.data_ptr(),
+                                                       C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), 'tamgcn_saliency_joints')
+        return sal, dxin, logits
+
 
 # ----------------------------------------------------------------------------------------------------------------------
 # The block as a registered operator: pure tensors in, a pure tensor out, a fake implementation for tracing / export.
@@ -144,9 +222,7 @@ class FusedEvalST(FusedEval):
 #   geom:   K, KT, stride, block residual (0 none | 1 identity | 2 conv)
 # x (N, Cin, T, V) -> out (N, Cout, (T - 1) // stride + 1, V).  Two launches.
 # ----------------------------------------------------------------------------------------------------------------------
-@torch.library.custom_op('tamgcn::st_gcn_eval', mutates_args=())
-def st_gcn_eval(x: Tensor, params: List[Tensor], geom: List[int]) -> Tensor:
-    name = 'tamgcn::st_gcn_eval'
+def _st_gcn_fwd(name, x, params, geom):
     if not x.is_cuda or x.dtype != torch.float32:
         raise RuntimeError(f'{name}: expected a float32 HIP (cuda) tensor; there is no CPU path')
     if x.dim() != 4 or len(params) != 7 or len(geom) != 4:
@@ -175,10 +251,78 @@ def st_gcn_eval(x: Tensor, params: List[Tensor], geom: List[int]) -> Tensor:
                         bt=bt.data_ptr(), x=x.data_ptr() if rmode else None, wr=_opt(Wr) if rmode == 2 else None,
                         br=_opt(br) if rmode == 2 else None, out=out.data_ptr())
     _lib.check(lib.tamgcn_f2s_tcn(C.byref(t), st), 'tamgcn_f2s_tcn')
-    return out
+    return out, h
+
+
+@torch.library.custom_op('tamgcn::st_gcn_eval', mutates_args=())
+def st_gcn_eval(x: Tensor, params: List[Tensor], geom: List[int]) -> Tensor:
+    return _st_gcn_fwd('tamgcn::st_gcn_eval', x, params, geom)[0]
 
 
 @st_gcn_eval.register_fake
 def _(x, params, geom):
     N, _, T, V = x.shape
     return x.new_empty(N, params[4].shape[0], (T - 1) // geom[2] + 1, V)
+
+
+# The same two launches, returning the gcn's h as well: what the data gradient needs to keep (its two ReLU masks).
+@torch.library.custom_op('tamgcn::st_gcn_eval_fwd', mutates_args=())
+def st_gcn_eval_fwd(x: Tensor, params: List[Tensor], geom: List[int]) -> Tuple[Tensor, Tensor]:
+    return _st_gcn_fwd('tamgcn::st_gcn_eval_fwd', x, params, geom)
+
+
+@st_gcn_eval_fwd.register_fake
+def _(x, params, geom):
+    N, _, T, V = x.shape
+    Cout = params[4].shape[0]
+    return x.new_empty(N, Cout, (T - 1) // geom[2] + 1, V), x.new_empty(N, Cout, T, V)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The block's data gradient as a registered operator (include/tamgcn.h "f2s backward").
+#   gout (N, Cout, T2, V): the gradient of the block's output;  out (N, Cout, T2, V), h (N, Cout, T, V): st_gcn_eval_fwd's results
+#   params: Ae [K][V][V], Wgb [K][Cin][Cout], Wtb [Cout][Cout][KT], Wrb [Cin][Cout] (empty if there is no residual conv)
+#   geom:   the forward's
+# -> dx (N, Cin, T, V).  Two launches.
+# ----------------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op('tamgcn::st_gcn_eval_bwd', mutates_args=())
+def st_gcn_eval_bwd(gout: Tensor, out: Tensor, h: Tensor, params: List[Tensor], geom: List[int]) -> Tensor:
+    name = 'tamgcn::st_gcn_eval_bwd'
+    if not (gout.is_cuda and out.is_cuda and h.is_cuda) or not (gout.dtype == out.dtype == h.dtype == torch.float32):
+        raise RuntimeError(f'{name}: expected float32 HIP (cuda) tensors; there is no CPU path')
+    if h.dim() != 4 or len(params) != 4 or len(geom) != 4:
+        raise RuntimeError(f'{name}: expected h (N, C, T, V), 4 tensors and 4 integers, got {tuple(h.shape)}, {len(params)}, {len(geom)}')
+    lib = _lib.load()
+    K, kt, stride, rmode = geom
+    Ae, Wgb, Wtb, Wrb = (t.contiguous() for t in params)
+    N, Cout, T, V = h.shape
+    Cin = Wgb.shape[1] if Wgb.dim() == 3 else 0
+    if not (2 <= V <= 32 and 1 <= K <= 3 and 1 <= Cin <= 256 and 16 <= Cout <= 256 and Cout % 16 == 0 and kt == KT and stride in (1, 2)):
+        raise RuntimeError(f'{name}: V={V} K={K} Cin={Cin} Cout={Cout} KT={kt} stride={stride} is outside the f2s kernels '
+                           '(2 <= V <= 32, K <= 3, Cin <= 256, Cout % 16 == 0, Cout <= 256, KT == 9, stride 1 | 2)')
+    T2 = (T - 1) // stride + 1
+    if tuple(gout.shape) != (N, Cout, T2, V) or tuple(out.shape) != (N, Cout, T2, V):
+        raise RuntimeError(f'{name}: gout {tuple(gout.shape)} and out {tuple(out.shape)} must be {(N, Cout, T2, V)} for h {tuple(h.shape)}, stride {stride}')
+    if tuple(Ae.shape) != (K, V, V) or tuple(Wgb.shape) != (K, Cin, Cout) or Wtb.numel() != Cout * Cout * kt:
+        raise RuntimeError(f'{name}: parameter shapes {[tuple(t.shape) for t in params]} do not fit h {tuple(h.shape)}, geom {list(geom)}')
+    if rmode == 2 and tuple(Wrb.shape) != (Cin, Cout) or rmode == 1 and (Cin != Cout or stride != 1) or rmode not in (0, 1, 2):
+        raise RuntimeError(f'{name}: residual mode {rmode} does not fit Cin={Cin} Cout={Cout} stride={stride}')
+    gout, out, h = gout.contiguous(), out.contiguous(), h.contiguous()
+    dev = h.device
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    dh = torch.empty(N, Cout, T, V, device=dev)
+    t = _lib.F2sTcnBwdDesc(N=N, Cout=Cout, T=T, V=V, KT=kt, stride=stride, gout=gout.data_ptr(), out=out.data_ptr(), h=h.data_ptr(),
+                           wtb=Wtb.data_ptr(), dh=dh.data_ptr())
+    _lib.check(lib.tamgcn_f2s_tcn_bwd(C.byref(t), st), 'tamgcn_f2s_tcn_bwd')
+    dx = torch.empty(N, Cin, T, V, device=dev)
+    g = _lib.F2sGcnBwdDesc(N=N, Cin=Cin, Cout=Cout, T=T, V=V, K=K, stride=stride, res_mode=rmode, dh=dh.data_ptr(), Ae=Ae.data_ptr(),
+                           wgb=Wgb.data_ptr(), gout=gout.data_ptr() if rmode else None, out=out.data_ptr() if rmode else None,
+                           wrb=Wrb.data_ptr() if rmode == 2 else None, dx=dx.data_ptr())
+    _lib.check(lib.tamgcn_f2s_gcn_bwd(C.byref(g), st), 'tamgcn_f2s_gcn_bwd')
+    return dx
+
+
+@st_gcn_eval_bwd.register_fake
+def _(gout, out, h, params, geom):
+    N, _, T, V = h.shape
+    return h.new_empty(N, params[1].shape[1], T, V)

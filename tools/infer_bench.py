@@ -15,7 +15,13 @@ one joint batch, every arrangement under HIP-graph replay, alternating within th
     (b) streams   the same with the G models on G streams inside the graph (functional.model_stream)
     (c) grouped   inference.StreamEnsemble(arrangement='grouped'): one grouped launch sequence
 then GraphedForward(StreamEnsemble(...)) with its default arrangement, and (a) and (c) launched from Python (eager): both
-carry the host cost of G parameter-state keys per call."""
+carry the host cost of G parameter-state keys per call.
+--model stgcn --saliency [--ab R]: gradient saliency (tam_gcn_amd/saliency.py) of the true class, (N, V) per batch, alternating in
+this process, R timings each (default 5):
+    A  general   eval-mode Model.forward in grad mode and torch.autograd.grad of the gathered score with respect to x (the only
+                 way without the f2s backward kernels), then |.| summed per joint -- eager
+    B  family    saliency.joint_saliency on the f2s forward + backward chain, forced on whatever the routing bound says -- eager and
+                 under HIP-graph replay"""
 import os, statistics, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -23,8 +29,11 @@ from tam_gcn_amd.models.ctrgcn import Model
 dev = torch.device('cuda:0')
 torch.manual_seed(0)
 args = sys.argv[1:]
-T, graph, ab, ens_g, model = 64, 'ucla', 0, 0, 'ctrgcn'
+T, graph, ab, ens_g, model, sal = 64, 'ucla', 0, 0, 'ctrgcn', False
 while args and args[0].startswith('--'):
+    if args[0] == '--saliency':
+        sal, args = True, args[1:]
+        continue
     if args[0] == '--t':
         T = int(args[1])
     elif args[0] == '--graph':
@@ -161,6 +170,53 @@ def ensemble_bench(G, batches, R):
               + ('WINS by more than the spread' if gain > spread else 'does NOT win (not below the better one by more than the spread)'), flush=True)
 
 
+def saliency_bench(batches, R):
+    from tam_gcn_amd import f2s, saliency
+    f2s.F2S_BWD_MAX_FRAMES = 1 << 40
+    print(f'saliency, model = stgcn, graph = {graph} (V = {V}, M = {P}), T = {T}; {R} alternating timings of {n} calls: median [min .. max]', flush=True)
+    for B in batches:
+        x = torch.rand(B, 3, T, V, P, device=dev) * 2 - 1
+        lab = torch.randint(0, 10, (B,), device=dev)
+
+        def general():
+            xd = x.detach().requires_grad_(True)
+            (g,) = torch.autograd.grad(torch.gather(m(xd), 1, lab.unsqueeze(1)).sum(), xd)
+            return g.abs().sum((1, 2, 4))
+
+        def family():
+            return saliency.joint_saliency(m, x, lab)
+        for _ in range(3):
+            ya, yb = general(), family()
+        s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            family()
+        torch.cuda.current_stream().wait_stream(s); torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            yg = family()
+        g.replay(); torch.cuda.synchronize()
+        assert torch.equal(yg, yb)
+        d = float((ya - yb).abs().max()) / float(ya.abs().max())
+        times = {'A general, eager': [], 'B family, eager ': [], 'B family, graph ': []}
+        for _ in range(R):
+            times['A general, eager'].append(timed(general))
+            times['B family, eager '].append(timed(family))
+            times['B family, graph '].append(timed(g.replay))
+        for k, v in times.items():
+            print(f'batch {B:4d} x {P} x {T} ({B * P * T:6d} frames)  {k}: {statistics.median(v) * 1e3:7.3f} ms [{min(v) * 1e3:7.3f} .. {max(v) * 1e3:7.3f}]', flush=True)
+        a, b = times['A general, eager'], times['B family, eager ']
+        spread = max(max(a) - min(a), max(b) - min(b))
+        gain = statistics.median(a) - statistics.median(b)
+        print(f'      family vs general saliency: {d:.1e} relative;  eager family {statistics.median(b) / statistics.median(a):5.2f}x of the general path\'s time, '
+              f'{gain * 1e3:+.3f} ms; larger [min .. max] spread {spread * 1e3:.3f} ms: the family '
+              + ('WINS by more than the spread' if gain > spread else 'does NOT win by more than the spread'), flush=True)
+
+
+if sal:
+    if model != 'stgcn':
+        sys.exit('--saliency: the family serves --model stgcn')
+    saliency_bench([int(v) for v in args] or (1, 16), ab or 5)
+    sys.exit(0)
 if ens_g:
     ensemble_bench(ens_g, [int(v) for v in args] or (1, 4), ab or 7)
     sys.exit(0)
