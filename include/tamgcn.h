@@ -141,6 +141,39 @@ typedef struct tamgcn_wgrad_desc {
 int tamgcn_wgrad_max_split(const tamgcn_wgrad_desc* d);
 int tamgcn_wgrad(const tamgcn_wgrad_desc* d, void* stream);
 
+/* Two stride-1 1x1 convolutions of the same tensor as one launch (MS-TCN: the stacked entry convolutions W0 and the plain
+ * 1x1 branch W1 both read g):   [y0; y1] = [W0; W1] . act(src) + [bias0; bias1]
+ * Rows [0, M0) go to (y0, yctot0, ycoff0) and the moment slice (stats_part0, stats_ctot0, stats_coff0), rows [M0, M0 + M1)
+ * to their own; w0 [M0][K], w1 [M1][K].  Runs the LDS-DMA GEMM of tamgcn_conv with the tiling of the single descriptor that
+ * has M = M0 + M1; a shape that kernel does not serve is refused.  Every output element and every moment partial is
+ * bit-identical to the two tamgcn_conv launches; the partial count is tamgcn_conv_nparts of M = M0 + M1. */
+typedef struct tamgcn_conv_pair_desc {
+    int N, T, V;                    /* every tensor is (N, *, T, V) */
+    int stride;                     /* must be 1 (a strided plain branch computes every other frame: two launches) */
+    tamgcn_src src;
+    int K, M0, M1;
+    const float* w0; const float* w1;
+    const float* bias0; const float* bias1;   /* optional */
+    float* y0; int yctot0, ycoff0;
+    float* y1; int yctot1, ycoff1;
+    float* stats_part0; int stats_ctot0, stats_coff0;   /* optional; both or neither */
+    float* stats_part1; int stats_ctot1, stats_coff1;
+} tamgcn_conv_pair_desc;
+int tamgcn_conv_pair(const tamgcn_conv_pair_desc* d, void* stream);
+
+/* Two weight gradients against the same src as one launch: rows [0, M0) of the gradient operand come from gy0, rows
+ * [M0, M0 + M1) from gy1 (both with the two-source BatchNorm-backward prologue); part [nsplit][M0 + M1][K].
+ * nsplit <= tamgcn_wgrad_max_split of the tamgcn_wgrad_desc with M = M0 + M1.  M0 % 8 == 0.  At the nsplit of a
+ * single tamgcn_wgrad launch the rows hold that launch's bits (a row's sum does not depend on the rows beside it). */
+typedef struct tamgcn_wgrad_pair_desc {
+    tamgcn_src gy0, gy1, src;
+    int N, M0, M1, K, T, V;
+    int stride;                     /* must be 1 */
+    float* part;
+    int nsplit;
+} tamgcn_wgrad_pair_desc;
+int tamgcn_wgrad_pair(const tamgcn_wgrad_pair_desc* d, void* stream);
+
 /* Several slab reductions in ONE launch (a layer's backward produces ~25 of them; the sums over (n, t, v) of aten's
  * convolution_backward / native_batch_norm_backward for the modules of reference models/ctrgcn.py:53-284): for each descriptor
  * out[e] (+)= scale * sum_s part[s*stride_s + e], fp64 accumulation in a fixed order. */

@@ -52,6 +52,23 @@ class WgradDesc(C.Structure):
                 ('part', C.c_void_p), ('nsplit', C.c_int)]
 
 
+class ConvPairDesc(C.Structure):
+    _fields_ = [('N', C.c_int), ('T', C.c_int), ('V', C.c_int), ('stride', C.c_int),
+                ('src', Src),
+                ('K', C.c_int), ('M0', C.c_int), ('M1', C.c_int),
+                ('w0', C.c_void_p), ('w1', C.c_void_p), ('bias0', C.c_void_p), ('bias1', C.c_void_p),
+                ('y0', C.c_void_p), ('yctot0', C.c_int), ('ycoff0', C.c_int),
+                ('y1', C.c_void_p), ('yctot1', C.c_int), ('ycoff1', C.c_int),
+                ('stats_part0', C.c_void_p), ('stats_ctot0', C.c_int), ('stats_coff0', C.c_int),
+                ('stats_part1', C.c_void_p), ('stats_ctot1', C.c_int), ('stats_coff1', C.c_int)]
+
+
+class WgradPairDesc(C.Structure):
+    _fields_ = [('gy0', Src), ('gy1', Src), ('src', Src),
+                ('N', C.c_int), ('M0', C.c_int), ('M1', C.c_int), ('K', C.c_int), ('T', C.c_int), ('V', C.c_int),
+                ('stride', C.c_int), ('part', C.c_void_p), ('nsplit', C.c_int)]
+
+
 class ReduceDesc(C.Structure):
     _fields_ = [('part', C.c_void_p), ('out', C.c_void_p), ('nsplit', C.c_int), ('accumulate', C.c_int),
                 ('stride_s', C.c_longlong), ('count', C.c_longlong), ('scale', C.c_float)]
@@ -144,6 +161,8 @@ SIGNATURES = {
     'tamgcn_conv': (_i, [C.POINTER(ConvDesc), _p]),
     'tamgcn_wgrad_max_split': (_i, [C.POINTER(WgradDesc)]),
     'tamgcn_wgrad': (_i, [C.POINTER(WgradDesc), _p]),
+    'tamgcn_conv_pair': (_i, [C.POINTER(ConvPairDesc), _p]),
+    'tamgcn_wgrad_pair': (_i, [C.POINTER(WgradPairDesc), _p]),
     'tamgcn_stem_stats': (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     'tamgcn_stem_apply': (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     'tamgcn_head_pool_fwd': (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),

@@ -53,6 +53,16 @@ struct ConvArgs {
     int Vs, Vp, nsl;
 };
 
+// The second half of a paired launch (tamgcn_conv_pair): two GEMMs on one operand as one.  Row split (forward, w[m][k]): rows
+// m >= M0 of the stacked output take their weights, bias, destination and moment slot from here (as row m - M0); a row's dot
+// product and its per-tile moment do not depend on the rows beside it.
+struct PairArgs {
+    int M0;
+    const float* w1; const float* bias1;
+    float* y1; int yctot1, ycoff1;
+    float* stats1; int sctot1, scoff1;
+};
+
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[4][MAXCW], float* Ss, int n, int m0, int t0,
                                               int ncols, int cw0, int mt_act, int c_act, const int (&tl)[MAXCW],
                                               const int (&vv)[MAXCW], int j, int kq, int wave, int tid) {
@@ -248,9 +258,9 @@ __global__ __launch_bounds__(NTHREADS) void conv_kernel(const ConvArgs a) {
 // Second half of the staged epilogue: rows r0..r0+RP-1 of the accumulator tile sit in LDS (Tt, pitch PT);
 // TPR threads walk one row in float4 steps: bias / broadcast / residual adds / mask / BatchNorm moments,
 // 16-byte coalesced loads and stores.  Row moments land in Ss[0..BMT) / Ss[4*BM..).
-template <int NTH>
+template <int NTH, bool PR = false>
 __device__ __forceinline__ void staged_rows(const ConvArgs& a, const float* Tt, int PT, int RP, int r0, int BMT, int m0, int n, int t0,
-                                            int ncols, float* Ss, int Vs, int v0) {
+                                            int ncols, float* Ss, int Vs, int v0, const PairArgs* pa = nullptr) {
     const int tid = threadIdx.x, V = a.V;
     const int TPR = NTH / RP;
     const int row = tid / TPR, seg = tid - row * TPR;
@@ -263,11 +273,20 @@ __device__ __forceinline__ void staged_rows(const ConvArgs& a, const float* Tt, 
     float p1 = 0.f, p2 = 0.f;
     const bool rowok = r0 + row < BMT && m < a.M;   // RP may overshoot the tile (BMT = 48, RP = 32)
     if (rowok) {
-        const float bia = a.bias ? a.bias[m] : 0.f;
+        // row split: the second part's rows have their own bias and destination (no adds, mask, aux or output affine: host-checked)
+        float bia = a.bias ? a.bias[m] : 0.f;
+        float* yp = a.y;
         const float ctr = a.aux ? a.aux_center[a.auxcoff + m] : 0.f;
         const float pc1 = a.post_coef ? a.post_coef[a.ycoff + m] : 1.f, pc0 = a.post_coef ? a.post_coef[2 * a.post_ctot + a.ycoff + m] : 0.f;
         const float plo = a.post_act == 1 ? 0.f : -__builtin_inff();
-        const long long ybase = ((long long)n * a.yctot + a.ycoff + m) * a.T_y * V;
+        long long ybase = ((long long)n * a.yctot + a.ycoff + m) * a.T_y * V;
+        if constexpr (PR) {
+            if (m >= pa->M0) {
+                const int m1 = m - pa->M0;
+                bia = pa->bias1 ? pa->bias1[m1] : 0.f; yp = pa->y1;
+                ybase = ((long long)n * pa->yctot1 + pa->ycoff1 + m1) * a.T_y * V;
+            }
+        }
         const long long mbase = a.has_mask ? ((long long)n * a.mask.ctot + a.mask.coff + m) * a.T_y * V : 0;
         const long long abase = a.aux ? ((long long)n * a.auxctot + a.auxcoff + m) * a.T_y * V : 0;
         const float* bc = a.bcast ? a.bcast + ((long long)m * a.N + n) * V : nullptr;
@@ -314,7 +333,7 @@ __device__ __forceinline__ void staged_rows(const ConvArgs& a, const float* Tt, 
                     p1 += (val.x + val.y) + (val.z + val.w);
                     p2 = fmaf(val.x, x2.x, fmaf(val.y, x2.y, fmaf(val.z, x2.z, fmaf(val.w, x2.w, p2))));
                 }
-                *reinterpret_cast<float4*>(a.y + ybase + off) = val;
+                *reinterpret_cast<float4*>(yp + ybase + off) = val;
             } else {
                 // the last, partial group of a tile whose column count is not a multiple of 4, or a group that leaves its
                 // frame in a strided / sliced output: one column at a time
@@ -335,7 +354,7 @@ __device__ __forceinline__ void staged_rows(const ConvArgs& a, const float* Tt, 
                         p1 += val;
                         p2 = fmaf(val, x2, p2);
                     }
-                    a.y[ybase + off] = val;
+                    yp[ybase + off] = val;
                 }
             }
         }
@@ -604,8 +623,9 @@ constexpr int G_NT = 512, G_BMT = 64, G_PA = 80, G_PBMAX = 320, G_NST = 3, G_CWT
 // arithmetic of a B fragment are paid once per wave that reads it -- four row tiles per wave halve both.
 // PRO: the source carries a prologue (coefficients, second source or ReLU).  A plain tensor (the dx <- dx3 GEMMs, K = 3 C) needs neither
 // the [3][K] coefficient table -- which alone pushed K >= 384 past 80 KB, i.e. to ONE workgroup per CU -- nor the VALU on the fragments.
-template <int NSRC, int BK, bool PRO, int NW>
-__global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void conv1x1_glds_kernel(const ConvArgs a, int ntt, int nmt) {
+// PAIR: 0 one GEMM; 1 the row-split form of tamgcn_conv_pair (PairArgs), a.M the stacked extent.
+template <int NSRC, int BK, bool PRO, int NW, int PAIR = 0>
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void conv1x1_glds_kernel(const ConvArgs a, int ntt, int nmt, const PairArgs pa) {
     constexpr int G_NT = NW * 64, G_MT = 16 / NW;                 // threads; row tiles per wave
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int STG = BK * G_PBMAX * NSRC + BK * G_PA;          // floats per stage
@@ -675,7 +695,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void conv1x1_glds_kernel(
         const int m = wave * RPP + ml;                              // row inside the tile (waves >= NAP0 idle)
         const int f = BK == 16 ? (m >> 1) & 3 : (m >> 2) & 1;
         a_ok = wave < NAP0 && m0 + m < a.M;
-        wbase = a.w + (long long)(m0 + (a_ok ? m : 0)) * a.ws_m + a.w_off + 4 * (q ^ f);
+        const float* wsel = a.w; int mrow = m0 + (a_ok ? m : 0);
+        if constexpr (PAIR == 1) {                                  // row split: this row's weights (chosen once, here)
+            if (mrow >= pa.M0) { wsel = pa.w1; mrow -= pa.M0; }
+        }
+        wbase = wsel + (long long)mrow * a.ws_m + a.w_off + 4 * (q ^ f);
         a_dst0 = wave * 256;
     } else {
         a_ok = m0 + lane < a.M;
@@ -906,14 +930,15 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void conv1x1_glds_kernel(
             }
         }
         __syncthreads();
-        staged_rows<G_NT>(a, Tt, PT, RP, r0, G_BMT, m0, n, t0, ncols, Ss, V, 0);
+        staged_rows<G_NT, PAIR == 1>(a, Tt, PT, RP, r0, G_BMT, m0, n, t0, ncols, Ss, V, 0, &pa);
     }
     if (a.stats_part) {
         __syncthreads();
         if (tid < 2 * G_BMT) {
             int stt = tid / G_BMT, row = tid - stt * G_BMT;
             int m = m0 + row;
-            if (m < a.M) a.stats_part[((long long)stt * a.stats_ctot + a.stats_coff + m) * a.nparts + g] = Ss[stt * 4 * BM + row];
+            if (PAIR == 1 && m < a.M && m >= pa.M0) pa.stats1[((long long)stt * pa.sctot1 + pa.scoff1 + m - pa.M0) * a.nparts + g] = Ss[stt * 4 * BM + row];
+            else if (m < a.M) a.stats_part[((long long)stt * a.stats_ctot + a.stats_coff + m) * a.nparts + g] = Ss[stt * 4 * BM + row];
         }
     }
     TG_T(tg1); TG_ACC(7, tg1 - tg0); TG_ACC(8, tg1 - tt0); TG_ACC(9, 1);
@@ -1306,7 +1331,7 @@ extern "C" int tamgcn_conv(const tamgcn_conv_desc* d, void* stream) {
 #define TG_GLDS_CASE(NS_, BK_, PRO_, NW_)                                                                                 \
         {                                                                                                                   \
             tg_launch_lds<conv1x1_glds_kernel<NS_, BK_, PRO_, NW_>>(160 * 1024, dim3(nblk), dim3(NW_ * 64), glds_lds_bytes<NS_, BK_>(d->K, PRO_), \
-                                                                    (hipStream_t)stream, a, p.ntt, nmt);                    \
+                                                                    (hipStream_t)stream, a, p.ntt, nmt, PairArgs{});        \
             tamgcn_note_kernel("conv1x1_glds_kernel<%d, %d, %s, %d>", NS_, BK_, PRO_ ? "true" : "false", NW_);              \
         }
         if (nw_env != 4) {
@@ -1333,5 +1358,72 @@ extern "C" int tamgcn_conv(const tamgcn_conv_desc* d, void* stream) {
         tamgcn_note_kernel("conv_kernel");
     }
     TG_LAUNCH_CHECK("tamgcn_conv");
+    return 0;
+}
+
+
+// ---------------------------------------------------------------------------
+// Two stride-1 1x1 convolutions of the same tensor as ONE launch of conv1x1_glds_kernel (MS-TCN: the stacked entry convolutions
+// and the plain 1x1 branch both read g).  The tiling, the kernel instantiation and the moment-partial count are those of the
+// single tamgcn_conv descriptor with the stacked rows (M = M0 + M1): every output element and moment partial holds the bits
+// of the two separate launches.  (The launch is always the eight-wave form: under TAMGCN_CONV_WAVES=4, a side-by-side knob
+// of tamgcn_conv, the single launches are another instantiation and the moments' summation order differs.)
+// ---------------------------------------------------------------------------
+extern "C" int tamgcn_conv_pair(const tamgcn_conv_pair_desc* d, void* stream) {
+    TG_CHECK(d, "tamgcn_conv_pair: null descriptor");
+    TG_CHECK(d->src.x1 && d->w0 && d->w1 && d->y0 && d->y1, "tamgcn_conv_pair: null pointer");
+    TG_CHECK(d->N > 0 && d->T > 0 && d->V > 0 && d->K > 0 && d->M0 > 0 && d->M1 >= 0,
+             "tamgcn_conv_pair: bad dims N=%d T=%d V=%d K=%d M0=%d M1=%d", d->N, d->T, d->V, d->K, d->M0, d->M1);
+    TG_CHECK(d->M1 > 0, "tamgcn_conv_pair: M1 = 0: nothing to pair (use tamgcn_conv)");
+    TG_CHECK(d->stride == 1, "tamgcn_conv_pair: stride %d: only stride-1 1x1 convolutions pair up", d->stride);
+    const bool two = d->src.x2 != nullptr;
+    const int bk = two ? 8 : 16;                            // the chunk of the instantiation tamgcn_conv chooses for this operand
+    TG_CHECK(d->K % 16 == 0, "tamgcn_conv_pair: K=%d is not a multiple of the chunk (%d rows; the kernel takes whole 16)", d->K, bk);
+    TG_CHECK(d->src.coff >= 0 && d->src.coff + d->K <= d->src.ctot, "tamgcn_conv_pair: source channel slice out of range");
+    TG_CHECK(d->ycoff0 >= 0 && d->ycoff0 + d->M0 <= d->yctot0 && d->ycoff1 >= 0 && d->ycoff1 + d->M1 <= d->yctot1,
+             "tamgcn_conv_pair: destination slice out of range");
+    TG_CHECK((d->stats_part0 != nullptr) == (d->stats_part1 != nullptr), "tamgcn_conv_pair: moments go with both parts or with neither");
+    if (d->stats_part0) TG_CHECK(d->stats_coff0 >= 0 && d->stats_coff0 + d->M0 <= d->stats_ctot0 && d->stats_coff1 >= 0 && d->stats_coff1 + d->M1 <= d->stats_ctot1,
+                                 "tamgcn_conv_pair: moment slice out of range");
+    const int yct = d->yctot0 > d->yctot1 ? d->yctot0 : d->yctot1;
+    TG_CHECK((long long)d->N * yct * d->T * d->V < (1LL << 32), "tamgcn_conv_pair: output tensor exceeds 2^32 elements");
+    const int K = d->K, M = d->M0 + d->M1;
+    tamgcn_conv_desc cd = {};                               // the single GEMM with the stacked rows: its plan is the pair's
+    cd.src = d->src; cd.N = d->N; cd.K = K; cd.T_in = d->T; cd.V = d->V; cd.w = d->w0; cd.M = M; cd.KT = 1; cd.dil = 1; cd.stride = 1;
+    cd.wmode = 0; cd.up = 1; cd.y = d->y0; cd.yctot = d->yctot0; cd.T_out = d->T; cd.T_y = d->T; cd.ostride = 1;
+    ConvPlan p;
+    TG_CHECK(plan_conv(&cd, &p) == 0, "tamgcn_conv_pair: no tiling for V=%d", d->V);
+    const uintptr_t al = (uintptr_t)d->src.x1 | (uintptr_t)(two ? d->src.x2 : d->src.x1) | (uintptr_t)d->w0 | (uintptr_t)d->w1;
+    const bool glds = p.vec && p.flat && p.LB >= 64 && p.LB <= G_PBMAX && (p.LB & 3) == 0 && (al & 15) == 0 && K <= 1024 &&
+                      (long long)K * d->T * d->V < (1LL << 30);
+    TG_CHECK(glds, "tamgcn_conv_pair: V=%d T=%d K=%d is not a shape of the LDS-DMA GEMM (or an operand is not 16-byte aligned)", d->V, d->T, K);
+    ConvArgs a = {};
+    a.src = make_src(d->src);
+    a.N = d->N; a.K = K; a.T_in = d->T; a.V = d->V;
+    a.w = d->w0; a.bias = d->bias0; a.M = M; a.KT = 1; a.dil = 1; a.stride = 1; a.pad = 0;
+    a.ws_m = K; a.ws_k = 1; a.ws_t = 1; a.w_off = 0;
+    a.up = 1; a.wmode = 0;
+    a.y = d->y0; a.yctot = d->yctot0; a.ycoff = d->ycoff0; a.T_out = d->T; a.T_y = d->T; a.ostride = 1;
+    a.mask = null_src();
+    a.stats_part = d->stats_part0; a.stats_ctot = d->stats_ctot0; a.stats_coff = d->stats_coff0;
+    a.nparts = d->N * p.ntt * p.nsl;
+    a.BT = p.BT; a.CW = p.CW; a.TIN = p.TIN; a.lstride = p.lstride; a.sB = p.sB; a.LB = p.LB; a.pitchB = p.pitchB;
+    a.Vs = p.Vs; a.Vp = p.Vp; a.nsl = p.nsl;
+    PairArgs pa = {};
+    pa.M0 = d->M0; pa.w1 = d->w1; pa.bias1 = d->bias1;
+    pa.y1 = d->y1; pa.yctot1 = d->yctot1; pa.ycoff1 = d->ycoff1;
+    pa.stats1 = d->stats_part1; pa.sctot1 = d->stats_ctot1; pa.scoff1 = d->stats_coff1;
+    const int nmt = ceil_div(M, G_BMT);
+    const unsigned nblk = (unsigned)(d->N * p.ntt * nmt);
+    const bool pro = d->src.coef || d->src.x2 || d->src.act;
+#define TG_PAIR_CASE(NS_, BK_, PRO_)                                                                                      \
+    {                                                                                                                   \
+        tg_launch_lds<conv1x1_glds_kernel<NS_, BK_, PRO_, 8, 1>>(160 * 1024, dim3(nblk), dim3(8 * 64), glds_lds_bytes<NS_, BK_>(K, PRO_), \
+                                                                 (hipStream_t)stream, a, p.ntt, nmt, pa);               \
+        tamgcn_note_kernel("conv1x1_glds_kernel<%d, %d, %s, 8, 1>", NS_, BK_, PRO_ ? "true" : "false");                 \
+    }
+    if (two) TG_PAIR_CASE(2, 8, true) else if (pro) TG_PAIR_CASE(1, 16, true) else TG_PAIR_CASE(1, 16, false)
+#undef TG_PAIR_CASE
+    TG_LAUNCH_CHECK("tamgcn_conv_pair");
     return 0;
 }

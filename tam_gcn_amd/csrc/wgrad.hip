@@ -345,11 +345,15 @@ __global__ __launch_bounds__(NTHREADS) void wgrad_kernel(const WgradArgs a) {
 // ===========================================================================
 constexpr int W_PC = 32, W_NST = 3, W_NT = 512;
 
-template <int WMT, int WKT, int NY, int NX, bool SPL, int NST>
+// tamgcn_wgrad_pair: rows m >= M0 of the gradient operand come from a second tensor (as its channel gy1.coff + m - M0, with its own
+// prologue coefficients); a.M is the stacked extent.  M0 % 8 == 0 (host): a DMA piece of eight rows belongs to one tensor.
+struct WgradPair { int M0; SrcDev gy1; };
+
+template <int WMT, int WKT, int NY, int NX, bool SPL, int NST, bool PAIR = false>
 #ifndef TG_WKO
 #define TG_WKO 0      // knock-out side builds of the weight-gradient kernel (tools/wgrad_knockout.py): 1 one MFMA in eight, 2 no DMA, 4 no fragment reads, 8 no barrier (profiles/r04_wgrad_knockout.txt)
 #endif
-__global__ __launch_bounds__(W_NT, 2) void wgrad_glds_kernel(const WgradArgs a, int ntk, int ntm) {
+__global__ __launch_bounds__(W_NT, 2) void wgrad_glds_kernel(const WgradArgs a, int ntk, int ntm, const WgradPair wp) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int BMW = 2 * WMT * 16, BKW = 4 * WKT * 16;
     constexpr int RY = BMW * NY, RX = BKW * NX, ROWS = RY + RX;
@@ -384,7 +388,7 @@ __global__ __launch_bounds__(W_NT, 2) void wgrad_glds_kernel(const WgradArgs a, 
     const int pr = lane >> 3, ps = lane & 7;
     const int pu = ps ^ pr;                                       // logical 16-byte slot this lane fetches
     const float* p_base[MAXP];
-    bool p_ok[MAXP], p_on[MAXP], p_isy[MAXP];
+    bool p_ok[MAXP], p_on[MAXP], p_isy[MAXP], p_y1[PAIR ? MAXP : 1];
     int p_dst[MAXP];
     int nissue = 0;
 #pragma unroll
@@ -400,24 +404,31 @@ __global__ __launch_bounds__(W_NT, 2) void wgrad_glds_kernel(const WgradArgs a, 
         const int ch = (isy ? m0 : k0) + r;
         p_ok[i] = qok && ch < (isy ? a.M : a.K);
         p_base[i] = (img == 0 ? sd.x1 : sd.x2) + (long long)(sd.coff + (p_ok[i] ? ch : 0)) * (isy ? cs : csx) + pu * 4;
+        if constexpr (PAIR) {
+            p_y1[i] = isy && p_ok[i] && ch >= wp.M0;
+            if (p_y1[i]) p_base[i] = (img == 0 ? wp.gy1.x1 : wp.gy1.x2) + (long long)(wp.gy1.coff + ch - wp.M0) * cs + pu * 4;
+        }
         p_isy[i] = isy;
         p_dst[i] = row0 * W_PC;
         p_on[i] = __ballot(p_ok[i]) != 0ull;
         nissue += p_on[i] ? 1 : 0;
     }
     const long long ystep = (long long)a.gy.ctot * cs, xstep = (long long)a.src.ctot * csx;
+    const long long ystep1 = PAIR ? (long long)wp.gy1.ctot * cs : 0;
     auto issue = [&](int c) {
         if (TG_WKO & 2) return;
         float* st = smem + (c % NST) * STG;
         const int gc = c_begin + c, nn = gc / cps, pc = gc - nn * cps;
         const int po = pc < cpf ? pc * W_PC : wlen - W_PC;        // the row's last, partial chunk: re-fetch the last 32
         const long long oy = (long long)nn * ystep + ylo + po;
+        const long long oy1 = PAIR ? (long long)nn * ystep1 + ylo + po : 0;
         // stride 2: this lane's slot starts at p0 = po + 4 pu of frame p0 / V; its x elements sit one frame further per frame
         const long long ox = (long long)nn * xstep + xlo + po + (a.stride == 2 ? tg_rcp_div(po + pu * 4, rV) * a.V : 0);
 #pragma unroll
         for (int i = 0; i < MAXP; ++i) {
             if (p_on[i]) {
                 const float* gp = p_base[i] + (p_isy[i] ? oy : ox);
+                if constexpr (PAIR) { if (p_y1[i]) gp = p_base[i] + oy1; }
                 if (p_ok[i]) __builtin_amdgcn_global_load_lds((tg_gptr)gp, (tg_lptr)(st + p_dst[i]), 16, 0, 0);
             }
         }
@@ -433,6 +444,12 @@ __global__ __launch_bounds__(W_NT, 2) void wgrad_glds_kernel(const WgradArgs a, 
         cy1[x] = ok ? a.gy.coef[ch] : 1.f;
         cy2[x] = (ok && NY == 2) ? a.gy.coef[a.gy.ctot + ch] : 0.f;
         cy0[x] = ok ? a.gy.coef[2 * a.gy.ctot + ch] : 0.f;
+        if constexpr (PAIR) {                                       // a row of the second tensor: its own coefficient table (host: not null)
+            if (m < a.M && m >= wp.M0) {
+                const int c1 = wp.gy1.coff + m - wp.M0, ct = wp.gy1.ctot;
+                cy1[x] = wp.gy1.coef[c1]; cy2[x] = NY == 2 ? wp.gy1.coef[ct + c1] : 0.f; cy0[x] = wp.gy1.coef[2 * ct + c1];
+            }
+        }
     }
 #pragma unroll
     for (int y = 0; y < WKT; ++y) {
@@ -547,16 +564,16 @@ __global__ __launch_bounds__(W_NT, 2) void wgrad_glds_kernel(const WgradArgs a, 
             }
 }
 
-template <int WMT, int WKT, int NY, int NX, bool SPL>
-static int launch_wgrad_glds(WgradArgs& a, hipStream_t s) {
+template <int WMT, int WKT, int NY, int NX, bool SPL, bool PAIR = false>
+static int launch_wgrad_glds(WgradArgs& a, hipStream_t s, const WgradPair& wp = WgradPair{}) {
     constexpr int BMW = 2 * WMT * 16, BKW = 4 * WKT * 16;
     constexpr size_t STAGE = sizeof(float) * (size_t)(BMW * NY + BKW * NX) * W_PC;
     // a third stage only where it does not cost the second workgroup per CU
     constexpr int NST = (2 * STAGE <= 80 * 1024 && 3 * STAGE > 80 * 1024) ? 2 : W_NST;
     const size_t lds = NST * STAGE;
     const int ntk = ceil_div(a.K, BKW), ntm = ceil_div(a.M, BMW);
-    tg_launch_lds<wgrad_glds_kernel<WMT, WKT, NY, NX, SPL, NST>>(160 * 1024, dim3((unsigned)(ntk * ntm * a.nsplit * a.KTG)), dim3(W_NT), lds, s, a, ntk, ntm);
-    tamgcn_note_kernel("wgrad_glds_kernel<%d, %d, %d, %d, %s, %d>%s", WMT, WKT, NY, NX, SPL ? "split" : "f32", NST, a.KTG > 1 ? " taps" : "");
+    tg_launch_lds<wgrad_glds_kernel<WMT, WKT, NY, NX, SPL, NST, PAIR>>(160 * 1024, dim3((unsigned)(ntk * ntm * a.nsplit * a.KTG)), dim3(W_NT), lds, s, a, ntk, ntm, wp);
+    tamgcn_note_kernel("wgrad_glds_kernel<%d, %d, %d, %d, %s, %d>%s%s", WMT, WKT, NY, NX, SPL ? "split" : "f32", NST, a.KTG > 1 ? " taps" : "", PAIR ? " pair" : "");
     return 0;
 }
 
@@ -616,6 +633,14 @@ static int launch_wgrad(WgradArgs& a, hipStream_t s) {
     if (vec) tg_launch_lds<wgrad_kernel<KT, WMT, WKT, true, PS>>(160 * 1024, grid, dim3(NTHREADS), lds, s, a);
     else tg_launch_lds<wgrad_kernel<KT, WMT, WKT, false>>(160 * 1024, grid, dim3(NTHREADS), lds, s, a);
     return 0;
+}
+
+// the paired form (tamgcn_wgrad_pair): both gradient tensors carry the two-source BatchNorm-backward prologue, x is plain or one-source
+template <int WMT, int WKT>
+static int launch_wgrad_glds_pair(WgradArgs& a, hipStream_t s, const WgradPair& wp) {
+    const bool spl = tamgcn_split_mode() >= 1, x2 = a.src.x2 != nullptr;
+    if (spl) return x2 ? launch_wgrad_glds<WMT, WKT, 2, 2, true, true>(a, s, wp) : launch_wgrad_glds<WMT, WKT, 2, 1, true, true>(a, s, wp);
+    return x2 ? launch_wgrad_glds<WMT, WKT, 2, 2, false, true>(a, s, wp) : launch_wgrad_glds<WMT, WKT, 2, 1, false, true>(a, s, wp);
 }
 
 // tile shape chosen from (M, K, KT); the host wrapper uses the same rule to size nsplit
@@ -723,5 +748,45 @@ extern "C" int tamgcn_wgrad(const tamgcn_wgrad_desc* d, void* stream) {
     }
     if (rc) return rc;
     TG_LAUNCH_CHECK("tamgcn_wgrad");
+    return 0;
+}
+
+
+// Two weight gradients against the same x as one launch: rows [0, M0) of the gradient operand from gy0, rows [M0, M0 + M1) from gy1,
+// one slab array [nsplit][M0 + M1][K].  nsplit is bounded by tamgcn_wgrad_max_split of the single descriptor with M = M0 + M1.
+extern "C" int tamgcn_wgrad_pair(const tamgcn_wgrad_pair_desc* d, void* stream) {
+    TG_CHECK(d, "tamgcn_wgrad_pair: null descriptor");
+    TG_CHECK(d->gy0.x1 && d->gy1.x1 && d->src.x1 && d->part, "tamgcn_wgrad_pair: null pointer");
+    TG_CHECK(d->N > 0 && d->M0 > 0 && d->M1 >= 0 && d->K > 0 && d->T > 0 && d->V > 0 && d->nsplit > 0,
+             "tamgcn_wgrad_pair: bad dims N=%d M0=%d M1=%d K=%d T=%d V=%d nsplit=%d", d->N, d->M0, d->M1, d->K, d->T, d->V, d->nsplit);
+    TG_CHECK(d->M1 > 0, "tamgcn_wgrad_pair: M1 = 0: nothing to pair (use tamgcn_wgrad)");
+    TG_CHECK(d->stride == 1, "tamgcn_wgrad_pair: stride %d: only stride-1 1x1 convolutions pair up", d->stride);
+    TG_CHECK(d->M0 % 8 == 0, "tamgcn_wgrad_pair: M0=%d is not a multiple of the chunk's 8-row pieces", d->M0);
+    TG_CHECK(d->gy0.coff >= 0 && d->gy0.coff + d->M0 <= d->gy0.ctot && d->gy1.coff >= 0 && d->gy1.coff + d->M1 <= d->gy1.ctot &&
+             d->src.coff >= 0 && d->src.coff + d->K <= d->src.ctot, "tamgcn_wgrad_pair: channel slice out of range");
+    TG_CHECK(d->gy0.x2 && d->gy1.x2 && d->gy0.coef && d->gy1.coef && d->gy0.act == d->gy1.act,
+             "tamgcn_wgrad_pair: both gradient operands carry the two-source prologue (x1, x2, coef)");
+    tamgcn_wgrad_desc sd = {};                               // the single weight gradient with the stacked rows: its plan is the pair's
+    sd.gy = d->gy0; sd.src = d->src; sd.N = d->N; sd.M = d->M0 + d->M1; sd.K = d->K; sd.T_in = d->T; sd.T_out = d->T; sd.V = d->V;
+    sd.KT = 1; sd.dil = 1; sd.stride = 1; sd.pad = 0; sd.part = d->part; sd.nsplit = d->nsplit;
+    TG_CHECK(d->nsplit <= tamgcn_wgrad_max_split(&sd), "tamgcn_wgrad_pair: nsplit=%d exceeds tamgcn_wgrad_max_split=%d", d->nsplit,
+             tamgcn_wgrad_max_split(&sd));
+    int wmt, wkt;
+    const bool al1 = (((uintptr_t)d->gy1.x1 | (uintptr_t)d->gy1.x2) & 15) == 0;
+    TG_CHECK(wgrad_glds_plan(&sd, &wmt, &wkt) && al1, "tamgcn_wgrad_pair: V=%d T=%d is not a shape of the LDS-DMA weight gradient (or an operand is not 16-byte aligned)", d->V, d->T);
+    WgradArgs a = {};
+    a.gy = make_src(d->gy0); a.src = make_src(d->src);
+    a.N = d->N; a.M = sd.M; a.K = d->K; a.T_in = d->T; a.T_out = d->T; a.V = d->V;
+    a.dil = 1; a.stride = 1; a.pad = 0; a.part = d->part; a.nsplit = d->nsplit; a.KTG = 1;
+    WgradPair wp;
+    wp.M0 = d->M0; wp.gy1 = make_src(d->gy1);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if (wmt == 2 && wkt == 2) rc = launch_wgrad_glds_pair<2, 1>(a, s, wp);
+    else if (wmt == 4 && wkt == 2) rc = launch_wgrad_glds_pair<4, 1>(a, s, wp);
+    else if (wmt == 2 && wkt == 4) rc = launch_wgrad_glds_pair<2, 2>(a, s, wp);
+    else rc = launch_wgrad_glds_pair<4, 2>(a, s, wp);
+    if (rc) return rc;
+    TG_LAUNCH_CHECK("tamgcn_wgrad_pair");
     return 0;
 }

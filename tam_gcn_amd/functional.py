@@ -458,11 +458,18 @@ def tcn_forward(g, P, training, save, xres=None, pool=None):
     cat_pre = ops.empty(N, Cout, T2, V, like=g)
     coef_c, save_c = _coef(Cout, g)
     bo = ops.BNBatch()                                 # the branches' output norms: one launch after the join
-    with fk.on(1):                                     # the plain 1x1 branch only needs g
-        _, lpart = ops.conv(gs, K=Cin, w=P.Wl, bias=P.bl, M=Cb, stride=s, y=cat_pre, ycoff=(nb + 1) * Cb, T_out=T2,
-                            stats=training)
-        P.bn_l.fwd(lpart, (nb + 1) * Cb, cnt2, training, coef_c, save_c, (nb + 1) * Cb, batch=bo)
-    h_pre, hpart = ops.conv(gs, K=Cin, w=P.Win, bias=P.bin, M=Ch, stats=training)
+    # stride 1: the stacked entry convs and the plain 1x1 branch are two GEMMs on the same g -- one launch, g read once
+    # (rows [0, Ch) into h_pre, rows [Ch, Cout) into cat_pre; bit-identical to the two launches, csrc/conv.hip)
+    pair = ops.TCN_PAIR and s == 1 and Ch + Cb == Cout and ops.pair_supported((g, P.Win, P.Wl, cat_pre), N, (Cin, Cout), T, V)
+    if pair:
+        h_pre, hpart, _, lpart = ops.conv_pair(gs, P.Win, P.Wl, bias0=P.bin, bias1=P.bl, y1=cat_pre, ycoff1=Ch, stats=training)
+        P.bn_l.fwd(lpart, Ch, cnt2, training, coef_c, save_c, Ch, batch=bo)
+    else:
+        with fk.on(1):                                 # the plain 1x1 branch only needs g
+            _, lpart = ops.conv(gs, K=Cin, w=P.Wl, bias=P.bl, M=Cb, stride=s, y=cat_pre, ycoff=(nb + 1) * Cb, T_out=T2,
+                                stats=training)
+            P.bn_l.fwd(lpart, (nb + 1) * Cb, cnt2, training, coef_c, save_c, (nb + 1) * Cb, batch=bo)
+        h_pre, hpart = ops.conv(gs, K=Cin, w=P.Win, bias=P.bin, M=Ch, stats=training)
     coef_h, save_h = _coef(Ch, g)
     bi = ops.BNBatch()                                 # the three entry norms: one launch
     for b in range(nb + 1):
@@ -655,10 +662,23 @@ def _tcn_backward(P, sv, dout, need_dg=True, need_dxres=True):
     gs = S(g)
     gyh = S(dh, h_pre, coefb_h)
     fk.refork()                                        # dh and its BN-backward coefficients are ready
-    with fk.on(0):
-        G['Win'] = ops.wgrad(gyh, gs, M=Ch, K=Cin, rows=[Cb] * (nb + 1))
-    with fk.on(1):
-        G['Wl'] = ops.wgrad(gcat((nb + 1) * Cb), gs, M=Cb, K=Cin, stride=s)
+    # stride 1: both weight gradients stream the same g -- one launch, where it reproduces the two launches bit for bit (the
+    # same number of contraction splits: the 64- and 128-channel blocks; at 256 channels the plain branch alone splits finer).
+    # The data gradients stay two launches: as one GEMM they would be a single K0 + K1-term sum, not the sum of two rounded
+    # sums -- a rounding change of dg that a training run amplifies (profiles/tcn_pair_step_ab.txt).
+    nsp = None
+    if ops.TCN_PAIR and s == 1 and Ch + Cb == Cout and Ch % 8 == 0 and \
+            ops.pair_supported((g, dh, h_pre, dz, cat_pre), N, (Cin, Cout), T, V):
+        nsp = ops.wgrad_pair_nsplit(gyh, gcat(Ch), gs, Ch, Cb, Cin)
+    if nsp is not None:
+        with fk.on(0):
+            gw = ops.wgrad_pair(gyh, gcat(Ch), gs, Ch, Cb, Cin, rows=[Cb] * (nb + 2), nsplit=nsp)
+            G['Win'], G['Wl'] = gw[:nb + 1], gw[nb + 1]
+    else:
+        with fk.on(0):
+            G['Win'] = ops.wgrad(gyh, gs, M=Ch, K=Cin, rows=[Cb] * (nb + 1))
+        with fk.on(1):
+            G['Wl'] = ops.wgrad(gcat((nb + 1) * Cb), gs, M=Cb, K=Cin, stride=s)
     dg = None
     if need_dg:
         dg, _ = ops.conv(gyh, K=Ch, w=P.Win, bias=None, M=Cin, wmode=1)

@@ -156,6 +156,119 @@ def conv(src, K, w, bias, M, KT=1, dil=1, stride=1, pad=0, wmode=0, up=1,
 
 
 # ---------------------------------------------------------------------------
+# two stride-1 1x1 GEMMs that share a tensor as one launch (tamgcn_conv_pair / tamgcn_wgrad_pair)
+TCN_PAIR = os.environ.get('TAMGCN_TCN_PAIR', '1') != '0'   # 0: MS-TCN's entry convs and plain 1x1 branch as two launches per direction (A/B, tests)
+
+
+def pair_supported(tensors, N, chans, T, V):
+    """Whether tamgcn_conv_pair / tamgcn_wgrad_pair serve this shape.  The library refuses what its LDS-DMA kernels do not run
+    (conv.hip plan_conv: vec / flat / LB; wgrad.hip wgrad_glds_plan) and there is no entry point to ask it, so this is the
+    CONSERVATIVE side of those rules -- everything it admits they admit: 16-byte rows (V % 4 == 0) of whole frames (V <= 32:
+    a tile of 320 // V frames holds >= 64 columns, and so does a shorter clip with T * V >= 64), 16-byte aligned contiguous
+    operands, channel counts in whole 16-row chunks, one launch for the batch.  chans <= 512 also keeps plan_conv's LDS bound
+    (4 * (64 * 34 + 32 * 336 + 512 + 3 * 512) < 64 KB at the largest row tile) away from its frame-halving loop, so the plan
+    -- frames per tile, hence moment partials -- is the same for M = M0, M1 and M0 + M1: what the row split's bit-identity
+    with the two launches rests on.  Anything else takes the two launches."""
+    if V % 4 or V > 32 or T * V < 64 or any(c % 16 or c > 512 for c in chans) or N * max(chans) * T * V > CHUNK_ELEMS:
+        return False
+    return all(t is None or (t.is_cuda and t.is_contiguous() and t.data_ptr() % 16 == 0) for t in tensors)
+
+
+def conv_pair(src, w0, w1, bias0=None, bias1=None, y0=None, ycoff0=0, y1=None, ycoff1=0, stats=False):
+    """y0[:, ycoff0:+M0] = w0 . src + bias0 and y1[:, ycoff1:+M1] = w1 . src + bias1 in one launch, w0 (M0, K, 1, 1),
+    w1 (M1, K, 1, 1); returns (y0, part0, y1, part1), bit-identical to the two conv() calls."""
+    x = src.x1
+    N, _, T, V = x.shape
+    M0, M1, K = w0.shape[0], w1.shape[0], w0.shape[1]
+    if w1.shape[1] != K:
+        raise RuntimeError('tamgcn_conv_pair: the two weight matrices have the same K')
+    d = _lib.ConvPairDesc()
+    d.N, d.T, d.V, d.stride = N, T, V, 1
+    d.src = src.c()
+    d.w0, d.w1 = _ptr(w0), _ptr(w1)
+    d.K, d.M0, d.M1 = K, M0, M1
+    d.bias0, d.bias1 = _ptr(bias0), _ptr(bias1)
+    if y0 is None:
+        y0 = empty(N, M0, T, V, like=x)
+    if y1 is None:
+        y1 = empty(N, M1, T, V, like=x)
+    if y0.shape[2:] != x.shape[2:] or y1.shape[2:] != x.shape[2:]:
+        raise RuntimeError('tamgcn_conv_pair: destination geometry differs from the source (stride-1 1x1 only)')
+    d.y0, d.yctot0, d.ycoff0 = _ptr(y0), y0.shape[1], ycoff0
+    d.y1, d.yctot1, d.ycoff1 = _ptr(y1), y1.shape[1], ycoff1
+    lib = _lib_()
+    part0 = part1 = None
+    if stats:
+        cd = ConvDesc()                                    # the partial count is that of the single GEMM with the stacked rows
+        cd.src = d.src
+        cd.N, cd.K, cd.T_in, cd.V, cd.M, cd.KT, cd.dil, cd.stride, cd.up = N, K, T, V, M0 + M1, 1, 1, 1, 1
+        cd.T_out, cd.T_y, cd.ostride = T, T, 1
+        nparts = lib.tamgcn_conv_nparts(C.byref(cd))
+        if nparts <= 0:
+            raise RuntimeError('tamgcn_conv_pair: no tiling for this shape')
+        part0 = empty(2, y0.shape[1], nparts, like=x)
+        part1 = empty(2, y1.shape[1], nparts, like=x)
+        d.stats_part0, d.stats_ctot0, d.stats_coff0 = _ptr(part0), y0.shape[1], ycoff0
+        d.stats_part1, d.stats_ctot1, d.stats_coff1 = _ptr(part1), y1.shape[1], ycoff1
+    _lib.check(lib.tamgcn_conv_pair(C.byref(d), _stream()), 'tamgcn_conv_pair')
+    return y0, part0, y1, part1
+
+
+def _wgrad_desc(gy, src, M, K, KT=1, dil=1, stride=1, pad=0):
+    d = WgradDesc()
+    d.gy, d.src = gy.c(), src.c()
+    d.N, d.M, d.K, d.T_in, d.T_out, d.V = gy.x1.shape[0], M, K, src.x1.shape[2], gy.x1.shape[2], gy.x1.shape[3]
+    d.KT, d.dil, d.stride, d.pad = KT, dil, stride, pad
+    return d
+
+
+def _wgrad_splits(d, nlaunch=1):
+    """The ONE sizing rule of the weight-gradient launches (wgrad(), wgrad_pair(), wgrad_pair_nsplit()): slabs for descriptor
+    d when nlaunch launches share the contraction -- aim at WGRAD_BLOCKS workgroups (tiles x splits; same tile rule as
+    wgrad_tile() in csrc/wgrad.hip), never past tamgcn_wgrad_max_split."""
+    M, K, KT = d.M, d.K, d.KT
+    taps = KT > 1 and d.stride == 1 and d.T_in == d.T_out and (M > 32 or K > 32 or (d.V % 4 != 0 and (M > 16 or K > 16)))      # one window per tap on the LDS-DMA kernel
+    if KT == 1 or taps:
+        bm, bk = (64 if M <= 64 else 128), (64 if K <= 64 else 128)
+    elif KT == 9:
+        bm = bk = 32
+    else:
+        bm = bk = 32 if (M <= 32 and K <= 32) else 64
+    tiles = ((M + bm - 1) // bm) * ((K + bk - 1) // bk) * (KT if taps else 1)
+    per = max(1, (WGRAD_BLOCKS + tiles - 1) // tiles // nlaunch)
+    return max(1, min(_lib_().tamgcn_wgrad_max_split(C.byref(d)), per))
+
+
+def wgrad_pair_nsplit(gy0, gy1, src, M0, M1, K):
+    """The split count at which wgrad_pair() is bit-identical to the two wgrad() launches, or None.  A row of dW sums its
+    products chunk by chunk inside a split and the splits in a fixed order, whatever rows share its tile: the paired launch
+    reproduces both single launches exactly when all three cut the contraction into the same number of splits."""
+    ns = [_wgrad_splits(_wgrad_desc(gy, src, M, K)) for gy, M in ((gy0, M0 + M1), (gy0, M0), (gy1, M1))]
+    return ns[0] if ns[0] == ns[1] == ns[2] else None
+
+
+def wgrad_pair(gy0, gy1, src, M0, M1, K, rows=None, nsplit=None):
+    """dW of two 1x1 convolutions of the same src in one launch: rows [0, M0) from gy0, rows [M0, M0 + M1) from gy1.
+    Returns the (M0 + M1, K, 1, 1) gradient, or with rows = [m0, m1, ...] (summing to M0 + M1) one tensor per entry.
+    nsplit: the slab count (None: wgrad()'s rule for M = M0 + M1; the library refuses one past tamgcn_wgrad_max_split)."""
+    N, _, T, V = src.x1.shape
+    M = M0 + M1
+    if nsplit is None:
+        nsplit = _wgrad_splits(_wgrad_desc(gy0, src, M, K))
+    part = empty(nsplit, M, K, 1, like=src.x1)
+    d = _lib.WgradPairDesc()
+    d.gy0, d.gy1, d.src = gy0.c(), gy1.c(), src.c()
+    d.N, d.M0, d.M1, d.K, d.T, d.V, d.stride = N, M0, M1, K, T, V, 1
+    d.part, d.nsplit = _ptr(part), nsplit
+    _lib.check(_lib_().tamgcn_wgrad_pair(C.byref(d), _stream()), 'tamgcn_wgrad_pair')
+    if rows is not None:
+        return reduce_sum(part, nsplit, chunks=[(m, K, 1, 1) for m in rows])
+    if nsplit == 1:
+        return part.view(M, K, 1, 1)
+    return reduce_sum(part, nsplit).view(M, K, 1, 1)
+
+
+# ---------------------------------------------------------------------------
 # the MS-TCN second stage in one launch per direction (csrc/tconv.hip)
 TCONV = os.environ.get('TAMGCN_TCONV', '1') != '0'         # 0: every branch through tamgcn_conv / tamgcn_maxpool_fwd (A/B, tests)
 
@@ -272,26 +385,12 @@ def wgrad(gy, src, M, K, KT=1, dil=1, stride=1, pad=0, rows=None):
     T_in = src.x1.shape[2]
     per_clip = max(gy.x1.shape[1] * T_out * V, src.x1.shape[1] * T_in * V)
     chunks = n_chunks(N, per_clip) if N * per_clip > CHUNK_ELEMS else [(0, N)]
-    # same tile rule as wgrad_tile() in csrc/wgrad.hip: aim at ~4 resident workgroups per CU
-    taps = KT > 1 and stride == 1 and T_in == T_out and (M > 32 or K > 32 or (V % 4 != 0 and (M > 16 or K > 16)))      # one window per tap on the LDS-DMA kernel
-    if KT == 1 or taps:
-        bm, bk = (64 if M <= 64 else 128), (64 if K <= 64 else 128)
-    elif KT == 9:
-        bm = bk = 32
-    else:
-        bm = bk = 32 if (M <= 32 and K <= 32) else 64
     lib = _lib_()
-    tiles = ((M + bm - 1) // bm) * ((K + bk - 1) // bk) * (KT if taps else 1)
     descs = []
     for n0, n1 in chunks:
-        d = WgradDesc()
         g_, s_ = (gy, src) if len(chunks) == 1 else (_slice_src(gy, n0, n1), _slice_src(src, n0, n1))
-        d.gy, d.src = g_.c(), s_.c()
-        d.N, d.M, d.K, d.T_in, d.T_out, d.V = n1 - n0, M, K, T_in, T_out, V
-        d.KT, d.dil, d.stride, d.pad = KT, dil, stride, pad
-        descs.append((d, g_, s_))
-    per = max(1, (WGRAD_BLOCKS + tiles - 1) // tiles // len(chunks))
-    splits = [max(1, min(lib.tamgcn_wgrad_max_split(C.byref(d)), per)) for d, _, _ in descs]
+        descs.append((_wgrad_desc(g_, s_, M, K, KT, dil, stride, pad), g_, s_))
+    splits = [_wgrad_splits(d, len(chunks)) for d, _, _ in descs]
     nsplit = sum(splits)                                   # every chunk's partial slabs sit in ONE array: one reduction
     part = empty(nsplit, M, K, KT, like=gy.x1)
     off = 0
