@@ -125,6 +125,18 @@ typedef struct tamgcn_conv_desc {
 int tamgcn_conv_nparts(const tamgcn_conv_desc* d);
 int tamgcn_conv(const tamgcn_conv_desc* d, void* stream);
 
+/* ReLU sign bits.  The forward kernels that apply a ReLU can leave one bit per element (1 iff the stored value is > 0;
+ * -0.0, +0.0 and NaN give 0) beside their output, so that the backward reads 1/16 of a tensor pass instead of the activation.
+ * Layout of the bits of an (N, C, T, V) tensor: every (n, c) row of L = T*V floats has ceil(L / 4) bytes; byte i of a row
+ * holds elements 4i .. 4i+3 in bits 0 .. 3 (bits 4 .. 7 are 0).  Row (n, c) starts at byte (n*C + c) * ceil(L / 4).
+ *
+ * tamgcn_conv_signmask: tamgcn_conv with  y *= bit  in place of  y *= (mask_src > 0)  -- after bias, broadcast, add1 and
+ * add2, before the moments and the store; `bits` has bctot channels of T_y*V elements and row m of the output uses channel
+ * bcoff + m.  Served by the two-source, stride-1 form of the LDS-DMA GEMM only (V % 4 == 0, K % 16 == 0, no fp32 mask, no
+ * output affine, ostride 1, split mode 0 or M < 128); anything else is refused: mask with the element-wise kernels instead.
+ * Every element equals the one tamgcn_conv writes, or 0. */
+int tamgcn_conv_signmask(const tamgcn_conv_desc* d, const unsigned char* bits, int bctot, int bcoff, void* stream);
+
 /* Weight gradient of the same convolution (aten::convolution_backward, weight part):
  *   dW[m][k][j] = sum_{n,t,v} gy(n,m,t,v) * src(n,k,t*stride + j*dil - pad, v)
  * Both operands go through the prologue.  Split over n into `nsplit` partial
@@ -346,6 +358,13 @@ int tamgcn_gcn_tail_fwd(const tamgcn_src* y, const tamgcn_src* o, const tamgcn_s
 /* dsum = dg*(g>0); doz = dsum*(1-tanh(obn)^2); partials (sum doz, sum doz*(o_pre - o_save[c])) */
 int tamgcn_gcn_tail_bwd(const float* dg, const float* g, const tamgcn_src* o, const float* o_save,
                         int N, int C, int T, int V, float* dsum, float* doz, float* part, void* stream);
+/* The same two with sign bits (layout: see tamgcn_conv_signmask).  _fwd_bits also writes the bits of g.  _bwd_bits takes
+ * them in place of g; with bits == NULL and dsum == NULL, dg IS dsum already (its producer masked it: tamgcn_conv_signmask)
+ * and only doz and the partials are written.  Every output holds the bits tamgcn_gcn_tail_fwd / _bwd write. */
+int tamgcn_gcn_tail_fwd_bits(const tamgcn_src* y, const tamgcn_src* o, const tamgcn_src* res,
+                             int N, int C, int T, int V, float* g, unsigned char* bits, void* stream);
+int tamgcn_gcn_tail_bwd_bits(const float* dg, const unsigned char* bits, const tamgcn_src* o, const float* o_save,
+                             int N, int C, int T, int V, float* dsum, float* doz, float* part, void* stream);
 /* dyb = dsum - ddiff ; dres = dsum + ddiff (dres optional);
  * part[0..1] = (sum dyb, sum dyb*y_pre); part[2..3] = (sum dres, sum dres*r_pre) if r_pre given */
 int tamgcn_gcn_mid_bwd(const float* dsum, const float* ddiff, const float* y_pre, const float* y_save,
@@ -420,6 +439,13 @@ int tamgcn_add_act_fwd(const tamgcn_src* a, const tamgcn_src* res, int relu,
 int tamgcn_add_act_bwd(const float* dout, const float* out, int relu, const float* a_pre, const float* a_save,
                        const float* r_pre, const float* r_save,
                        int N, int C, int T, int V, float* dz, float* part, void* stream);
+/* relu = 1 with sign bits (layout: see tamgcn_conv_signmask): _fwd_bits also writes the bits of `out`, _bwd_bits takes them
+ * in place of `out`.  Every output holds the bits tamgcn_add_act_fwd / _bwd write. */
+int tamgcn_add_act_fwd_bits(const tamgcn_src* a, const tamgcn_src* res,
+                            int N, int C, int T, int V, float* out, float* rowmean, float* xbar, unsigned char* bits, void* stream);
+int tamgcn_add_act_bwd_bits(const float* dout, const unsigned char* bits, const float* a_pre, const float* a_save,
+                            const float* r_pre, const float* r_save,
+                            int N, int C, int T, int V, float* dz, float* part, void* stream);
 
 /* y = prologue value (materialise a src; used by stand-alone modules and tests) */
 int tamgcn_apply(const tamgcn_src* src, int N, int C, int T, int V, float* y, int yctot, int ycoff, void* stream);

@@ -161,6 +161,7 @@ SIGNATURES = {
     'tamgcn_conv': (_i, [C.POINTER(ConvDesc), _p]),
     'tamgcn_wgrad_max_split': (_i, [C.POINTER(WgradDesc)]),
     'tamgcn_wgrad': (_i, [C.POINTER(WgradDesc), _p]),
+    'tamgcn_conv_signmask': (_i, [C.POINTER(ConvDesc), _p, _i, _i, _p]),
     'tamgcn_conv_pair': (_i, [C.POINTER(ConvPairDesc), _p]),
     'tamgcn_wgrad_pair': (_i, [C.POINTER(WgradPairDesc), _p]),
     'tamgcn_stem_stats': (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
@@ -199,6 +200,8 @@ SIGNATURES = {
     'tamgcn_ew_nparts': (_i, [_i, _i, _i, _i]),
     'tamgcn_gcn_tail_fwd': (_i, [_SP, _SP, _SP, _i, _i, _i, _i, _p, _p]),
     'tamgcn_gcn_tail_bwd': (_i, [_p, _p, _SP, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    'tamgcn_gcn_tail_fwd_bits': (_i, [_SP, _SP, _SP, _i, _i, _i, _i, _p, _p, _p]),
+    'tamgcn_gcn_tail_bwd_bits': (_i, [_p, _p, _SP, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     'tamgcn_gcn_mid_bwd': (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     'tamgcn_tconv_supported': (_i, [_i, _i, _i, _i, C.POINTER(C.c_int), _i, _i]),
     'tamgcn_tconv_nparts': (_i, [C.POINTER(TconvDesc), _i]),
@@ -211,6 +214,8 @@ SIGNATURES = {
     'tamgcn_maxpool_bwd': (_i, [_SP, _SP, _p, _i, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p]),
     'tamgcn_add_act_fwd': (_i, [_SP, _SP, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     'tamgcn_add_act_bwd': (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    'tamgcn_add_act_fwd_bits': (_i, [_SP, _SP, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    'tamgcn_add_act_bwd_bits': (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     'tamgcn_apply': (_i, [_SP, _i, _i, _i, _i, _p, _i, _i, _p]),
     'tamgcn_score_fuse': (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     'tamgcn_ce_fwd': (_i, [_p, _p, _i, _i, _p, _p, _p]),

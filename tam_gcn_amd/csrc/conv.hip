@@ -62,6 +62,11 @@ struct PairArgs {
     float* y1; int yctot1, ycoff1;
     float* stats1; int sctot1, scoff1;
 };
+// The side argument of the sign-bit mask form (tamgcn_conv_signmask): the ReLU mask of the epilogue as one bit per element,
+// a byte per group of four consecutive floats of a (n, channel) row of T_y * V floats (the layout csrc/elementwise.hip writes).
+struct SignArgs {
+    const unsigned char* bits; int ctot, coff;
+};
 
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[4][MAXCW], float* Ss, int n, int m0, int t0,
                                               int ncols, int cw0, int mt_act, int c_act, const int (&tl)[MAXCW],
@@ -258,9 +263,11 @@ __global__ __launch_bounds__(NTHREADS) void conv_kernel(const ConvArgs a) {
 // Second half of the staged epilogue: rows r0..r0+RP-1 of the accumulator tile sit in LDS (Tt, pitch PT);
 // TPR threads walk one row in float4 steps: bias / broadcast / residual adds / mask / BatchNorm moments,
 // 16-byte coalesced loads and stores.  Row moments land in Ss[0..BMT) / Ss[4*BM..).
-template <int NTH, bool PR = false>
+// PR: 0 plain; 1 row split (PairArgs); 2 sign-bit mask (SignArgs: V % 4 == 0, so a group of four columns is one byte) applied where
+// the fp32 mask operand is: after bias, broadcast, the residual adds and plo, before the moments and the store.
+template <int NTH, int PR = 0, typename SIDE = PairArgs>
 __device__ __forceinline__ void staged_rows(const ConvArgs& a, const float* Tt, int PT, int RP, int r0, int BMT, int m0, int n, int t0,
-                                            int ncols, float* Ss, int Vs, int v0, const PairArgs* pa = nullptr) {
+                                            int ncols, float* Ss, int Vs, int v0, const SIDE* pa = nullptr) {
     const int tid = threadIdx.x, V = a.V;
     const int TPR = NTH / RP;
     const int row = tid / TPR, seg = tid - row * TPR;
@@ -280,7 +287,7 @@ __device__ __forceinline__ void staged_rows(const ConvArgs& a, const float* Tt, 
         const float pc1 = a.post_coef ? a.post_coef[a.ycoff + m] : 1.f, pc0 = a.post_coef ? a.post_coef[2 * a.post_ctot + a.ycoff + m] : 0.f;
         const float plo = a.post_act == 1 ? 0.f : -__builtin_inff();
         long long ybase = ((long long)n * a.yctot + a.ycoff + m) * a.T_y * V;
-        if constexpr (PR) {
+        if constexpr (PR == 1) {
             if (m >= pa->M0) {
                 const int m1 = m - pa->M0;
                 bia = pa->bias1 ? pa->bias1[m1] : 0.f; yp = pa->y1;
@@ -288,6 +295,8 @@ __device__ __forceinline__ void staged_rows(const ConvArgs& a, const float* Tt, 
             }
         }
         const long long mbase = a.has_mask ? ((long long)n * a.mask.ctot + a.mask.coff + m) * a.T_y * V : 0;
+        const unsigned char* sb = nullptr;
+        if constexpr (PR == 2) sb = pa->bits + ((long long)n * pa->ctot + pa->coff + m) * ((a.T_y * V + 3) >> 2);
         const long long abase = a.aux ? ((long long)n * a.auxctot + a.auxcoff + m) * a.T_y * V : 0;
         const float* bc = a.bcast ? a.bcast + ((long long)m * a.N + n) * V : nullptr;
         float mc1 = 1.f, mc2 = 0.f, mc0 = 0.f;
@@ -297,7 +306,21 @@ __device__ __forceinline__ void staged_rows(const ConvArgs& a, const float* Tt, 
             if (a.mask.x2) mc2 = a.mask.coef[a.mask.ctot + mch];
         }
         const int nc4 = (ncols + 3) >> 2;
-        for (int c4 = seg; c4 < nc4; c4 += TPR) {
+        // sign-bit mask: the lane's bytes of all its groups are requested HERE, in one batch with the row constants.  (Loaded per
+        // group, each byte got a full wait of its own behind the residual's: two dependent round trips per group, 61.5 against
+        // 58.3 us per launch at K = 16, profiles/signbits_step_ab.txt.)  The tile is flat (host-checked): group c4 of the row is byte (t0 * V) / 4 + c4; a lane has at most
+        // 320 / 4 / TPR = 5 groups -- beyond six nibbles a group loads its byte itself.
+        unsigned snib = 0;
+        if constexpr (PR == 2) {
+            const unsigned char* sp = sb + ((t0 * V) >> 2);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {                                // unconditional (a group past the tile re-reads the last one)
+                const int c = seg + k * TPR;
+                snib |= (unsigned)sp[c < nc4 ? c : nc4 - 1] << (4 * k);
+            }
+        }
+        int it = 0;
+        for (int c4 = seg; c4 < nc4; c4 += TPR, ++it) {
             const int col = c4 << 2;
             const int fr = col / Vs, v = col - fr * Vs;
             if ((vecok || v + 4 <= Vs) && col + 4 <= ncols) {
@@ -324,6 +347,13 @@ __device__ __forceinline__ void staged_rows(const ConvArgs& a, const float* Tt, 
                     if (!(fmaf(mc1, q.z, fmaf(mc2, q2.z, mc0)) > 0.f)) val.z = 0.f;
                     if (!(fmaf(mc1, q.w, fmaf(mc2, q2.w, mc0)) > 0.f)) val.w = 0.f;
                 }
+                if constexpr (PR == 2) {
+                    const unsigned q = it < 6 ? snib >> (4 * it) : sb[off >> 2];     // off % 4 == 0 (V % 4 == 0: host-checked)
+                    if (!(q & 1u)) val.x = 0.f;
+                    if (!(q & 2u)) val.y = 0.f;
+                    if (!(q & 4u)) val.z = 0.f;
+                    if (!(q & 8u)) val.w = 0.f;
+                }
                 if (a.stats_part) {
                     float4 x2 = val;
                     if (a.aux) {
@@ -348,6 +378,9 @@ __device__ __forceinline__ void staged_rows(const ConvArgs& a, const float* Tt, 
                     if (a.has_mask) {
                         const float q = a.mask.x1[mbase + off], q2 = a.mask.x2 ? a.mask.x2[mbase + off] : 0.f;
                         if (!(fmaf(mc1, q, fmaf(mc2, q2, mc0)) > 0.f)) val = 0.f;
+                    }
+                    if constexpr (PR == 2) {
+                        if (!((sb[off >> 2] >> (off & 3)) & 1u)) val = 0.f;
                     }
                     if (a.stats_part) {
                         const float x2 = a.aux ? a.aux[abase + off] - ctr : val;
@@ -623,9 +656,12 @@ constexpr int G_NT = 512, G_BMT = 64, G_PA = 80, G_PBMAX = 320, G_NST = 3, G_CWT
 // arithmetic of a B fragment are paid once per wave that reads it -- four row tiles per wave halve both.
 // PRO: the source carries a prologue (coefficients, second source or ReLU).  A plain tensor (the dx <- dx3 GEMMs, K = 3 C) needs neither
 // the [3][K] coefficient table -- which alone pushed K >= 384 past 80 KB, i.e. to ONE workgroup per CU -- nor the VALU on the fragments.
-// PAIR: 0 one GEMM; 1 the row-split form of tamgcn_conv_pair (PairArgs), a.M the stacked extent.
+// PAIR: 0 one GEMM; 1 the row-split form of tamgcn_conv_pair (PairArgs), a.M the stacked extent; 2 one GEMM whose epilogue masks
+// by sign bits (tamgcn_conv_signmask, SignArgs).
+template <int PAIR> struct GldsSide { typedef PairArgs type; };
+template <> struct GldsSide<2> { typedef SignArgs type; };
 template <int NSRC, int BK, bool PRO, int NW, int PAIR = 0>
-__global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void conv1x1_glds_kernel(const ConvArgs a, int ntt, int nmt, const PairArgs pa) {
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void conv1x1_glds_kernel(const ConvArgs a, int ntt, int nmt, const typename GldsSide<PAIR>::type pa) {
     constexpr int G_NT = NW * 64, G_MT = 16 / NW;                 // threads; row tiles per wave
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int STG = BK * G_PBMAX * NSRC + BK * G_PA;          // floats per stage
@@ -930,15 +966,19 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : 2) void conv1x1_glds_kernel(
             }
         }
         __syncthreads();
-        staged_rows<G_NT, PAIR == 1>(a, Tt, PT, RP, r0, G_BMT, m0, n, t0, ncols, Ss, V, 0, &pa);
+        staged_rows<G_NT, PAIR>(a, Tt, PT, RP, r0, G_BMT, m0, n, t0, ncols, Ss, V, 0, &pa);
     }
     if (a.stats_part) {
         __syncthreads();
         if (tid < 2 * G_BMT) {
             int stt = tid / G_BMT, row = tid - stt * G_BMT;
             int m = m0 + row;
-            if (PAIR == 1 && m < a.M && m >= pa.M0) pa.stats1[((long long)stt * pa.sctot1 + pa.scoff1 + m - pa.M0) * a.nparts + g] = Ss[stt * 4 * BM + row];
-            else if (m < a.M) a.stats_part[((long long)stt * a.stats_ctot + a.stats_coff + m) * a.nparts + g] = Ss[stt * 4 * BM + row];
+            if constexpr (PAIR == 1) {
+                if (m < a.M && m >= pa.M0) pa.stats1[((long long)stt * pa.sctot1 + pa.scoff1 + m - pa.M0) * a.nparts + g] = Ss[stt * 4 * BM + row];
+                else if (m < a.M) a.stats_part[((long long)stt * a.stats_ctot + a.stats_coff + m) * a.nparts + g] = Ss[stt * 4 * BM + row];
+            } else {
+                if (m < a.M) a.stats_part[((long long)stt * a.stats_ctot + a.stats_coff + m) * a.nparts + g] = Ss[stt * 4 * BM + row];
+            }
         }
     }
     TG_T(tg1); TG_ACC(7, tg1 - tg0); TG_ACC(8, tg1 - tt0); TG_ACC(9, 1);
@@ -1271,7 +1311,8 @@ extern "C" int tamgcn_conv_nparts(const tamgcn_conv_desc* d) {
     return d->N * p.ntt * p.nsl;
 }
 
-extern "C" int tamgcn_conv(const tamgcn_conv_desc* d, void* stream) {
+// sg: the sign-bit mask of tamgcn_conv_signmask (nullptr: tamgcn_conv)
+static int conv_launch(const tamgcn_conv_desc* d, const SignArgs* sg, void* stream) {
     TG_CHECK(d && d->src.x1 && d->w && d->y, "tamgcn_conv: null pointer");
     TG_CHECK(d->N > 0 && d->K > 0 && d->M > 0 && d->T_in > 0 && d->T_out > 0 && d->V > 0,
              "tamgcn_conv: bad dims N=%d K=%d M=%d T_in=%d T_out=%d V=%d", d->N, d->K, d->M, d->T_in, d->T_out, d->V);
@@ -1314,7 +1355,19 @@ extern "C" int tamgcn_conv(const tamgcn_conv_desc* d, void* stream) {
     const size_t lds_split = sizeof(float) * ((size_t)GS_NST * (GS_BK * G_PBMAX + GS_BK * 128) + 3 * (size_t)d->K + 2 * 4 * BM + 128);
     const bool big = glds && tamgcn_split_mode() >= 1 && d->src.act == 0 && d->M >= 128 && d->M % 4 == 0 && d->K % GS_BK == 0 &&
                      lds_split <= 160 * 1024 && !d->post_coef && d->wmode == 1 && !d->stats_part;
-    if (big) {
+    if (sg) {
+        // the sign-bit mask lives in ONE instantiation, the one its caller runs (the MS-TCN plain branch's data gradient:
+        // two-source prologue, eight waves); everything else is refused -- the caller masks with its element-wise kernel instead
+        static int nw8 = -1;
+        if (nw8 < 0) { const char* e = getenv("TAMGCN_CONV_WAVES"); nw8 = (e && atoi(e) == 4) ? 0 : 1; }
+        TG_CHECK(glds && !big && p.flat && d->src.x2 && nw8 && (d->V & 3) == 0 && !d->mask && !d->post_coef,
+                 "tamgcn_conv_signmask: not the two-source stride-1 LDS-DMA GEMM with V %% 4 == 0 (K=%d M=%d T=%d V=%d)", d->K, d->M, d->T_in, d->V);
+        const int nmt = ceil_div(d->M, G_BMT);
+        const unsigned nblk = (unsigned)(d->N * p.ntt * nmt);
+        tg_launch_lds<conv1x1_glds_kernel<2, 8, true, 8, 2>>(160 * 1024, dim3(nblk), dim3(8 * 64), glds_lds_bytes<2, 8>(d->K, true),
+                                                             (hipStream_t)stream, a, p.ntt, nmt, *sg);
+        tamgcn_note_kernel("conv1x1_glds_kernel<2, 8, true, 8, 2>");
+    } else if (big) {
         const int nmt = ceil_div(d->M, 128);
         const unsigned nblk = (unsigned)(d->N * p.ntt * nmt);
         tg_launch_lds<conv1x1_glds_split_kernel<2, false, 4>>(160 * 1024, dim3(nblk), dim3(G_NT), lds_split, (hipStream_t)stream, a, p.ntt, nmt);
@@ -1359,6 +1412,18 @@ extern "C" int tamgcn_conv(const tamgcn_conv_desc* d, void* stream) {
     }
     TG_LAUNCH_CHECK("tamgcn_conv");
     return 0;
+}
+
+extern "C" int tamgcn_conv(const tamgcn_conv_desc* d, void* stream) { return conv_launch(d, nullptr, stream); }
+
+// tamgcn_conv whose epilogue zeroes y where a sign bit is 0, at the place of the fp32 mask operand (after bias, broadcast and the
+// residual adds, before the moments and the store): the same bits as tamgcn_conv followed by that select.
+extern "C" int tamgcn_conv_signmask(const tamgcn_conv_desc* d, const unsigned char* bits, int bctot, int bcoff, void* stream) {
+    TG_CHECK(d && bits, "tamgcn_conv_signmask: null pointer");
+    TG_CHECK(bcoff >= 0 && bcoff + d->M <= bctot, "tamgcn_conv_signmask: mask channel slice out of range");
+    TG_CHECK(d->ostride == 1 && d->T_out == d->T_y, "tamgcn_conv_signmask: the output covers every frame of y (ostride 1)");
+    const SignArgs sg = {bits, bctot, bcoff};
+    return conv_launch(d, &sg, stream);
 }
 
 

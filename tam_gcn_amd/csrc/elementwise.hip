@@ -49,6 +49,29 @@ __device__ __forceinline__ void row_store_sums(const float* vals, int nst, float
     }
 }
 
+// ---- ReLU sign bits --------------------------------------------------------
+// One bit per element, set iff the stored activation is > 0.f (the test its backward applies; -0.0, +0.0 and NaN give 0), so
+// that the backward reads 1/16 of a tensor pass instead of the activation.  Layout: every (n, c) row of L floats has
+// sign_row_bytes(L) = ceil(L / 4) bytes; byte i holds elements 4i .. 4i+3 in bits 0 .. 3 -- the byte of the float4 a lane
+// holds anyway.  The last byte of a row with L % 4 != 0 is assembled from the scalar tail's lanes (sign_tail_store).
+__device__ __forceinline__ unsigned sign4(const float4& v) {
+    return (v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u);
+}
+// the scalar tail: lanes 0 .. (L % 4) - 1 of the row hold one element each (tb = their bit, shifted to its place; 0 elsewhere).
+// Every thread of the workgroup calls it; lanes 0 .. 3 of a row are neighbours in one wave (tpr >= 16).
+__device__ __forceinline__ void sign_tail_store(unsigned tb, unsigned char* brow, int L, int li) {
+    tb |= __shfl_xor(tb, 1);
+    tb |= __shfl_xor(tb, 2);
+    if (li == 0 && (L & 3)) brow[L >> 2] = (unsigned char)tb;
+}
+__device__ __forceinline__ float4 sign_mask4(float4 d, unsigned q) {
+    if (!(q & 1u)) d.x = 0.f;
+    if (!(q & 2u)) d.y = 0.f;
+    if (!(q & 4u)) d.z = 0.f;
+    if (!(q & 8u)) d.w = 0.f;
+    return d;
+}
+
 // float4 view of the fused prologue for one channel row (coefficients are per channel)
 struct RowSrc {
     const float* x1; const float* x2; float c1, c2, c0; int act;
@@ -81,7 +104,7 @@ __device__ __forceinline__ float4 row_val4(const RowSrc& r, int i4) {
 
 // ---- unit_gcn tail -------------------------------------------------------
 __global__ __launch_bounds__(EW_THREADS) void gcn_tail_fwd_kernel(RowGeo geo, SrcDev y, SrcDev o, SrcDev res, int has_res,
-                                                                  int C, int L, float* g) {
+                                                                  int C, int L, float* g, unsigned char* bits) {
     int c, n, li;
     const bool rowok = row_coords(geo, C, c, n, li);
     if (!rowok) L = 0;                     // idle lanes only take part in the shuffles
@@ -90,6 +113,8 @@ __global__ __launch_bounds__(EW_THREADS) void gcn_tail_fwd_kernel(RowGeo geo, Sr
     RowSrc rr = ry;
     if (has_res) rr = row_src(res, ((long long)n * res.ctot + res.coff + c) * L, res.coff + c);
     float* gp = g + ((long long)n * C + c) * L;
+    unsigned char* brow = bits ? bits + ((long long)n * C + c) * ((L + 3) >> 2) : nullptr;
+    unsigned tb = 0;
     {                                      // groups of four floats (rows need only be 4-byte aligned: V = 25), then the row's tail
         for (int i = li; i < (L >> 2); i += geo.tpr) {
             float4 a = row_val4(ry, i), b = row_val4(ro, i);
@@ -98,38 +123,55 @@ __global__ __launch_bounds__(EW_THREADS) void gcn_tail_fwd_kernel(RowGeo geo, Sr
             v.x = fmaxf(a.x + tanhf(b.x) + r.x, 0.f); v.y = fmaxf(a.y + tanhf(b.y) + r.y, 0.f);
             v.z = fmaxf(a.z + tanhf(b.z) + r.z, 0.f); v.w = fmaxf(a.w + tanhf(b.w) + r.w, 0.f);
             reinterpret_cast<float4*>(gp)[i] = v;
+            if (brow) brow[i] = (unsigned char)sign4(v);
         }
     }
     {
         for (int i = (L & ~3) + li; i < L; i += geo.tpr) {
             float v = row_val(ry, i) + tanhf(row_val(ro, i));
             if (has_res) v += row_val(rr, i);
-            gp[i] = fmaxf(v, 0.f);
+            v = fmaxf(v, 0.f);
+            gp[i] = v;
+            if (v > 0.f) tb |= 1u << (i & 3);
         }
     }
+    if (bits) sign_tail_store(tb, brow, L, li);     // uniform over the launch: every lane of the wave reaches the shuffles
 }
 
-__global__ __launch_bounds__(EW_THREADS) void gcn_tail_bwd_kernel(RowGeo geo, const float* dg, const float* g, SrcDev o, const float* o_save,
-                                                                  int C, int L, int N, float* dsum, float* doz, float* part) {
+// SIGN: where the ReLU mask of g comes from.  0: the saved activation g itself (g > 0); 1: its sign bits (form (b): dg in, dsum out);
+// 2: nowhere -- dg is dsum already, masked by its producer's epilogue (form (a): g is not read, dsum is not written).
+// One body: the three forms share every expression and the order of the sums.
+template <int SIGN>
+__device__ __forceinline__ void gcn_tail_bwd_body(const RowGeo& geo, const float* dg, const float* g, const unsigned char* bits, const SrcDev& o,
+                                                  const float* o_save, int C, int L, int N, float* dsum, float* doz, float* part) {
     int c, n, li;
     const bool rowok = row_coords(geo, C, c, n, li);
     if (!rowok) L = 0;                     // idle lanes only take part in the shuffles
     const long long b = ((long long)n * C + c) * L;
     const long long bo = ((long long)n * o.ctot + o.coff + c) * L;
+    const unsigned char* brow = SIGN == 1 ? bits + ((long long)n * C + c) * ((L + 3) >> 2) : nullptr;
     const RowSrc ro = row_src(o, bo, o.coff + c);
     float s[2] = {0.f, 0.f};
     const float mu = o_save[o.coff + c];
     {                                      // groups of four floats (rows need only be 4-byte aligned: V = 25), then the row's tail
         for (int i = li; i < (L >> 2); i += geo.tpr) {
-            float4 gg = reinterpret_cast<const float4*>(g + b)[i], dd = reinterpret_cast<const float4*>(dg + b)[i];
+            float4 dd = reinterpret_cast<const float4*>(dg + b)[i];
             float4 ob = row_val4(ro, i), op = reinterpret_cast<const float4*>(o.x1 + bo)[i];
             float4 d, z;
             float t;
-            d.x = gg.x > 0.f ? dd.x : 0.f; t = tanhf(ob.x); z.x = d.x * (1.f - t * t);
-            d.y = gg.y > 0.f ? dd.y : 0.f; t = tanhf(ob.y); z.y = d.y * (1.f - t * t);
-            d.z = gg.z > 0.f ? dd.z : 0.f; t = tanhf(ob.z); z.z = d.z * (1.f - t * t);
-            d.w = gg.w > 0.f ? dd.w : 0.f; t = tanhf(ob.w); z.w = d.w * (1.f - t * t);
-            reinterpret_cast<float4*>(dsum + b)[i] = d;
+            if (SIGN == 0) {
+                float4 gg = reinterpret_cast<const float4*>(g + b)[i];
+                d.x = gg.x > 0.f ? dd.x : 0.f; d.y = gg.y > 0.f ? dd.y : 0.f; d.z = gg.z > 0.f ? dd.z : 0.f; d.w = gg.w > 0.f ? dd.w : 0.f;
+            } else if (SIGN == 1) {
+                d = sign_mask4(dd, brow[i]);
+            } else {
+                d = dd;
+            }
+            t = tanhf(ob.x); z.x = d.x * (1.f - t * t);
+            t = tanhf(ob.y); z.y = d.y * (1.f - t * t);
+            t = tanhf(ob.z); z.z = d.z * (1.f - t * t);
+            t = tanhf(ob.w); z.w = d.w * (1.f - t * t);
+            if (SIGN != 2) reinterpret_cast<float4*>(dsum + b)[i] = d;
             reinterpret_cast<float4*>(doz + b)[i] = z;
             s[0] += (z.x + z.y) + (z.z + z.w);
             s[1] = fmaf(z.x, op.x - mu, fmaf(z.y, op.y - mu, fmaf(z.z, op.z - mu, fmaf(z.w, op.w - mu, s[1]))));
@@ -137,16 +179,25 @@ __global__ __launch_bounds__(EW_THREADS) void gcn_tail_bwd_kernel(RowGeo geo, co
     }
     {
         for (int i = (L & ~3) + li; i < L; i += geo.tpr) {
-            float d = g[b + i] > 0.f ? dg[b + i] : 0.f;
+            float d = dg[b + i];
+            if (SIGN == 0) d = g[b + i] > 0.f ? d : 0.f;
+            if (SIGN == 1) d = ((brow[i >> 2] >> (i & 3)) & 1) ? d : 0.f;
             float off = tanhf(row_val(ro, i));
             float dz = d * (1.f - off * off);
-            dsum[b + i] = d;
+            if (SIGN != 2) dsum[b + i] = d;
             doz[b + i] = dz;
             s[0] += dz;
             s[1] = fmaf(dz, o.x1[bo + i] - mu, s[1]);
         }
     }
     row_store_sums(s, 2, part, C, N, c, n, geo, li, rowok);
+}
+// one kernel, three loops: which one runs is uniform over the launch (g: today's form; bits: form (b); neither: form (a))
+__global__ __launch_bounds__(EW_THREADS) void gcn_tail_bwd_kernel(RowGeo geo, const float* dg, const float* g, const unsigned char* bits, SrcDev o,
+                                                                  const float* o_save, int C, int L, int N, float* dsum, float* doz, float* part) {
+    if (g) gcn_tail_bwd_body<0>(geo, dg, g, nullptr, o, o_save, C, L, N, dsum, doz, part);
+    else if (bits) gcn_tail_bwd_body<1>(geo, dg, nullptr, bits, o, o_save, C, L, N, dsum, doz, part);
+    else gcn_tail_bwd_body<2>(geo, dg, nullptr, nullptr, o, o_save, C, L, N, nullptr, doz, part);
 }
 
 __global__ __launch_bounds__(EW_THREADS) void gcn_mid_bwd_kernel(RowGeo geo, const float* dsum, const float* ddiff, const float* y_pre, const float* y_save,
@@ -450,7 +501,7 @@ __global__ __launch_bounds__(EW_THREADS) void maxpool_bwd_flat_kernel(RowGeo geo
 // rowmean != nullptr: also the mean of every output row (the last block's contribution to the model head's pooling,
 // models/ctrgcn.py:343-345, taken while the row is in registers)
 __global__ __launch_bounds__(EW_THREADS) void add_act_fwd_kernel(RowGeo geo, SrcDev a, SrcDev res, int has_res, int relu,
-                                                                 int C, int L, float* out, float* rowmean) {
+                                                                 int C, int L, float* out, float* rowmean, unsigned char* bits) {
     int c, n, li;
     const bool rowok = row_coords(geo, C, c, n, li);
     if (!rowok) L = 0;                     // idle lanes only take part in the shuffles
@@ -458,6 +509,8 @@ __global__ __launch_bounds__(EW_THREADS) void add_act_fwd_kernel(RowGeo geo, Src
     RowSrc rr = ra;
     if (has_res) rr = row_src(res, ((long long)n * res.ctot + res.coff + c) * L, res.coff + c);
     float* op = out + ((long long)n * C + c) * L;
+    unsigned char* brow = bits ? bits + ((long long)n * C + c) * ((L + 3) >> 2) : nullptr;
+    unsigned tb = 0;
     const int Lrow = L;
     float acc = 0.f;
     {                                      // groups of four floats (rows need only be 4-byte aligned: V = 25), then the row's tail
@@ -466,6 +519,7 @@ __global__ __launch_bounds__(EW_THREADS) void add_act_fwd_kernel(RowGeo geo, Src
             if (has_res) { float4 r = row_val4(rr, i); v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
             if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
             reinterpret_cast<float4*>(op)[i] = v;
+            if (brow) brow[i] = (unsigned char)sign4(v);
             acc += (v.x + v.y) + (v.z + v.w);
         }
     }
@@ -475,29 +529,35 @@ __global__ __launch_bounds__(EW_THREADS) void add_act_fwd_kernel(RowGeo geo, Src
             if (has_res) v += row_val(rr, i);
             v = relu ? fmaxf(v, 0.f) : v;
             op[i] = v;
+            if (v > 0.f) tb |= 1u << (i & 3);
             acc += v;
         }
     }
+    if (bits) sign_tail_store(tb, brow, L, li);     // uniform over the launch: every lane of the wave reaches the shuffles
     if (rowmean) {                          // uniform over the launch: every lane of the wave reaches the shuffles
         acc = row_sum(acc, geo);
         if (li == 0 && rowok) rowmean[(long long)n * C + c] = acc / (float)Lrow;
     }
 }
 
-__global__ __launch_bounds__(EW_THREADS) void add_act_bwd_kernel(RowGeo geo, const float* dout, const float* out, int relu,
-                                                                 const float* a_pre, const float* a_save,
-                                                                 const float* r_pre, const float* r_save,
-                                                                 int C, int L, int N, float* dz, float* part) {
+// BITS: the ReLU mask of `out` comes from its sign bits instead of the activation (one body: the same expressions and sums)
+template <bool BITS>
+__device__ __forceinline__ void add_act_bwd_body(const RowGeo& geo, const float* dout, const float* out, const unsigned char* bits, int relu,
+                                                 const float* a_pre, const float* a_save, const float* r_pre, const float* r_save,
+                                                 int C, int L, int N, float* dz, float* part) {
     int c, n, li;
     const bool rowok = row_coords(geo, C, c, n, li);
     if (!rowok) L = 0;                     // idle lanes only take part in the shuffles
     const long long b = ((long long)n * C + c) * L;
+    const unsigned char* brow = BITS ? bits + ((long long)n * C + c) * ((L + 3) >> 2) : nullptr;
     float s[4] = {0.f, 0.f, 0.f, 0.f};
     const float mua = a_pre ? a_save[c] : 0.f, mur = r_pre ? r_save[c] : 0.f;
     {                                      // groups of four floats (rows need only be 4-byte aligned: V = 25), then the row's tail
         for (int i = li; i < (L >> 2); i += geo.tpr) {
             float4 d = reinterpret_cast<const float4*>(dout + b)[i];
-            if (relu) {
+            if (BITS) {
+                d = sign_mask4(d, brow[i]);
+            } else if (relu) {
                 float4 o = reinterpret_cast<const float4*>(out + b)[i];
                 if (!(o.x > 0.f)) d.x = 0.f;
                 if (!(o.y > 0.f)) d.y = 0.f;
@@ -520,7 +580,8 @@ __global__ __launch_bounds__(EW_THREADS) void add_act_bwd_kernel(RowGeo geo, con
     {
         for (int i = (L & ~3) + li; i < L; i += geo.tpr) {
             float d = dout[b + i];
-            if (relu && !(out[b + i] > 0.f)) d = 0.f;
+            if (BITS) { if (!((brow[i >> 2] >> (i & 3)) & 1)) d = 0.f; }
+            else if (relu && !(out[b + i] > 0.f)) d = 0.f;
             if (dz) dz[b + i] = d;
             s[0] += d;
             if (a_pre) s[1] = fmaf(d, a_pre[b + i] - mua, s[1]);
@@ -528,6 +589,13 @@ __global__ __launch_bounds__(EW_THREADS) void add_act_bwd_kernel(RowGeo geo, con
         }
     }
     row_store_sums(s, r_pre ? 4 : 2, part, C, N, c, n, geo, li, rowok);
+}
+__global__ __launch_bounds__(EW_THREADS) void add_act_bwd_kernel(RowGeo geo, const float* dout, const float* out, const unsigned char* bits, int relu,
+                                                                 const float* a_pre, const float* a_save,
+                                                                 const float* r_pre, const float* r_save,
+                                                                 int C, int L, int N, float* dz, float* part) {
+    if (bits) add_act_bwd_body<true>(geo, dout, nullptr, bits, 1, a_pre, a_save, r_pre, r_save, C, L, N, dz, part);     // uniform over the launch
+    else add_act_bwd_body<false>(geo, dout, out, nullptr, relu, a_pre, a_save, r_pre, r_save, C, L, N, dz, part);
 }
 
 __global__ __launch_bounds__(EW_THREADS) void apply_kernel(RowGeo geo, SrcDev src, int C, int L, float* y, int yctot, int ycoff) {
@@ -546,7 +614,7 @@ __global__ __launch_bounds__(EW_THREADS) void apply_kernel(RowGeo geo, SrcDev sr
 // float4; the sums over the F frame phases and then over the four groups are fixed-order shuffle chains: deterministic, graph
 // replay = eager bit for bit.
 __global__ __launch_bounds__(EW_THREADS) void add_act_fwd_tmean_kernel(SrcDev a, SrcDev res, int has_res, int relu, int N, int C, int T, int V,
-                                                                       float* out, float* xbar) {
+                                                                       float* out, float* xbar, unsigned char* bits) {
     const int row = blockIdx.x * (EW_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int sub = lane >> 4, l = lane & 15;
     const int V4 = V >> 2, F = 16 / V4;
@@ -560,6 +628,7 @@ __global__ __launch_bounds__(EW_THREADS) void add_act_fwd_tmean_kernel(SrcDev a,
     RowSrc rr = ra;
     if (has_res) rr = row_src(res, ((long long)n * res.ctot + res.coff + c) * L, res.coff + c);
     float* op = out + ((long long)n * C + c) * L;
+    unsigned char* brow = bits ? bits + ((long long)n * C + c) * (L >> 2) : nullptr;     // V % 4 == 0: whole groups
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     if (lane_on) {
         for (int t = f + F * sub; t < T; t += 4 * F) {
@@ -568,6 +637,7 @@ __global__ __launch_bounds__(EW_THREADS) void add_act_fwd_tmean_kernel(SrcDev a,
             if (has_res) { const float4 q = row_val4(rr, i4); v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
             if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
             reinterpret_cast<float4*>(op)[i4] = v;
+            if (brow) brow[i4] = (unsigned char)sign4(v);
             acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
         }
     }
@@ -627,15 +697,24 @@ static dim3 row_grid(const RowGeo& g) { return dim3((unsigned)ceil_div(g.rows, E
 
 extern "C" int tamgcn_ew_nparts(int N, int C, int T, int V) { (void)C; (void)T; (void)V; return N; }
 
-extern "C" int tamgcn_gcn_tail_fwd(const tamgcn_src* y, const tamgcn_src* o, const tamgcn_src* res,
-                                   int N, int C, int T, int V, float* g, void* stream) {
-    TG_CHECK(y && o && g && y->x1 && o->x1 && grid_ok(N, C), "tamgcn_gcn_tail_fwd: bad args");
+static int gcn_tail_fwd_launch(const char* who, const tamgcn_src* y, const tamgcn_src* o, const tamgcn_src* res,
+                               int N, int C, int T, int V, float* g, unsigned char* bits, void* stream) {
+    TG_CHECK(y && o && g && y->x1 && o->x1 && grid_ok(N, C), "%s: bad args", who);
     const RowGeo geo = row_geo(N, C, T * V, true);
     hipLaunchKernelGGL(gcn_tail_fwd_kernel, row_grid(geo), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                       geo, make_src(*y), make_src(*o), res ? make_src(*res) : null_src(), res ? 1 : 0, C, T * V, g);
+                       geo, make_src(*y), make_src(*o), res ? make_src(*res) : null_src(), res ? 1 : 0, C, T * V, g, bits);
     tamgcn_note_kernel("gcn_tail_fwd_kernel");
-    TG_LAUNCH_CHECK("tamgcn_gcn_tail_fwd");
+    TG_LAUNCH_CHECK(who);
     return 0;
+}
+extern "C" int tamgcn_gcn_tail_fwd(const tamgcn_src* y, const tamgcn_src* o, const tamgcn_src* res,
+                                   int N, int C, int T, int V, float* g, void* stream) {
+    return gcn_tail_fwd_launch("tamgcn_gcn_tail_fwd", y, o, res, N, C, T, V, g, nullptr, stream);
+}
+extern "C" int tamgcn_gcn_tail_fwd_bits(const tamgcn_src* y, const tamgcn_src* o, const tamgcn_src* res,
+                                        int N, int C, int T, int V, float* g, unsigned char* bits, void* stream) {
+    TG_CHECK(bits, "tamgcn_gcn_tail_fwd_bits: no sign-bit output (use tamgcn_gcn_tail_fwd)");
+    return gcn_tail_fwd_launch("tamgcn_gcn_tail_fwd_bits", y, o, res, N, C, T, V, g, bits, stream);
 }
 
 extern "C" int tamgcn_gcn_tail_bwd(const float* dg, const float* g, const tamgcn_src* o, const float* o_save,
@@ -643,9 +722,22 @@ extern "C" int tamgcn_gcn_tail_bwd(const float* dg, const float* g, const tamgcn
     TG_CHECK(dg && g && o && o->x1 && o_save && dsum && doz && part && grid_ok(N, C), "tamgcn_gcn_tail_bwd: bad args");
     const RowGeo geo = row_geo(N, C, T * V, true);
     hipLaunchKernelGGL(gcn_tail_bwd_kernel, row_grid(geo), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                       geo, dg, g, make_src(*o), o_save, C, T * V, N, dsum, doz, part);
+                       geo, dg, g, (const unsigned char*)nullptr, make_src(*o), o_save, C, T * V, N, dsum, doz, part);
     tamgcn_note_kernel("gcn_tail_bwd_kernel");
     TG_LAUNCH_CHECK("tamgcn_gcn_tail_bwd");
+    return 0;
+}
+
+extern "C" int tamgcn_gcn_tail_bwd_bits(const float* dg, const unsigned char* bits, const tamgcn_src* o, const float* o_save,
+                                        int N, int C, int T, int V, float* dsum, float* doz, float* part, void* stream) {
+    TG_CHECK(dg && o && o->x1 && o_save && doz && part && grid_ok(N, C), "tamgcn_gcn_tail_bwd_bits: bad args");
+    TG_CHECK((bits != nullptr) == (dsum != nullptr),
+             "tamgcn_gcn_tail_bwd_bits: sign bits and dsum go together (both: dg is masked here; neither: dg is dsum already)");
+    const RowGeo geo = row_geo(N, C, T * V, true);
+    hipLaunchKernelGGL(gcn_tail_bwd_kernel, row_grid(geo), dim3(EW_THREADS), 0, (hipStream_t)stream,
+                       geo, dg, (const float*)nullptr, bits, make_src(*o), o_save, C, T * V, N, dsum, doz, part);
+    tamgcn_note_kernel("gcn_tail_bwd_kernel");
+    TG_LAUNCH_CHECK("tamgcn_gcn_tail_bwd_bits");
     return 0;
 }
 
@@ -725,26 +817,35 @@ extern "C" int tamgcn_maxpool_bwd(const tamgcn_src* gy, const tamgcn_src* src, c
     return 0;
 }
 
-extern "C" int tamgcn_add_act_fwd(const tamgcn_src* a, const tamgcn_src* res, int relu,
-                                  int N, int C, int T, int V, float* out, float* rowmean, float* xbar, void* stream) {
-    TG_CHECK(a && a->x1 && out && grid_ok(N, C), "tamgcn_add_act_fwd: bad args");
+static int add_act_fwd_launch(const char* who, const tamgcn_src* a, const tamgcn_src* res, int relu,
+                              int N, int C, int T, int V, float* out, float* rowmean, float* xbar, unsigned char* bits, void* stream) {
+    TG_CHECK(a && a->x1 && out && grid_ok(N, C), "%s: bad args", who);
     if (xbar) {
         TG_CHECK(!rowmean && (V & 3) == 0 && V <= 64, "tamgcn_add_act_fwd: the frame-mean output needs V %% 4 == 0, V <= 64 and no row-mean output");
         const bool al16 = (((uintptr_t)a->x1 | (uintptr_t)(a->x2 ? a->x2 : a->x1) | (uintptr_t)out | (uintptr_t)xbar |
                             (uintptr_t)(res ? res->x1 : a->x1) | (uintptr_t)((res && res->x2) ? res->x2 : a->x1)) & 15) == 0;
         TG_CHECK(al16, "tamgcn_add_act_fwd: the frame-mean form needs 16-byte aligned operands");
         hipLaunchKernelGGL(add_act_fwd_tmean_kernel, dim3((unsigned)ceil_div(N * C, EW_THREADS / 64)), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                           make_src(*a), res ? make_src(*res) : null_src(), res ? 1 : 0, relu, N, C, T, V, out, xbar);
+                           make_src(*a), res ? make_src(*res) : null_src(), res ? 1 : 0, relu, N, C, T, V, out, xbar, bits);
         tamgcn_note_kernel("add_act_fwd_tmean_kernel");
-        TG_LAUNCH_CHECK("tamgcn_add_act_fwd");
+        TG_LAUNCH_CHECK(who);
         return 0;
     }
     const RowGeo geo = row_geo(N, C, T * V, true);
     hipLaunchKernelGGL(add_act_fwd_kernel, row_grid(geo), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                       geo, make_src(*a), res ? make_src(*res) : null_src(), res ? 1 : 0, relu, C, T * V, out, rowmean);
+                       geo, make_src(*a), res ? make_src(*res) : null_src(), res ? 1 : 0, relu, C, T * V, out, rowmean, bits);
     tamgcn_note_kernel("add_act_fwd_kernel");
-    TG_LAUNCH_CHECK("tamgcn_add_act_fwd");
+    TG_LAUNCH_CHECK(who);
     return 0;
+}
+extern "C" int tamgcn_add_act_fwd(const tamgcn_src* a, const tamgcn_src* res, int relu,
+                                  int N, int C, int T, int V, float* out, float* rowmean, float* xbar, void* stream) {
+    return add_act_fwd_launch("tamgcn_add_act_fwd", a, res, relu, N, C, T, V, out, rowmean, xbar, nullptr, stream);
+}
+extern "C" int tamgcn_add_act_fwd_bits(const tamgcn_src* a, const tamgcn_src* res,
+                                       int N, int C, int T, int V, float* out, float* rowmean, float* xbar, unsigned char* bits, void* stream) {
+    TG_CHECK(bits, "tamgcn_add_act_fwd_bits: no sign-bit output (use tamgcn_add_act_fwd)");
+    return add_act_fwd_launch("tamgcn_add_act_fwd_bits", a, res, 1, N, C, T, V, out, rowmean, xbar, bits, stream);
 }
 
 extern "C" int tamgcn_add_act_bwd(const float* dout, const float* out, int relu, const float* a_pre, const float* a_save,
@@ -753,9 +854,21 @@ extern "C" int tamgcn_add_act_bwd(const float* dout, const float* out, int relu,
     TG_CHECK(dout && part && grid_ok(N, C) && (!relu || out) && (!a_pre || a_save) && (!r_pre || r_save), "tamgcn_add_act_bwd: bad args");
     const RowGeo geo = row_geo(N, C, T * V, true);
     hipLaunchKernelGGL(add_act_bwd_kernel, row_grid(geo), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                       geo, dout, out, relu, a_pre, a_save, r_pre, r_save, C, T * V, N, dz, part);
+                       geo, dout, out, (const unsigned char*)nullptr, relu, a_pre, a_save, r_pre, r_save, C, T * V, N, dz, part);
     tamgcn_note_kernel("add_act_bwd_kernel");
     TG_LAUNCH_CHECK("tamgcn_add_act_bwd");
+    return 0;
+}
+
+extern "C" int tamgcn_add_act_bwd_bits(const float* dout, const unsigned char* bits, const float* a_pre, const float* a_save,
+                                       const float* r_pre, const float* r_save,
+                                       int N, int C, int T, int V, float* dz, float* part, void* stream) {
+    TG_CHECK(dout && bits && part && grid_ok(N, C) && (!a_pre || a_save) && (!r_pre || r_save), "tamgcn_add_act_bwd_bits: bad args");
+    const RowGeo geo = row_geo(N, C, T * V, true);
+    hipLaunchKernelGGL(add_act_bwd_kernel, row_grid(geo), dim3(EW_THREADS), 0, (hipStream_t)stream,
+                       geo, dout, (const float*)nullptr, bits, 1, a_pre, a_save, r_pre, r_save, C, T * V, N, dz, part);
+    tamgcn_note_kernel("add_act_bwd_kernel");
+    TG_LAUNCH_CHECK("tamgcn_add_act_bwd_bits");
     return 0;
 }
 

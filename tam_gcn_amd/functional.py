@@ -319,23 +319,26 @@ def gcn_forward(x, P, training, save):
     else:
         coef_o, save_o = _coef(Cout, x)
         P.bno.fwd(opart, 0, count, training, coef_o, save_o, 0)
-    g = ops.gcn_tail_fwd(S(y_pre, coef=coef_y), S(o_pre, coef=coef_o), res)
+    sign = [] if save and ops.SIGNBITS else None       # the sign bits of g ride along for the backward (ops.SIGNBITS)
+    g = ops.gcn_tail_fwd(S(y_pre, coef=coef_y), S(o_pre, coef=coef_o), res, sign=sign)
     sv = None
     if save:
         sv = dict(x=x, xbar=xbar, pq=pq, x3=x3, E=E, y_pre=y_pre, d_pre=d_pre, o_pre=o_pre, g=g, coef_y=coef_y, save_y=save_y,
                   coef_d=coef_d, save_d=save_d, coef_o=coef_o, save_o=save_o, coef_diff=coef_diff,
-                  training=training)
+                  training=training, gbits=sign[0] if sign else None)
     return g, sv
 
 
-def gcn_backward(P, sv, dg, need_dx=True, extra_dx=None):
+def gcn_backward(P, sv, dg, need_dx=True, extra_dx=None, dg_masked=False):
     """Returns (dx, grads) with grads keyed like GcnParams' tensors.  All partial-slab reductions of the weight and
-    parameter gradients are deferred into ONE launch after the side streams have joined (ops.ReduceBatch)."""
+    parameter gradients are deferred into ONE launch after the side streams have joined (ops.ReduceBatch).
+    dg_masked: dg is dg * (g > 0) already (tcn_backward's last GEMM applied g's sign bits, inside one autograd node only:
+    a gradient that autograd delivers is never assumed masked)."""
     with ops.ReduceBatch():
-        return _gcn_backward(P, sv, dg, need_dx, extra_dx)
+        return _gcn_backward(P, sv, dg, need_dx, extra_dx, dg_masked)
 
 
-def _gcn_backward(P, sv, dg, need_dx=True, extra_dx=None):
+def _gcn_backward(P, sv, dg, need_dx=True, extra_dx=None, dg_masked=False):
     x, xbar, pq, y_pre, d_pre, o_pre, g = sv['x'], sv['xbar'], sv['pq'], sv['y_pre'], sv['d_pre'], sv['o_pre'], sv['g']
     training = sv['training']
     N, Cin, T, V = x.shape
@@ -345,7 +348,13 @@ def _gcn_backward(P, sv, dg, need_dx=True, extra_dx=None):
     fk = Fork(x.device, 2)
     fk.__enter__()
     # tail: relu, tanh(BN(offset conv))
-    dsum, doz, part_o = ops.gcn_tail_bwd(dg, g, S(o_pre, coef=sv['coef_o']), sv['save_o'])
+    gbits = sv.get('gbits')
+    if dg_masked:                                      # form (a): dg is dsum; g is not read, dsum is not written
+        dsum, doz, part_o = ops.gcn_tail_bwd_bits(dg, None, S(o_pre, coef=sv['coef_o']), sv['save_o'])
+    elif gbits is not None:                            # form (b): 1/16 of a pass instead of g
+        dsum, doz, part_o = ops.gcn_tail_bwd_bits(dg, gbits, S(o_pre, coef=sv['coef_o']), sv['save_o'])
+    else:
+        dsum, doz, part_o = ops.gcn_tail_bwd(dg, g, S(o_pre, coef=sv['coef_o']), sv['save_o'])
     coefb_o = torch.empty(3, Cout, device=x.device)
     G['bno.w'], G['bno.b'], G['bo'] = P.bno.bwd(part_o, 0, count, sv['save_o'], 0, training, coefb_o, 0, want_dbias=True)
     gyo = S(doz, o_pre, coefb_o)
@@ -509,21 +518,22 @@ def tcn_forward(g, P, training, save, xres=None, pool=None):
         res = None
     fk.__exit__()                                      # join all branches
     bo.flush()
+    sign = [] if save and ops.SIGNBITS and P.relu else None     # the sign bits of out ride along for the backward
     if pool is not None:
-        out, rm = ops.add_act_fwd(S(cat_pre, coef=coef_c), res, P.relu, Cout, rowmean=True)
+        out, rm = ops.add_act_fwd(S(cat_pre, coef=coef_c), res, P.relu, Cout, rowmean=True, sign=sign)
         pool.append(rm)
     else:
         # the next block's frame means ride along in train mode / under autograd (the step this path is built for); a plain
         # eval forward keeps tamgcn_tmean, so that it stays bit-compatible with the launch-fused eval path (EVAL_FUSED)
         if training or save:
-            out, xb = ops.add_act_fwd(S(cat_pre, coef=coef_c), res, P.relu, Cout, xbar=True)
+            out, xb = ops.add_act_fwd(S(cat_pre, coef=coef_c), res, P.relu, Cout, xbar=True, sign=sign)
             attach_xbar(out, xb)
         else:
-            out = ops.add_act_fwd(S(cat_pre, coef=coef_c), res, P.relu, Cout)
+            out = ops.add_act_fwd(S(cat_pre, coef=coef_c), res, P.relu, Cout, sign=sign)
     sv = None
     if save:
         sv = dict(g=g, xres=xres, h_pre=h_pre, cat_pre=cat_pre, r_pre=r_pre, out=out, coef_h=coef_h, save_h=save_h,
-                  coef_c=coef_c, save_c=save_c, coef_r=coef_r, save_r=save_r, training=training)
+                  coef_c=coef_c, save_c=save_c, coef_r=coef_r, save_r=save_r, training=training, obits=sign[0] if sign else None)
     return out, sv
 
 
@@ -570,12 +580,24 @@ def _tcn_forward_eval(g, P, xres):
     return out
 
 
-def tcn_backward(P, sv, dout, need_dg=True, need_dxres=True):
+def signmask_route(stride, have_bits, N, Cb, Cin, T, V, split_mode=0):
+    """How the ReLU mask of g reaches dg inside TCN_GCN_unit's backward: 'a' the block's last data-gradient GEMM applies g's
+    sign bits in its epilogue (stride 1, a shape of tamgcn_conv_signmask) and unit_gcn's tail takes dsum as it comes; 'b'
+    the tail applies the bits itself (strided blocks: that GEMM writes every other frame; shapes the GEMM refuses); None
+    without bits (TAMGCN_SIGNBITS=0): the tail reads g."""
+    if not have_bits:
+        return None
+    return 'a' if stride == 1 and ops.signmask_shape_ok(N, Cb, Cin, T, V, split_mode) else 'b'
+
+
+def tcn_backward(P, sv, dout, need_dg=True, need_dxres=True, dg_sign=None, route=None):
+    """dg_sign: the sign bits of g (the block's input activation inside TCN_GCN_unit) -- where the last data-gradient GEMM can
+    mask by them it does, and route['dg_masked'] tells the caller that dg is dg * (g > 0) already."""
     with ops.ReduceBatch():                            # one launch for every slab reduction of this backward
-        return _tcn_backward(P, sv, dout, need_dg, need_dxres)
+        return _tcn_backward(P, sv, dout, need_dg, need_dxres, dg_sign, route)
 
 
-def _tcn_backward(P, sv, dout, need_dg=True, need_dxres=True):
+def _tcn_backward(P, sv, dout, need_dg=True, need_dxres=True, dg_sign=None, route=None):
     """Returns (dg, dxres, grads).  dxres is None for rmode 'zero'; for 'identity' it is the
     masked upstream gradient itself (caller adds it)."""
     g, xres, h_pre, cat_pre, r_pre, out = sv['g'], sv['xres'], sv['h_pre'], sv['cat_pre'], sv['r_pre'], sv['out']
@@ -588,7 +610,10 @@ def _tcn_backward(P, sv, dout, need_dg=True, need_dxres=True):
     G = {}
     fk = Fork(g.device, 2)
     fk.__enter__()
-    dz, part = ops.add_act_bwd(dout, out, P.relu, cat_pre, sv['save_c'], r_pre, sv['save_r'], want_dz=bool(P.relu))
+    if sv.get('obits') is not None:                    # the sign bits of out instead of out (P.relu is set)
+        dz, part = ops.add_act_bwd_bits(dout, sv['obits'], cat_pre, sv['save_c'], r_pre, sv['save_r'], want_dz=True)
+    else:
+        dz, part = ops.add_act_bwd(dout, out, P.relu, cat_pre, sv['save_c'], r_pre, sv['save_r'], want_dz=bool(P.relu))
     if dz is None:
         dz = dout
     coefb_c = torch.empty(3, Cout, device=g.device)
@@ -682,7 +707,13 @@ def _tcn_backward(P, sv, dout, need_dg=True, need_dxres=True):
     dg = None
     if need_dg:
         dg, _ = ops.conv(gyh, K=Ch, w=P.Win, bias=None, M=Cin, wmode=1)
-        ops.conv(gcat((nb + 1) * Cb), K=Cb, w=P.Wl, bias=None, M=Cin, wmode=1, y=dg, T_out=T2, ostride=s, add1=dg)
+        # the mask of unit_gcn's ReLU is a select after the sum: applied here, dg leaves as the dsum gcn_tail_bwd would compute
+        masked = signmask_route(s, dg_sign is not None, N, Cb, Cin, T, V, ops._lib_().tamgcn_get_split_mode()) == 'a' and \
+            ops.signmask_supported((dz, cat_pre, P.Wl, dg, dg_sign), N, Cb, Cin, T, V)
+        ops.conv(gcat((nb + 1) * Cb), K=Cb, w=P.Wl, bias=None, M=Cin, wmode=1, y=dg, T_out=T2, ostride=s, add1=dg,
+                 sign=dg_sign if masked else None)
+        if route is not None:
+            route['dg_masked'] = masked
     dxres = None
     if P.rmode == 'identity':
         dxres = dz
@@ -788,9 +819,11 @@ class TCNGCNUnitFn(_Fn):
     @staticmethod
     def backward(ctx, dout, _drm=None):
         need_dx = ctx.needs_input_grad[1]
-        dg, dxres, Gt = tcn_backward(ctx.Pt, ctx.svt, dout.contiguous(), need_dg=True, need_dxres=need_dx)
+        route = {}
+        dg, dxres, Gt = tcn_backward(ctx.Pt, ctx.svt, dout.contiguous(), need_dg=True, need_dxres=need_dx,
+                                     dg_sign=ctx.svg.get('gbits'), route=route)
         ctx.svt = None
-        dx, Gg = gcn_backward(ctx.Pg, ctx.svg, dg, need_dx=need_dx, extra_dx=dxres)
+        dx, Gg = gcn_backward(ctx.Pg, ctx.svg, dg, need_dx=need_dx, extra_dx=dxres, dg_masked=route.get('dg_masked', False))
         ctx.svg = None
         return (None, dx, None, None) + tuple(ctx.mod.gcn1._route(Gg)) + tuple(ctx.mod._route_tcn(Gt))
 

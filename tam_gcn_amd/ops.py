@@ -22,7 +22,7 @@ def _ptr(t):
         return None
     if not (t.is_cuda and t.is_contiguous()):
         raise RuntimeError('tam_gcn_amd: expected a contiguous HIP (cuda) tensor; there is no CPU path')
-    if t.dtype not in (torch.float32, torch.int64, torch.int32, torch.float64):
+    if t.dtype not in (torch.float32, torch.int64, torch.int32, torch.float64, torch.uint8):
         raise RuntimeError(f'tam_gcn_amd: unsupported dtype {t.dtype}')
     return t.data_ptr()
 
@@ -100,9 +100,11 @@ def with_slack(t):
 def conv(src, K, w, bias, M, KT=1, dil=1, stride=1, pad=0, wmode=0, up=1,
          y=None, ycoff=0, T_out=None, T_y=None, ostride=1, add1=None, add2=None,
          bcast=None, bcast_scale=0.0, mask=None, aux=None, aux_center=None, auxcoff=0, stats=False,
-         post_coef=None, post_act=0):
+         post_coef=None, post_act=0, sign=None, sign_coff=0):
     """y (N, yctot, T_y, V); returns (y, stats_part [2][yctot][nparts] or None).
-    post_coef [3][yctot] / post_act: eval-mode fusion, y = act(c1*(conv + bias) + c0 + adds)."""
+    post_coef [3][yctot] / post_act: eval-mode fusion, y = act(c1*(conv + bias) + c0 + adds).
+    sign (N, C, ceil(T_y*V / 4)) uint8: sign bits in place of `mask` (tamgcn_conv_signmask; row m uses channel sign_coff + m).
+    The library refuses the shapes signmask_supported() does not admit."""
     if src.x1.shape[-1] % 4:
         src = S(with_slack(src.x1), with_slack(src.x2), src.coef, src.coff, src.act)
     x = src.x1
@@ -117,7 +119,7 @@ def conv(src, K, w, bias, M, KT=1, dil=1, stride=1, pad=0, wmode=0, up=1,
         T_y = y.shape[2]
     per_clip = max(x.shape[1] * T_in * V, y.shape[1] * T_y * V)
     if N > 1 and N * per_clip > CHUNK_ELEMS:
-        if stats or mask is not None or aux is not None:
+        if stats or mask is not None or aux is not None or sign is not None:
             raise RuntimeError('tam_gcn_amd: a convolution over >= 2^31 elements cannot carry BatchNorm moments / a mask')
         for n0, n1 in n_chunks(N, per_clip):
             conv(_slice_src(src, n0, n1), K, w, bias, M, KT, dil, stride, pad, wmode, up, y=y[n0:n1], ycoff=ycoff, T_out=T_out,
@@ -151,8 +153,40 @@ def conv(src, K, w, bias, M, KT=1, dil=1, stride=1, pad=0, wmode=0, up=1,
             raise RuntimeError('tamgcn_conv: no tiling for this shape')
         part = empty(2, y.shape[1], nparts, like=x)
         d.stats_part, d.stats_ctot, d.stats_coff = _ptr(part), y.shape[1], ycoff
-    _lib.check(lib.tamgcn_conv(C.byref(d), _stream()), 'tamgcn_conv')
+    if sign is not None:
+        _lib.check(lib.tamgcn_conv_signmask(C.byref(d), _ptr(sign), sign.shape[1], sign_coff, _stream()), 'tamgcn_conv_signmask')
+    else:
+        _lib.check(lib.tamgcn_conv(C.byref(d), _stream()), 'tamgcn_conv')
     return y, part
+
+
+# ---------------------------------------------------------------------------
+# ReLU sign bits (include/tamgcn.h: tamgcn_conv_signmask): the forward passes that save for a backward leave one bit per element
+# of g and of the block output, and the backward reads those instead of the activations
+SIGNBITS = os.environ.get('TAMGCN_SIGNBITS', '1') != '0'   # 0: the backward reads the activations' signs, as before (A/B, tests)
+
+
+def sign_empty(N, C_, T, V, like):
+    """The sign-bit array of an (N, C_, T, V) tensor: a byte per four consecutive floats of a row."""
+    return torch.empty(N, C_, (T * V + 3) // 4, device=like.device, dtype=torch.uint8)
+
+
+def signmask_shape_ok(N, K, M, T, V, split_mode=0):
+    """Whether tamgcn_conv_signmask serves a stride-1 two-source 1x1 data gradient of K channels into M at (N, *, T, V): the
+    CONSERVATIVE side of the library's rule (conv.hip: the LDS-DMA GEMM's shapes as in pair_supported, its eight-wave form,
+    and not the bf16 split kernel that takes M >= 128 in split mode 1)."""
+    if V % 4 or V > 32 or T * V < 64 or K % 16 or M % 16 or K > 512 or M > 512 or N * max(K, M) * T * V > CHUNK_ELEMS:
+        return False
+    if os.environ.get('TAMGCN_CONV_WAVES', '8') == '4':
+        return False
+    return split_mode == 0 or M < 128
+
+
+def signmask_supported(tensors, N, K, M, T, V):
+    """signmask_shape_ok() at the library's current split mode, and every operand contiguous and 16-byte aligned."""
+    if not signmask_shape_ok(N, K, M, T, V, _lib_().tamgcn_get_split_mode()):
+        return False
+    return all(t is None or (t.is_cuda and t.is_contiguous() and t.data_ptr() % 16 == 0) for t in tensors)
 
 
 # ---------------------------------------------------------------------------
@@ -749,12 +783,19 @@ def ctrgc_bwd(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, x3=None, E=N
 
 
 # ---------------------------------------------------------------------------
-def gcn_tail_fwd(y, o, res):
+def gcn_tail_fwd(y, o, res, sign=None):
+    """sign: None | list -- the sign bits of g are written too and appended to it."""
     N, _, T, V = y.x1.shape
     Cc = y.ctot
     g = empty(N, Cc, T, V, like=y.x1)
     yc, oc = y.c(), o.c()
     rc = res.c() if res is not None else None
+    if sign is not None:
+        bits = sign_empty(N, Cc, T, V, g)
+        _lib.check(_lib_().tamgcn_gcn_tail_fwd_bits(C.byref(yc), C.byref(oc), C.byref(rc) if rc is not None else None,
+                                                    N, Cc, T, V, _ptr(g), _ptr(bits), _stream()), 'tamgcn_gcn_tail_fwd_bits')
+        sign.append(bits)
+        return g
     _lib.check(_lib_().tamgcn_gcn_tail_fwd(C.byref(yc), C.byref(oc), C.byref(rc) if rc is not None else None,
                                            N, Cc, T, V, _ptr(g), _stream()), 'tamgcn_gcn_tail_fwd')
     return g
@@ -768,6 +809,19 @@ def gcn_tail_bwd(dg, g, o, o_save):
     _lib.check(_lib_().tamgcn_gcn_tail_bwd(_ptr(dg), _ptr(g), C.byref(oc), _ptr(o_save), N, Cc, T, V, _ptr(dsum), _ptr(doz),
                                            _ptr(part), _stream()), 'tamgcn_gcn_tail_bwd')
     return dsum, doz, part
+
+
+def gcn_tail_bwd_bits(dg, bits, o, o_save):
+    """gcn_tail_bwd with the sign bits of g in place of g.  bits None: dg is dsum already (masked by its producer) and is
+    returned as such -- g is not read and dsum is not written."""
+    N, Cc, T, V = dg.shape
+    dsum = empty_like(dg) if bits is not None else None
+    doz = empty_like(dg)
+    part = empty(2, Cc, N, like=dg)
+    oc = o.c()
+    _lib.check(_lib_().tamgcn_gcn_tail_bwd_bits(_ptr(dg), _ptr(bits), C.byref(oc), _ptr(o_save), N, Cc, T, V, _ptr(dsum), _ptr(doz),
+                                                _ptr(part), _stream()), 'tamgcn_gcn_tail_bwd_bits')
+    return (dsum if bits is not None else dg), doz, part
 
 
 def gcn_mid_bwd(dsum, ddiff, y_pre, y_save, r_pre, r_save, want_dres):
@@ -811,8 +865,9 @@ def maxpool_bwd(gy, src, src_save, C_, stride, d, dcoff):
 XBAR_FOLD = os.environ.get('TAMGCN_XBAR_FOLD', '1') != '0'    # 0: every block computes its own frame means (tamgcn_tmean)
 
 
-def add_act_fwd(a, res, relu, C_, rowmean=False, xbar=False):
-    """rowmean: also return the (N, C) means over (t, v) of the output (the model head's pooling input).
+def add_act_fwd(a, res, relu, C_, rowmean=False, xbar=False, sign=None):
+    """sign: None | list -- with relu, the sign bits of the output are written too and appended to it.
+    rowmean: also return the (N, C) means over (t, v) of the output (the model head's pooling input).
     xbar: also return the (C, N, V) means over t of the output (the next block's pooled joint-embedding input) -- or None
     where the fused form does not apply (V % 4 != 0, V > 64)."""
     N, _, T, V = a.x1.shape
@@ -823,8 +878,14 @@ def add_act_fwd(a, res, relu, C_, rowmean=False, xbar=False):
         xb = empty(C_, N, V, like=a.x1)
     ac = a.c()
     rc = res.c() if res is not None else None
-    _lib.check(_lib_().tamgcn_add_act_fwd(C.byref(ac), C.byref(rc) if rc is not None else None, int(relu),
-                                          N, C_, T, V, _ptr(out), _ptr(rm), _ptr(xb), _stream()), 'tamgcn_add_act_fwd')
+    if sign is not None and relu:
+        bits = sign_empty(N, C_, T, V, out)
+        _lib.check(_lib_().tamgcn_add_act_fwd_bits(C.byref(ac), C.byref(rc) if rc is not None else None,
+                                                   N, C_, T, V, _ptr(out), _ptr(rm), _ptr(xb), _ptr(bits), _stream()), 'tamgcn_add_act_fwd_bits')
+        sign.append(bits)
+    else:
+        _lib.check(_lib_().tamgcn_add_act_fwd(C.byref(ac), C.byref(rc) if rc is not None else None, int(relu),
+                                              N, C_, T, V, _ptr(out), _ptr(rm), _ptr(xb), _stream()), 'tamgcn_add_act_fwd')
     if xbar:
         return out, xb
     return (out, rm) if rowmean else out
@@ -836,6 +897,16 @@ def add_act_bwd(dout, out, relu, a_pre, a_save, r_pre, r_save, want_dz):
     part = empty(4 if r_pre is not None else 2, Cc, N, like=dout)
     _lib.check(_lib_().tamgcn_add_act_bwd(_ptr(dout), _ptr(out), int(relu), _ptr(a_pre), _ptr(a_save), _ptr(r_pre), _ptr(r_save), N, Cc, T, V,
                                           _ptr(dz), _ptr(part), _stream()), 'tamgcn_add_act_bwd')
+    return dz, part
+
+
+def add_act_bwd_bits(dout, bits, a_pre, a_save, r_pre, r_save, want_dz):
+    """add_act_bwd (relu = 1) with the sign bits of `out` in place of `out`."""
+    N, Cc, T, V = dout.shape
+    dz = empty_like(dout) if want_dz else None
+    part = empty(4 if r_pre is not None else 2, Cc, N, like=dout)
+    _lib.check(_lib_().tamgcn_add_act_bwd_bits(_ptr(dout), _ptr(bits), _ptr(a_pre), _ptr(a_save), _ptr(r_pre), _ptr(r_save), N, Cc, T, V,
+                                               _ptr(dz), _ptr(part), _stream()), 'tamgcn_add_act_bwd_bits')
     return dz, part
 
 

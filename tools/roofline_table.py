@@ -21,13 +21,18 @@ HBM, MF = 6.0e12, bench.F32_MFMA_PEAK        # 6 TB/s: what a streaming kernel r
 
 
 def sig(name, args):
+    if name in ('tamgcn_add_act_fwd', 'tamgcn_add_act_bwd', 'tamgcn_gcn_tail_fwd', 'tamgcn_gcn_tail_bwd', 'tamgcn_gcn_mid_bwd',
+                'tamgcn_add_act_fwd_bits', 'tamgcn_add_act_bwd_bits', 'tamgcn_gcn_tail_fwd_bits', 'tamgcn_gcn_tail_bwd_bits'):
+        ints = [x for x in args if isinstance(x, int) and x < (1 << 31)]       # N, C, T, V (device pointers are ints too)
+        form = ' dsum in' if name == 'tamgcn_gcn_tail_bwd_bits' and args[1] is None else ''
+        return f'{name[7:]} ' + 'x'.join(str(v) for v in ints[-4:]) + form
     try:
         d = args[0]._obj
     except AttributeError:
         return name
-    if name == 'tamgcn_conv':
+    if name in ('tamgcn_conv', 'tamgcn_conv_signmask'):        # signmask: the mask is 1/16 of a pass (not counted in ex)
         ex = (1 if d.add1 else 0) + (1 if d.add2 else 0) + (1 if d.mask else 0) + (1 if d.aux else 0)
-        return f'conv K{d.K} M{d.M} KT{d.KT} T{d.T_in}>{d.T_out} src{bench._src_reads(d.src)} ex{ex} wm{d.wmode} st{1 if d.stats_part else 0} s{d.stride} N{d.N}' + (f' [al{(d.src.x1 or 0) % 16}/{(d.src.x2 or 0) % 16}/{(d.w or 0) % 16} coff{d.src.coff}/{d.src.ctot} ycoff{d.ycoff}/{d.yctot} os{d.ostride} up{d.up} bc{1 if d.bcast else 0}]' if os.environ.get('RT_DETAIL') else '')
+        return ('conv' if name == 'tamgcn_conv' else 'conv_signmask') + f' K{d.K} M{d.M} KT{d.KT} T{d.T_in}>{d.T_out} src{bench._src_reads(d.src)} ex{ex} wm{d.wmode} st{1 if d.stats_part else 0} s{d.stride} N{d.N}' + (f' [al{(d.src.x1 or 0) % 16}/{(d.src.x2 or 0) % 16}/{(d.w or 0) % 16} coff{d.src.coff}/{d.src.ctot} ycoff{d.ycoff}/{d.yctot} os{d.ostride} up{d.up} bc{1 if d.bcast else 0}]' if os.environ.get('RT_DETAIL') else '')
     if name == 'tamgcn_wgrad':
         return f'wgrad K{d.K} M{d.M} KT{d.KT} T{d.T_in}>{d.T_out} gy{bench._src_reads(d.gy)} src{bench._src_reads(d.src)} N{d.N}'
     if name == 'tamgcn_conv_pair':
@@ -38,9 +43,6 @@ def sig(name, args):
         return f'{name[7:]} Cb{d.Cb} nb{d.nb} KT{d.KT} T{d.T_in}>{d.T_out} s{d.stride}' + (' +pool' if name == 'tamgcn_tconv_fwd' and d.pool else '') + f' N{d.N}'
     if name.startswith('tamgcn_ctrgc'):
         return f'{name[7:]} {d.Cin}>{d.Cout} T{d.T}'
-    if name in ('tamgcn_add_act_fwd', 'tamgcn_add_act_bwd', 'tamgcn_gcn_tail_fwd', 'tamgcn_gcn_tail_bwd', 'tamgcn_gcn_mid_bwd'):
-        ints = [x for x in args if isinstance(x, int)]
-        return f'{name[7:]} ' + 'x'.join(str(v) for v in ints[-4:])
     return name
 
 
