@@ -653,6 +653,28 @@ int tamgcn_f2v_gcn(const tamgcn_f2_gcn_desc* d, void* stream);
 int tamgcn_f2v_gemm(const tamgcn_f2_gemm_desc* d, void* stream);
 int tamgcn_f2v_tcn(const tamgcn_f2_tcn_desc* d, void* stream);
 
+/* ---- f2g: the same four stages for EVERY joint count 8 <= d->V <= 28, multiples of four included, with V a kernel argument
+ * (tam_gcn_amd/csrc/f2g.hip, tam_gcn_amd/f2g.py).  The f2 descriptors, the algebra above and f2v's buffer layout, all
+ * unchanged: the block's input and output contiguous (N, C, T, V); E (N, S, Cout, V, VP), sum, diff, the gemm operands, h
+ * (N, C, T, VP) and xpart (N, tiles, C, VP) with frames of VP = (V + 3) & ~3 floats; columns V..VP-1 of E, sum, diff and xpart
+ * exactly zero whatever the inputs' pad columns hold; at V % 4 == 0, VP = V and nothing is padded.  Alignment and the 12
+ * readable bytes behind x: as f2v.  The kernels are instantiated per frame pitch VP (8, 12, 16, 20, 24, 28), not per joint
+ * count; 17, 18, 20 and 25 are accepted too (the run-time-V form of the f2 / f2v kernels at the same V).  Any other d->V is
+ * refused on the host before any launch, the message naming the entry point and "V=<value>".  No grouped entry points.
+ *   tamgcn_f2g_supported(V)  1 for 8 <= V <= 28, else 0
+ *   tamgcn_f2g_lds_bytes(stage, V, c, r)  the largest dynamic-LDS request, in bytes, that stage 0 (_e: c = Cin, r = R), 1 (_gcn:
+ *       c = Cin), 2 (_gemm: c = K) or 3 (_tcn: c = the residual conv's Cin, r = Cb; the maximum over res_mode) makes at joint
+ *       count V; -1 for a geometry the entry points refuse (V outside 8..28, c outside 1..256, R outside 1..32, Cb not 16, 32,
+ *       48 or 64).  Never above 160 KB: _gcn stages K in chunks chosen from V (112 rows at V = 28, 128 below), _e sums the
+ *       frames in two phases instead of four where four partial tiles do not fit.
+ * Deterministic: two runs are bit-equal.  Added in ABI 401 without a version bump: new entry points only. */
+int tamgcn_f2g_supported(int V);
+int tamgcn_f2g_lds_bytes(int stage, int V, int c, int r);
+int tamgcn_f2g_e(const tamgcn_f2_gcn_desc* d, void* stream);
+int tamgcn_f2g_gcn(const tamgcn_f2_gcn_desc* d, void* stream);
+int tamgcn_f2g_gemm(const tamgcn_f2_gemm_desc* d, void* stream);
+int tamgcn_f2g_tcn(const tamgcn_f2_tcn_desc* d, void* stream);
+
 /* ---- grouped: the four stages of both families for `groups` models of ONE geometry in one launch (a multi-stream ensemble:
  * tam_gcn_amd.inference.StreamEnsemble).  The descriptors above, unchanged, plus `int groups`:
  *   samples      d->N is the TOTAL number of clip-persons, N % groups == 0; samples [g N/groups, (g+1) N/groups) belong to group g

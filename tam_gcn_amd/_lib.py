@@ -234,6 +234,12 @@ SIGNATURES = {
     'tamgcn_f2v_gcn': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2v_gemm': (_i, [C.POINTER(F2GemmDesc), _p]),
     'tamgcn_f2v_tcn': (_i, [C.POINTER(F2TcnDesc), _p]),
+    'tamgcn_f2g_supported': (_i, [_i]),
+    'tamgcn_f2g_lds_bytes': (_i, [_i, _i, _i, _i]),
+    'tamgcn_f2g_e': (_i, [C.POINTER(F2GcnDesc), _p]),
+    'tamgcn_f2g_gcn': (_i, [C.POINTER(F2GcnDesc), _p]),
+    'tamgcn_f2g_gemm': (_i, [C.POINTER(F2GemmDesc), _p]),
+    'tamgcn_f2g_tcn': (_i, [C.POINTER(F2TcnDesc), _p]),
     'tamgcn_f2_e_grouped': (_i, [C.POINTER(F2GcnDesc), _i, _p]),
     'tamgcn_f2_gcn_grouped': (_i, [C.POINTER(F2GcnDesc), _i, _p]),
     'tamgcn_f2_gemm_grouped': (_i, [C.POINTER(F2GemmDesc), _i, _p]),

@@ -236,7 +236,7 @@ def _(x, xpart, params, geom):
 # Group g's slice of the result is bit-equal to tcn_gcn_unit_eval on group g's slice and parameters.
 # ----------------------------------------------------------------------------------------------------------------------
 def _unit(fam, x, xpart, params, geom, groups, joints=(25,), tag='_v25'):
-    """The five launches of one block: the body of all six registered block operators.  fam 'f2' (V = 20) | 'f2v' (V =
+    """The five launches of one block: the body of all registered block operators.  fam 'f2' (V = 20) | 'f2v' | 'f2g' (V =
     x.shape[3], one of `joints`: frames of VP = (V + 3) & ~3 floats in the family's own buffers, 12 bytes of slack behind the
     contiguous input and output; `tag` names the operator in messages); groups None: the plain entry points on one model's
     params, else the grouped ones on params stacked on a leading group axis."""

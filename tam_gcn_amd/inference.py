@@ -26,9 +26,9 @@ from . import ops
 
 __all__ = ['GraphedForward', 'StreamEnsemble']
 
-# where models.ctrgcn.Model keeps its small-batch engines: f2.FusedEval, f2v.FusedEvalV, f2v.FusedEvalJ (one slot per class),
-# and models.stgcn.Model its f2s.FusedEvalST
-ENGINE_SLOTS = ('_tamgcn_f2', '_tamgcn_f2v', '_tamgcn_f2j', '_tamgcn_f2s')
+# where models.ctrgcn.Model keeps its small-batch engines: f2.FusedEval, f2v.FusedEvalV, f2v.FusedEvalJ, f2g.FusedEvalG (one slot
+# per class), and models.stgcn.Model its f2s.FusedEvalST
+ENGINE_SLOTS = ('_tamgcn_f2', '_tamgcn_f2v', '_tamgcn_f2j', '_tamgcn_f2g', '_tamgcn_f2s')
 
 
 class GraphedForward:

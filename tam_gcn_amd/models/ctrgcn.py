@@ -521,6 +521,20 @@ class Model(nn.Module):
             return None
         return self._small_batch_engine(x, '_tamgcn_f2j', f2v.FusedEvalJ)
 
+    def _f2g(self, x):
+        """The same for every other joint count of f2g.JOINTS_RANGE (8..28 without the dedicated 17, 18, 20, 25), on the f2g
+        kernels that take V at run time: at most F2G_MAX_FRAMES clip-persons x frames.  Its own slot, _tamgcn_f2g."""
+        if self.training or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32:
+            return None
+        from .. import f2g
+        v = self.num_point
+        if not f2g.JOINTS_RANGE[0] <= v <= f2g.JOINTS_RANGE[1] or v in f2g.DEDICATED:
+            return None
+        frames = x.shape[0] * x.shape[4] * x.shape[2] if x.dim() == 5 else x.shape[0] * x.shape[1]
+        if not f2g.enabled() or frames > f2g.F2G_MAX_FRAMES:
+            return None
+        return self._small_batch_engine(x, '_tamgcn_f2g', f2g.FusedEvalG)
+
     def _small_batch_engine(self, x, slot, cls):
         from .. import f2
         # the engine calls the block operator directly: forward hooks on any sub-module would not fire.  A model that
@@ -542,7 +556,7 @@ class Model(nn.Module):
 
     def forward(self, x):
         x = _require_hip(x)
-        eng = self._f2(x) or self._f2v(x) or self._f2j(x)
+        eng = self._f2(x) or self._f2v(x) or self._f2j(x) or self._f2g(x)
         if eng is not None:
             return eng(x)
         if isinstance(self.drop_out, nn.Dropout):          # drop_out > 0: pool here, torch's dropout + linear (reference :343-348)
@@ -556,7 +570,7 @@ class Model(nn.Module):
 
     def extract_feature(self, x):
         x = _require_hip(x)
-        eng = self._f2(x) or self._f2v(x) or self._f2j(x)
+        eng = self._f2(x) or self._f2v(x) or self._f2j(x) or self._f2g(x)
         x, N, M = eng.blocks(x) if eng is not None else self._blocks(x)
         _, C, T, V = x.size()
         x = x.view(N, M, C, T, V).permute(0, 2, 3, 4, 1).contiguous()

@@ -1,6 +1,11 @@
 """GPU-box tool: forward-only throughput (eval mode, no_grad) of the N-UCLA or the NTU-RGB+D model at a few batch sizes -- what
 the inference-only callers (cross-modal attention, ensemble eval, visualisation) see.  Eager launches and HIP-graph replay.
-    python tools/infer_bench.py [--model ctrgcn|stgcn] [--graph ucla|ntu|coco|openpose] [--t T] [--ab R] [batch ...]     (default ctrgcn, ucla, T = 64, batches 1 16 256)
+    python tools/infer_bench.py [--model ctrgcn|stgcn] [--graph ucla|ntu|coco|openpose|synthetic] [--t T] [--ab R] [batch ...]     (default ctrgcn, ucla, T = 64, batches 1 16 256)
+--graph synthetic --joints V [--persons M]: graph.synthetic's binary tree of V joints (default 21), M persons (default 1) -- a
+skeleton of any joint count; CTR-GCN models of 8..28 joints without a dedicated family take the f2g kernels (tam_gcn_amd/f2g.py,
+TAMGCN_F2G_MAX_FRAMES).
+--f2g R: the run-time-V family (f2g.FusedEvalG, called directly) against whatever Model.forward routes to (f2 / f2v at 17, 18,
+20, 25 joints), alternating within this process, R timings each, eager and HIP-graph replay.
 --model stgcn: models.stgcn.Model on the same graphs; its small-batch family is tam_gcn_amd/f2s.py (TAMGCN_F2S_MAX_FRAMES).
 --graph ntu: 25 joints, 2 persons (a batch of B clips is 2B clip-persons); coco: 17 joints, 1 person; openpose: 18 joints, 2
 persons (the skeletons a pose estimator hands over: graph.coco, graph.openpose).
@@ -29,7 +34,7 @@ from tam_gcn_amd.models.ctrgcn import Model
 dev = torch.device('cuda:0')
 torch.manual_seed(0)
 args = sys.argv[1:]
-T, graph, ab, ens_g, model, sal = 64, 'ucla', 0, 0, 'ctrgcn', False
+T, graph, ab, ens_g, model, sal, joints, persons, vs_g = 64, 'ucla', 0, 0, 'ctrgcn', False, 21, 1, 0
 while args and args[0].startswith('--'):
     if args[0] == '--saliency':
         sal, args = True, args[1:]
@@ -44,6 +49,12 @@ while args and args[0].startswith('--'):
         model = args[1]
     elif args[0] == '--ensemble':
         ens_g = int(args[1])
+    elif args[0] == '--joints':
+        joints = int(args[1])
+    elif args[0] == '--persons':
+        persons = int(args[1])
+    elif args[0] == '--f2g':
+        vs_g = int(args[1])
     else:
         sys.exit(__doc__)
     args = args[2:]
@@ -60,6 +71,9 @@ elif graph == 'coco':
 elif graph == 'openpose':
     V, P = 18, 2
     m = Model(num_class=12, num_point=18, num_person=2, graph='tam_gcn_amd.graph.openpose.Graph', graph_args=dict(labeling_mode='spatial'))
+elif graph == 'synthetic':
+    V, P = joints, persons
+    m = Model(num_class=10, num_point=V, num_person=P, graph='tam_gcn_amd.graph.synthetic.Graph', graph_args=dict(num_node=V, arity=2))
 elif graph != 'ucla':
     sys.exit(__doc__)
 else:
@@ -82,14 +96,15 @@ def timed(fn):
     return (time.perf_counter() - t0) / n
 
 
-def capture(x):
+def capture(x, fn=None):
+    fn = fn or m
     s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
-        y = m(x)
+        y = fn(x)
     torch.cuda.current_stream().wait_stream(s); torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
-        y = m(x)
+        y = fn(x)
     g.replay(); torch.cuda.synchronize()
     return g, y
 
@@ -212,6 +227,40 @@ def saliency_bench(batches, R):
               + ('WINS by more than the spread' if gain > spread else 'does NOT win by more than the spread'), flush=True)
 
 
+def f2g_bench(batches, R):
+    from tam_gcn_amd import f2, f2v, f2g
+    f2.F2_MAX_CLIPS = f2v.F2V_MAX_FRAMES = f2v.F2J_MAX_FRAMES = f2g.F2G_MAX_FRAMES = 1 << 40
+    eng = f2g.FusedEvalG(m)
+    print(f'f2g (V at run time) against the routed family, graph = {graph} (V = {V}, M = {P}), T = {T}; {R} alternating timings of {n} calls: '
+          'median [min .. max]', flush=True)
+    for B in batches:
+        x = torch.rand(B, 3, T, V, P, device=dev) * 2 - 1
+        with torch.no_grad():
+            routed = next((type(e).FAMILY for e in (m._f2(x), m._f2v(x), m._f2j(x), m._f2g(x)) if e is not None), 'general')
+            runs = {}
+            for name, fn in ((routed, m), ('f2g', eng)):
+                for _ in range(3):
+                    fn(x)
+                g, y = capture(x, fn)
+                runs[name] = (fn, g, y, {'eager': [], 'graph': []})
+            for _ in range(R):
+                for name, (fn, g, y, r) in runs.items():
+                    r['eager'].append(timed(lambda: fn(x)))
+                    r['graph'].append(timed(g.replay))
+        ys = [v[2] for v in runs.values()]
+        for name, (fn, g, y, r) in runs.items():
+            print(f'batch {B:4d} x {P} x {T} ({B * P * T:6d} frames) {name:7s}: ' + '   '.join(
+                f'{k} {statistics.median(v) * 1e3:7.3f} ms [{min(v) * 1e3:7.3f} .. {max(v) * 1e3:7.3f}]' for k, v in r.items()), flush=True)
+        a, b = runs[routed][3]['graph'], runs['f2g'][3]['graph']
+        print(f'      f2g vs {routed} logits: {float((ys[1] - ys[0]).abs().max()) / float(ys[0].abs().max()):.1e} relative;  '
+              f'replay: f2g takes {statistics.median(b) / statistics.median(a):5.3f}x of the {routed} time', flush=True)
+
+
+if vs_g:
+    if model != 'ctrgcn':
+        sys.exit('--f2g: the family serves --model ctrgcn')
+    f2g_bench([int(v) for v in args] or (1, 16), vs_g)
+    sys.exit(0)
 if sal:
     if model != 'stgcn':
         sys.exit('--saliency: the family serves --model stgcn')
@@ -234,6 +283,9 @@ for B in ([int(v) for v in args] or (1, 16, 256)):
             elif graph in ('coco', 'openpose'):
                 from tam_gcn_amd import f2v
                 f2v.F2J_MAX_FRAMES = 1 << 40
+            elif graph == 'synthetic':
+                from tam_gcn_amd import f2, f2v, f2g
+                f2.F2_MAX_CLIPS = f2v.F2V_MAX_FRAMES = f2v.F2J_MAX_FRAMES = f2g.F2G_MAX_FRAMES = 1 << 40
             else:
                 from tam_gcn_amd import f2
                 f2.F2_MAX_CLIPS = 1 << 40
