@@ -777,6 +777,34 @@ int tamgcn_saliency_joints(const float* dx0, const float* coef, int N, int C, in
 int tamgcn_saliency_accumulate(const float* sal, const long long* labels, int N, int V, const int* part_off, const int* part_joints,
                                int P, int num_class, int per_class, int* count, double* sum, void* stream);
 
+/* ---- guidance (tam_gcn_amd/csrc/guidance.hip; tam_gcn_amd/guidance.py): the arithmetic between extract_feature and the plot of
+ * the reference's visual.py:53-87, and the pooled feature of models/resnet_gcn_attention.py:82-85, read from the block stack's
+ * output h (N*M, C, T', V) (row n*M + m = person m of clip n) without the permuted 5-D copy.  No host synchronisation, no atomics:
+ * two calls give the same bits.  2 <= V <= 32.
+ *   _guidance_parts    the workgroups of _guidance_reduce, N*M*ceil(T'V / 64) (-1: bad dims): its scratch sizes.
+ *   _guidance_reduce   intensity (N, T', V, M) = sqrt(sum_c h^2);  pooled (N, C) = mean over (T', V, M) of h;  csum: parts*C floats of
+ *                      scratch (per-workgroup channel sums, added per clip in (m, chunk) order by a second launch);  minmax
+ *                      [parts][2]: each workgroup's smallest and largest intensity.  One read of h.
+ *   _guidance_weights  weights (N, J).  min / max over ALL nparts partials (the whole call, visual.py:58-59);  f = 255 (I - min) /
+ *                      (max - min) in fp32, or I itself when max == min;  person 1 if M > 1 and the mean of f over (T', V) of person
+ *                      0 is strictly less than person 1's, else person 0 (only these two are compared);  per target joint v =
+ *                      joints[j] (int32 on the device): the mean of the min(k, T') largest of f[n, :, v, person], divided by 127;
+ *                      0 for v outside [0, V).  T' <= 1024.  One workgroup per clip.
+ *   _guidance_apply    the (225, 45 frames) map of the reference has weights[n][j] in rows 45j .. 45(j+1) when j < J and j < frames,
+ *                      0 elsewhere, every column equal; resized to (H, W) bilinearly with align_corners = False that is one factor per
+ *                      row: src = max((y + 0.5) 225 / H - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, 224), l = src - i0, factor =
+ *                      (1 - l) row[i0] + l row[i1].  out (N, Crgb, H, W) = rgb * factor (rgb, out: both or neither);  map: NULL |
+ *                      (N, 1, H, W) = factor.  Pointers need 4-byte alignment only; 16-byte accesses are used where rgb and out
+ *                      agree modulo 16.
+ * Added in ABI 401 without a version bump: new entry points. */
+int tamgcn_guidance_parts(int N, int M, int Tp, int V);
+int tamgcn_guidance_reduce(const float* h, int N, int M, int C, int Tp, int V, float* intensity, float* pooled, float* csum, float* minmax,
+                           void* stream);
+int tamgcn_guidance_weights(const float* intensity, const float* minmax, int nparts, int N, int Tp, int V, int M, const int* joints, int J,
+                            int k, float* weights, void* stream);
+int tamgcn_guidance_apply(const float* weights, int N, int J, int frames, const float* rgb, int Crgb, int H, int W, float* out, float* map,
+                          void* stream);
+
 /* Stem and head of such an ensemble, one launch each:
  *   _stem_streams_eval  x (N, C, T, V, M) joint clips -> out (G*N*M, C, T, V), row g*N*M + n*M + m = model g's eval-mode data_bn
  *                       (coef [G][3][J], J = C*V*M, each in _stem_apply's layout: c1 at [0][j], c0 at [2][j]) of stream modes[g]

@@ -255,6 +255,10 @@ SIGNATURES = {
     'tamgcn_f2s_gcn_bwd': (_i, [C.POINTER(F2sGcnBwdDesc), _p]),
     'tamgcn_saliency_joints': (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     'tamgcn_saliency_accumulate': (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p]),
+    'tamgcn_guidance_parts': (_i, [_i, _i, _i, _i]),
+    'tamgcn_guidance_reduce': (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    'tamgcn_guidance_weights': (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p]),
+    'tamgcn_guidance_apply': (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
     'tamgcn_stem_streams_eval': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     'tamgcn_head_fc_grouped': (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     'tamgcn_optim_step': (_i, [C.POINTER(OptimDesc), _p]),

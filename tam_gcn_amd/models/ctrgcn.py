@@ -568,10 +568,15 @@ class Model(nn.Module):
             return torch.ops.tamgcn.head_pooled(x, rm, self.fc.weight, self.fc.bias, M)
         return torch.ops.tamgcn.head(x, self.fc.weight, self.fc.bias, M)
 
+    def _block_stack(self, x):
+        """x -> (h (N*M, C, T', V), N, M): l10's output, row n*M + m = person m of clip n, from the small-batch family that
+        serves this call or else the general path.  extract_feature and tam_gcn_amd.guidance read it."""
+        eng = self._f2(x) or self._f2v(x) or self._f2j(x) or self._f2g(x)
+        return eng.blocks(x) if eng is not None else self._blocks(x)
+
     def extract_feature(self, x):
         x = _require_hip(x)
-        eng = self._f2(x) or self._f2v(x) or self._f2j(x) or self._f2g(x)
-        x, N, M = eng.blocks(x) if eng is not None else self._blocks(x)
+        x, N, M = self._block_stack(x)
         _, C, T, V = x.size()
         x = x.view(N, M, C, T, V).permute(0, 2, 3, 4, 1).contiguous()
         return x, x

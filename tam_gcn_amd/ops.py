@@ -1199,3 +1199,61 @@ def optim_step_guarded(p, g, s0, s1, lr, step, scal, mode, partial, stat, skippe
         raise RuntimeError('tam_gcn_amd.optim_step_guarded: skipped must be int32 with 1 element')
     gd = _lib.GradGuard(float(max_norm), int(bool(skip_nonfinite)), _ptr(partial), partial.numel(), _ptr(stat), _ptr(skipped))
     _lib.check(_lib_().tamgcn_optim_step_guarded(C.byref(d), C.byref(gd), _stream()), 'tamgcn_optim_step_guarded')
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# skeleton guidance (csrc/guidance.hip; tam_gcn_amd/guidance.py)
+# ---------------------------------------------------------------------------------------------------------------
+def guidance_reduce(h, M):
+    """h (N*M, C, T', V) fp32, the block stack's output -> intensity (N, T', V, M), pooled (N, C), minmax (parts, 2): one read of h."""
+    _want(h, 'h', torch.float32)
+    if h.dim() != 4 or M < 1 or h.shape[0] % M:
+        raise RuntimeError(f'tam_gcn_amd.guidance_reduce: h {tuple(h.shape)} is not (N*M, C, T, V) with M = {M}')
+    NM, C_, Tp, V = h.shape
+    N = NM // M
+    parts = _lib_().tamgcn_guidance_parts(N, M, Tp, V)
+    if parts < 1:
+        raise RuntimeError(f'tam_gcn_amd.guidance_reduce: bad dims N={N} M={M} T={Tp} V={V}')
+    intensity = torch.empty(N, Tp, V, M, device=h.device, dtype=torch.float32)
+    pooled = torch.empty(N, C_, device=h.device, dtype=torch.float32)
+    csum = torch.empty(parts, C_, device=h.device, dtype=torch.float32)
+    minmax = torch.empty(parts, 2, device=h.device, dtype=torch.float32)
+    _lib.check(_lib_().tamgcn_guidance_reduce(_ptr(h), N, M, C_, Tp, V, _ptr(intensity), _ptr(pooled), _ptr(csum), _ptr(minmax), _stream()),
+               'tamgcn_guidance_reduce')
+    return intensity, pooled, minmax
+
+
+def guidance_weights(intensity, minmax, joints, k):
+    """intensity (N, T', V, M), minmax (parts, 2) of the same call, joints int32 [J] on the device -> weights (N, J)."""
+    _want(intensity, 'intensity', torch.float32)
+    _want(minmax, 'minmax', torch.float32)
+    _want(joints, 'joints', torch.int32)
+    if intensity.dim() != 4 or minmax.dim() != 2 or minmax.shape[1] != 2 or joints.dim() != 1:
+        raise RuntimeError('tam_gcn_amd.guidance_weights: intensity (N, T, V, M), minmax (parts, 2), joints (J,)')
+    N, Tp, V, M = intensity.shape
+    J = joints.numel()
+    w = torch.empty(N, J, device=intensity.device, dtype=torch.float32)
+    _lib.check(_lib_().tamgcn_guidance_weights(_ptr(intensity), _ptr(minmax), minmax.shape[0], N, Tp, V, M, _ptr(joints), J, int(k), _ptr(w),
+                                               _stream()), 'tamgcn_guidance_weights')
+    return w
+
+
+def guidance_apply(weights, rgb, frames, H, W, want_map=False):
+    """weights (N, J); rgb None | (N, Crgb, H, W) fp32 -> (rgb * resized map | None, the (N, 1, H, W) map | None)."""
+    _want(weights, 'weights', torch.float32)
+    if weights.dim() != 2:
+        raise RuntimeError('tam_gcn_amd.guidance_apply: weights (N, J)')
+    N, J = weights.shape
+    out = wmap = None
+    Crgb = 0
+    if rgb is not None:
+        _want(rgb, 'rgb', torch.float32)
+        if rgb.dim() != 4 or rgb.shape[0] != N or tuple(rgb.shape[2:]) != (H, W):
+            raise RuntimeError(f'tam_gcn_amd.guidance_apply: rgb is {tuple(rgb.shape)}, expected ({N}, Crgb, {H}, {W})')
+        Crgb = rgb.shape[1]
+        out = torch.empty(N, Crgb, H, W, device=weights.device, dtype=torch.float32)
+    if want_map:
+        wmap = torch.empty(N, 1, H, W, device=weights.device, dtype=torch.float32)
+    _lib.check(_lib_().tamgcn_guidance_apply(_ptr(weights), N, J, int(frames), _ptr(rgb), Crgb, int(H), int(W), _ptr(out), _ptr(wmap), _stream()),
+               'tamgcn_guidance_apply')
+    return out, wmap

@@ -12,6 +12,8 @@ backward is itself a registered op:
     tamgcn::head_pooled(x, rowmean, W, b, M): the same with the row means of x already taken by the producer of x
     tamgcn::stream_derive(x, parent, mode) -> stream            feeder/feeder_nucla_gcn.py:119-127
     tamgcn::feeder_transform(raw, offsets, rot, idx, parent, V, time_steps, center_joint, mode) -> clips   :85-130
+    tamgcn::guidance_reduce(h, M) -> (intensity, pooled, minmax);  tamgcn::guidance_weights(intensity, minmax, joints, k) -> weights;
+    tamgcn::guidance_apply(weights, rgb | None, frames, H, W, want_map) -> (rgb * map, map)                 visual.py:53-87
 
     tamgcn::tcn_gcn_unit_eval(x, xpart, params, geom) -> (out, xpart)   the whole eval-mode TCN_GCN_unit (:266-284) for small
                                                  batches, BatchNorm folded; registered by tam_gcn_amd/f2.py with the engine that uses it
@@ -289,3 +291,44 @@ def feeder_transform(raw: Tensor, offsets: Tensor, rot: Tensor, idx: Tensor, par
 @feeder_transform.register_fake
 def _(raw, offsets, rot, idx, parent, V, time_steps, center_joint, mode):
     return raw.new_empty(offsets.shape[0] - 1, 3, time_steps, V, 1, dtype=torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# skeleton guidance (tam_gcn_amd/guidance.py; no autograd: the callers run under no_grad)
+# ---------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op('tamgcn::guidance_reduce', mutates_args=())
+def guidance_reduce(h: Tensor, M: int) -> tuple[Tensor, Tensor, Tensor]:
+    return ops.guidance_reduce(_c(h), M)
+
+
+@guidance_reduce.register_fake
+def _(h, M):
+    NM, C_, Tp, V = h.shape
+    N = NM // M
+    parts = NM * ((Tp * V + 63) // 64)
+    return (h.new_empty(N, Tp, V, M, dtype=torch.float32), h.new_empty(N, C_, dtype=torch.float32),
+            h.new_empty(parts, 2, dtype=torch.float32))
+
+
+@torch.library.custom_op('tamgcn::guidance_weights', mutates_args=())
+def guidance_weights(intensity: Tensor, minmax: Tensor, joints: Tensor, k: int) -> Tensor:
+    return ops.guidance_weights(_c(intensity), _c(minmax), _c(joints), k)
+
+
+@guidance_weights.register_fake
+def _(intensity, minmax, joints, k):
+    return intensity.new_empty(intensity.shape[0], joints.shape[0], dtype=torch.float32)
+
+
+@torch.library.custom_op('tamgcn::guidance_apply', mutates_args=())
+def guidance_apply(weights: Tensor, rgb: Tensor | None, frames: int, H: int, W: int, want_map: bool) -> tuple[Tensor, Tensor]:
+    """(rgb * map, map); a part that was not asked for (rgb None, want_map False) comes back with 0 elements"""
+    out, wmap = ops.guidance_apply(_c(weights), None if rgb is None else _c(rgb), frames, H, W, want_map)
+    return (weights.new_empty(0) if out is None else out), (weights.new_empty(0) if wmap is None else wmap)
+
+
+@guidance_apply.register_fake
+def _(weights, rgb, frames, H, W, want_map):
+    N = weights.shape[0]
+    out = weights.new_empty(0) if rgb is None else weights.new_empty(N, rgb.shape[1], H, W)
+    return out, (weights.new_empty(N, 1, H, W) if want_map else weights.new_empty(0))

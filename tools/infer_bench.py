@@ -26,7 +26,15 @@ this process, R timings each (default 5):
     A  general   eval-mode Model.forward in grad mode and torch.autograd.grad of the gathered score with respect to x (the only
                  way without the f2s backward kernels), then |.| summed per joint -- eager
     B  family    saliency.joint_saliency on the f2s forward + backward chain, forced on whatever the routing bound says -- eager and
-                 under HIP-graph replay"""
+                 under HIP-graph replay
+--guidance [--ab R]: skeleton guidance (tam_gcn_amd/guidance.py; the reference's visual.py:53-87) on N-UCLA clips (1 and 16 x 3 x 52 x
+20 x 1 with rgb (N, 15, 224, 224)) and one NTU clip (1 x 3 x 300 x 25 x 2), alternating in this process, R timings each (default 7):
+    A  host tail   the reference's shape of it: extract_feature, the torch ops, .cpu().numpy(), np.partition in two Python loops,
+                   F.interpolate and the multiply -- eager only (it synchronises, so it cannot be captured)
+    B  device      SkeletonGuidance.apply -- eager and under HIP-graph replay
+then the three launches on their own (back to back on one stream between two events: the larger of the cost of issuing the operator from
+Python and the kernel time; a kernel trace, a run of its own, gives the kernel time itself) and the apply kernel's bytes per second (rgb read + out written).  --guidance --kernels runs
+only those launches, 20 of each per shape, for a run under rocprofv3 --kernel-trace --stats."""
 import os, statistics, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -34,10 +42,13 @@ from tam_gcn_amd.models.ctrgcn import Model
 dev = torch.device('cuda:0')
 torch.manual_seed(0)
 args = sys.argv[1:]
-T, graph, ab, ens_g, model, sal, joints, persons, vs_g = 64, 'ucla', 0, 0, 'ctrgcn', False, 21, 1, 0
+T, graph, ab, ens_g, model, sal, joints, persons, vs_g, guid, only_kernels = 64, 'ucla', 0, 0, 'ctrgcn', False, 21, 1, 0, False, False
 while args and args[0].startswith('--'):
     if args[0] == '--saliency':
         sal, args = True, args[1:]
+        continue
+    if args[0] in ('--guidance', '--kernels'):                 # --kernels implies --guidance
+        guid, only_kernels, args = True, only_kernels or args[0] == '--kernels', args[1:]
         continue
     if args[0] == '--t':
         T = int(args[1])
@@ -256,6 +267,109 @@ def f2g_bench(batches, R):
               f'replay: f2g takes {statistics.median(b) / statistics.median(a):5.3f}x of the {routed} time', flush=True)
 
 
+def guidance_bench(R):
+    import numpy as np
+    import torch.nn.functional as F
+    from tam_gcn_amd import guidance
+    ucla = dict(num_class=10, num_point=20, num_person=1, graph='graph.ucla.Graph', graph_args=dict(labeling_mode='spatial'))
+    ntu = dict(num_class=60, num_point=25, num_person=2, graph='graph.ntu_rgb_d.Graph', graph_args=dict(labeling_mode='spatial'))
+    targets, k, frames = (3, 11, 7, 18, 14), 15, 5
+    print(f'guidance: {R} alternating timings of {n} calls each: median [min .. max]', flush=True)
+    for margs, shape in ((ucla, (1, 3, 52, 20, 1)), (ucla, (16, 3, 52, 20, 1)), (ntu, (1, 3, 300, 25, 2))):
+        mm = Model(**margs).to(dev)
+        with torch.no_grad():
+            for name, p in mm.named_parameters():
+                if name.endswith('alpha'):
+                    p.fill_(0.5)
+        x = torch.rand(*shape, device=dev) * 2 - 1
+        rgb = torch.rand(shape[0], 15, 224, 224, device=dev)
+        for b in mm.modules():                            # running statistics of this input: features of a sensible size
+            if isinstance(b, torch.nn.modules.batchnorm._BatchNorm):
+                b.momentum = 1.0
+        with torch.no_grad():
+            mm.train()(x)
+        mm.eval()
+        g = guidance.SkeletonGuidance(mm, targets, k, frames)
+
+        def host_tail():
+            with torch.no_grad():
+                _, feat = mm.extract_feature(x)
+            f = np.abs(((feat * feat).sum(dim=1) ** 0.5).cpu().numpy())
+            if f.max() - f.min() != 0:
+                f = 255 * (f - f.min()) / (f.max() - f.min())
+            N, _, V_, M_ = f.shape
+            canvas = np.zeros((N, 1, 225, 45 * frames))
+            for i in range(N):
+                who = 1 if M_ > 1 and f[i, :, :, 0].mean() < f[i, :, :, 1].mean() else 0
+                for j, v in enumerate(targets):
+                    if v < V_ and 45 * (j + 1) <= canvas.shape[3]:
+                        col = f[i, :, v, who]
+                        canvas[i, 0, 45 * j:45 * (j + 1), :] = -np.partition(-col, min(k, len(col) - 1))[:k].mean()
+            wm = F.interpolate(torch.from_numpy(canvas).float().to(dev) / 127.0, size=rgb.shape[-2:], mode='bilinear', align_corners=False)
+            return rgb * wm
+
+        def device():
+            return g.apply(x, rgb)
+        if only_kernels:
+            with torch.no_grad():
+                h, N, M_ = mm._block_stack(x)
+                for _ in range(20):
+                    inten, pooled, minmax = torch.ops.tamgcn.guidance_reduce(h, M_)
+                    w = torch.ops.tamgcn.guidance_weights(inten, minmax, g._joints_on(dev), k)
+                    torch.ops.tamgcn.guidance_apply(w, rgb, frames, 224, 224, False)
+            torch.cuda.synchronize()
+            print(f'{shape}: 20 calls of each launch', flush=True)
+            continue
+        for _ in range(3):
+            ya, yb = host_tail(), device()
+        gr, yg = capture(x, lambda _: device())
+        assert torch.equal(yg, yb)
+        d = float((ya - yb).abs().max()) / float(ya.abs().max())
+        times = {'A host tail, eager': [], 'B device, eager   ': [], 'B device, graph   ': []}
+        for _ in range(R):
+            times['A host tail, eager'].append(timed(host_tail))
+            times['B device, eager   '].append(timed(device))
+            times['B device, graph   '].append(timed(gr.replay))
+        tag = f'{margs["num_point"]} joints, x {shape}, rgb {tuple(rgb.shape)}'
+        for name, v in times.items():
+            print(f'{tag}  {name}: {statistics.median(v) * 1e3:7.3f} ms [{min(v) * 1e3:7.3f} .. {max(v) * 1e3:7.3f}]', flush=True)
+        a, b = times['A host tail, eager'], times['B device, eager   ']
+        spread = max(max(a) - min(a), max(b) - min(b))
+        gain = statistics.median(a) - statistics.median(b)
+        print(f'      device vs host tail: {d:.1e} relative;  eager device path {statistics.median(b) / statistics.median(a):5.2f}x of the host tail\'s time, '
+              f'{gain * 1e3:+.3f} ms; larger [min .. max] spread {spread * 1e3:.3f} ms: the device path '
+              + ('WINS by more than the spread' if gain > spread else 'does NOT win by more than the spread'), flush=True)
+        # the three launches on their own
+        with torch.no_grad():
+            h, N, M_ = mm._block_stack(x)
+            inten, pooled, minmax = torch.ops.tamgcn.guidance_reduce(h, M_)
+            jt = g._joints_on(dev)
+            w = torch.ops.tamgcn.guidance_weights(inten, minmax, jt, k)
+            H, W = rgb.shape[-2:]
+            reps = 200
+            for name, fn, nbytes in (('guidance_reduce (2 launches)', lambda: torch.ops.tamgcn.guidance_reduce(h, M_), h.numel() * 4),
+                                     ('guidance_weights', lambda: torch.ops.tamgcn.guidance_weights(inten, minmax, jt, k), inten.numel() * 4),
+                                     ('guidance_apply', lambda: torch.ops.tamgcn.guidance_apply(w, rgb, frames, H, W, False), 2 * rgb.numel() * 4)):
+                for _ in range(5):
+                    fn()
+                best = []
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    for _ in range(reps):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    best.append(e0.elapsed_time(e1) / reps * 1e-3)
+                t = statistics.median(best)
+                print(f'      {name:30s} {t * 1e6:8.2f} us per call back to back [{min(best) * 1e6:.2f} .. {max(best) * 1e6:.2f}]   '
+                      f'{nbytes / 1e6:8.3f} MB moved: {nbytes / t / 1e12:6.3f} TB/s', flush=True)
+
+
+if guid:
+    guidance_bench(ab or 7)
+    sys.exit(0)
 if vs_g:
     if model != 'ctrgcn':
         sys.exit('--f2g: the family serves --model ctrgcn')
