@@ -63,7 +63,12 @@ __device__ __forceinline__ void fuse_softmax_stats(const float* x, int K, int so
         inv = 1.f / den;
     }
 }
-// separate multiply and add (no fma contraction): numpy evaluates score_a + (alpha * score_b) with both roundings
+// separate multiply and add (no fma contraction): numpy evaluates score_a + (alpha * score_b) with both roundings.
+// __fmul_rn / __fadd_rn are plain * and + in the HIP headers and, once inlined, were contracted to one v_fmac_f32 (one rounding);
+// the pragma takes the contract flag off this function's operations, which the inliner keeps.
 __device__ __forceinline__ float fuse_add(float f, float ws, const float* x, int k, int softmax, float mx, float inv) {
-    return __fadd_rn(f, __fmul_rn(ws, softmax ? expf(x[k] - mx) * inv : x[k]));
+#pragma clang fp contract(off)
+    const float term = softmax ? expf(x[k] - mx) * inv : x[k];
+    const float prod = ws * term;
+    return f + prod;
 }
