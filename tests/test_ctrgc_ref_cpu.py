@@ -49,6 +49,15 @@ def test_every_dispatch_site_is_pinned_elsewhere_or_unreachable():
     both = sorted(k for k in list(L.UNREACHABLE) + list(L.ELSEWHERE) if k in L.PINNED)
     assert not both, f'listed as unreachable / elsewhere but pinned by a case: {both}'
     assert all(L.UNREACHABLE.values()) and all(L.ELSEWHERE.values())
+    # the fused forward: all six instantiations of ctrgc.hip, each through a case of the forward ledger that asserts the symbol
+    # the dispatch reports for it -- none is merely run elsewhere, none is unreachable
+    fwd = {k for k in found if k.startswith(('ctrgc_fwd_kernel<', 'ctrgc_fwd2_kernel<'))}
+    assert len(fwd) == 6 and fwd == set(L.FWD_PINNED), sorted(fwd ^ set(L.FWD_PINNED))
+    assert not [k for k in list(L.ELSEWHERE) + list(L.UNREACHABLE) if 'fwd' in k]
+    import ctrgc_fwd_ref as FR
+    for inst, sym in L.FWD_PINNED.items():
+        assert any(c['sym'] == sym and FR.INSTANTIATION[c['form']] == inst for c in FR.CASES.values()), inst
+    assert not any(k in L.FWD_PINNED for c in L.CASES.values() for k in (c['sym'],))
 
 
 def test_case_table_covers_what_it_promises():

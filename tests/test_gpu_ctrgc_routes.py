@@ -7,7 +7,8 @@ with NaN in the allocator's slack floats behind it.
 
 tests/test_ctrgc_ref_cpu.py (CPU) checks that the reference's formulas are autograd's, that an fp32 torch evaluation of every
 case below passes its bars, that subtly wrong results do not, and that every instantiation the three sources dispatch to is
-pinned here, run by another test (ELSEWHERE) or listed in UNREACHABLE with the reason no case launches it.
+pinned here or by the forward ledger (tests/test_gpu_ctrgc_fwd_forms.py), run by another test (ELSEWHERE) or listed in
+UNREACHABLE with the reason no case launches it; both of those lists are empty.
 
 Run with -s to see the measured err / bound ratios (profiles/ctrgc_route_bars.txt records one run)."""
 import ctypes as C
@@ -15,6 +16,7 @@ import ctypes as C
 import pytest
 import torch
 
+import ctrgc_fwd_ref as FR_
 import ctrgc_ref as R_
 import fp64_bars as B
 
@@ -74,24 +76,14 @@ for _V, _R, _S, _N, _C, _sym, _kw in [
         (64, 20, 3, 1, 16, 'ctrgc_de_tail_tiled_kernel<64, 2>', {}), (64, 32, 1, 1, 48, 'ctrgc_de_tail_tiled_kernel<64, 2>', {})]:
     _add('tail', _sym, V=_V, R=_R, S=_S, N=_N, C=_C, **_kw)
 
-# forward forms of ctrgc.hip that another test of the suite runs (the dispatch is read once per process from TAMGCN_CTRGC_FWD2).
-# Those tests hold the results to 2e-4 and do NOT assert the kernel symbol: the forms are run there, not symbol-checked.
-_FWD = 'tests/test_gpu_ctrgc_fwd_shapes.py::test_ctrgc_fwd_step_shapes'
-ELSEWHERE = {
-    f'ctrgc_fwd_kernel<{G20W}, 3>': _FWD + ' (l1: Cin = 3); run, not symbol-checked',
-    f'ctrgc_fwd_kernel<{G20W}, 3, false>': _FWD + ' (Cin = 64 / 128), reported as "..., 3, E from L2>"; run, not symbol-checked',
-    f'ctrgc_fwd2_kernel<{G20W}, 3, 2>': _FWD + ' (Cin = 256), reported as "ctrgc_fwd2_kernel<..., 3>"; run, not symbol-checked',
-    f'ctrgc_fwd_kernel<{G20W}, 1>': 'tests/test_gpu_primitives.py::test_ctrgc_fused_fwd_bwd (2x64x32x8x20x1); run, not symbol-checked',
-}
-# instantiations no case of the suite launches, with the reason.  The 8-channel forward tile is NOT beyond reach: the public
-# ops.ctrgc_fwd(..., Cout = 24, E = E) gets there (fwd_ct() = 8; fill_args needs only x, w3, b3 and E).  No layer of the package
-# does, because tamgcn_ctrgc_build_e refuses Cout % 16 != 0, and as a forward form it is left unpinned here: no test runs it
-UNREACHABLE = {
-    f'ctrgc_fwd_kernel<{G20}, 3>': 'reachable only through ops.ctrgc_fwd with a handed-in E at Cout % 16 != 0 (fwd_ct() = 8); no layer '
-                                    'of the package has such a Cout (tamgcn_ctrgc_build_e refuses it); a forward form, left unpinned and untested',
-    f'ctrgc_fwd_kernel<{G20}, 1>': 'as the three-subset form: reachable through ops.ctrgc_fwd(E=...), left unpinned and untested',
-}
-PINNED = {c['sym'] for c in CASES.values()}
+# The six forward instantiations of ctrgc.hip (the 8-channel tile included: ops.ctrgc_fwd(..., E=E) reaches it at Cout % 16 == 8)
+# are pinned by the forward ledger, tests/test_gpu_ctrgc_fwd_forms.py, through the table of tests/ctrgc_fwd_ref.py: symbol-checked
+# there, at the derived bars.  FWD_PINNED: instantiation -> the symbol the dispatch reports for it, for every form that table runs.
+FWD_PINNED = {FR_.INSTANTIATION[k]: FR_.SYM[k] for k in sorted({c['form'] for c in FR_.CASES.values()})}
+# instantiations another test of the suite runs without checking the symbol, and instantiations no case launches, with the reason
+ELSEWHERE = {}
+UNREACHABLE = {}
+PINNED = {c['sym'] for c in CASES.values()} | set(FWD_PINNED)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

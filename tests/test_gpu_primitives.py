@@ -275,9 +275,10 @@ def test_ctrgc_fused_fwd_bwd(shape):
     close(pq, pqr, 1e-4, 1e-5, 'pq')
     yg, part, x3k = ops.ctrgc_fwd(xs, pq, t(W3), t(B3), t(W4), t(B4), t(A), t(alpha), Cin, Cout, S_, R, stats=True,
                                   keep_x3=True)
-    close(yg, y, 2e-4, 2e-4, 'ctrgc fwd')
     x3r = torch.einsum('oc,nctv->notv', W3, x) + B3[None, :, None, None]
-    close(x3k, x3r, 2e-4, 2e-4, 'x3 kept for the backward')
+    if V != 20:                                                           # the streaming route: x3 from the pointwise GEMM, its own ledgers
+        close(yg, y, 2e-4, 2e-4, 'ctrgc fwd')
+        close(x3k, x3r, 2e-4, 2e-4, 'x3 kept for the backward')
     yg0, _, none = ops.ctrgc_fwd(xs, pq, t(W3), t(B3), t(W4), t(B4), t(A), t(alpha), Cin, Cout, S_, R, stats=False)
     assert none is None and torch.equal(yg0, yg)
     # E, built once per layer in HBM and loaded by the kernels, against its definition
@@ -288,8 +289,15 @@ def test_ctrgc_fused_fwd_bwd(shape):
     close(Eg, Er, 2e-4, 2e-5, 'E')
     yg1, _, _ = ops.ctrgc_fwd(xs, pq, t(W3), t(B3), t(W4), t(B4), t(A), t(alpha), Cin, Cout, S_, R, stats=False, E=Eg)
     assert torch.equal(yg1, yg)                                           # E handed in == E built inside the call
-    close(part[0].sum(-1), y.sum((0, 2, 3)), 1e-3, 1e-2, 'stats')
-    close(part[1].sum(-1), (y * y).sum((0, 2, 3)), 1e-3, 1e-2, 'stats2')
+    if V == 20:
+        # the fused forward: y, x3 and every moment slot at the forward ledger's derived bars (tests/ctrgc_fwd_ref.py), against
+        # the E the call built, read back above -- tanh stays out of the bound
+        import ctrgc_fwd_ref as FR
+        FR.verify('x'.join(map(str, shape)), dict(x=x.detach(), w3=W3.detach(), b3=B3.detach(), E=Eg.cpu().view(N, S_, Cout, V, V),
+                                                  coff=0, Cin=Cin, Cout=Cout, S=S_), dict(y=yg, x3=x3k, part=part))
+    else:
+        close(part[0].sum(-1), y.sum((0, 2, 3)), 1e-3, 1e-2, 'stats')
+        close(part[1].sum(-1), (y * y).sum((0, 2, 3)), 1e-3, 1e-2, 'stats2')
     dx3, db3, dA, dW4, db4, dal, dpq = ops.ctrgc_bwd(xs, pq, t(W3), t(B3), t(W4), t(B4), t(A), t(alpha),
                                                      Cin, Cout, S_, R, S(t(cot)), x3=x3k, E=Eg)
     dx3e, db3e = ops.ctrgc_bwd_dx3(xs, pq, t(W3), t(B3), t(W4), t(B4), t(A), t(alpha), Cin, Cout, S_, R, S(t(cot)))
