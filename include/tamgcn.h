@@ -568,6 +568,48 @@ int tamgcn_feeder_transform_indexed(const double* raw, const long long* offsets,
                                     const double* rot, const int* idx, const int* parent, int B, int V, int time_steps,
                                     int center_joint, int mode, float* out, void* stream);
 
+/* ---- the feeder for fixed-shape skeleton arrays (csrc/clipfeeder.hip; tam_gcn_amd/feeder/clip_feeder.py) -------------------
+ * The split is ONE resident fp32 array raw (n_clips, C, T, V, M); a batch is (B, C, W, V, M) fp32.  Reference: the pipeline of
+ * feeder/feeder_nucla_fusion.py:95-106 over feeder/tools.py -- random_shift (:118-130), random_choose / auto_pading (:39-62)
+ * or the centre crop, random_move (:65-115).  Added in ABI 401 without a version bump: new entry points only.
+ *
+ * Shift and window compose to a PLAN of three integers per slot.  With (begin, end) the clip's extent, size = end - begin,
+ * bias the shift's draw on 0 .. T - size (0, begin = 0 and size = T without the shift) and d the window's offset -- the crop's
+ * start on 0 .. T - W when T > W, minus the pad position on 0 .. W - T when T < W, 0 when T = W; without random_choose
+ * (T - W) / 2 and 0 -- the plan is
+ *     src0 = d - bias + begin,  lo = max(0, bias - d),  hi = min(W, bias + size - d):
+ * output frame t is raw frame src0 + t for lo <= t < hi and zero elsewhere.
+ *
+ * The draw stream: Philox4x32-10, key = (seed low, seed high), counter = (call low, call high, slot b, block j); state int64 [2]
+ * = (seed, call) is READ ON THE DEVICE.  flags = 1 shift | 2 choose | 4 move.
+ *     block 0:      bias = mulhi(w0, T - size + 1);  d or the pad position = mulhi(w1, T - W + 1 or W - T + 1);  w2, w3 unused
+ *     block 1 + i:  node i of the move: angle index mulhi(w0, nA), scale index mulhi(w1, nS), t_x index mulhi(w2, nT), t_y index
+ *                   mulhi(w3, nT)
+ * The call counter advances by one after the draw, in a one-thread launch that follows it on the stream (plain store), iff
+ * flags != 0.
+ *
+ * _clip_extent    extent int32 [n_clips][2] = (begin, end): first valid frame and last valid frame + 1, a frame being valid iff
+ *                 any of its C V M elements != 0 (NaN is valid, -0.0 is not); no valid frame: (0, T).  One workgroup per clip.
+ * _clip_draw      clip_ids int64 [B] (slot b takes clip clip_ids[b] mod n_clips, Python's sign rule) -> plan int32 [B][3],
+ *                 draws int32 [B][2] = (bias, d), and with the move: move_idx int32 [B][num_node][4] and, when keys is given
+ *                 with the candidate tables angle fp64 [nA], scale [nS], trans [nT], keys fp64 [B][num_node][4] = (angle in
+ *                 degrees, scale, t_x, t_y); labels_out int64 [B] = labels[clip] when both are given.
+ * _clip_transform the gather: out (B, C, W, V, M) from raw, clip_ids and plan; frames the plan would take from outside the clip
+ *                 or the window are clamped away, so no plan reads out of bounds.  node int32 [num_node] and keys fp64
+ *                 [B][num_node][4] (both or neither) add the move: node = round_half_even(arange(0, W, W / move_time)) with
+ *                 W appended; in segment [node[i], node[i+1]) the four quantities follow np.linspace(key[i], key[i+1], n)
+ *                 (k (stop - start) / (n - 1) + start, last element stop, n = 1 -> start), the angle times pi, over 180; then
+ *                 for EVERY frame of the window, its zero frames included, in fp64 and in this order
+ *                     x' = (cos a . s) x + (-sin a . s) y + t_x,   y' = (sin a . s) x + (cos a . s) y + t_y
+ *                 of channels 0 and 1 (C >= 2), rounded to fp32 once; channels >= 2 are copied.  No atomics: two calls give
+ *                 the same bits. */
+int tamgcn_clip_extent(const float* raw, long long n_clips, int C, int T, int V, int M, int* extent, void* stream);
+int tamgcn_clip_draw(const int* extent, long long n_clips, const long long* clip_ids, int B, const long long* labels, long long* state,
+                     int flags, int T, int W, int num_node, int nA, int nS, int nT, const double* angle, const double* scale,
+                     const double* trans, int* plan, int* draws, int* move_idx, double* keys, long long* labels_out, void* stream);
+int tamgcn_clip_transform(const float* raw, long long n_clips, const long long* clip_ids, const int* plan, const int* node,
+                          const double* keys, int num_node, int B, int C, int T, int W, int V, int M, float* out, void* stream);
+
 /* ---- f2: the eval-mode TCN_GCN_unit for small batches (callers: reference
  * ensemble/ensemble_ctrgcn_resnet_eval.py:147-183, models/resnet_gcn_attention.py:82-85, visual.py:53-55 -- model(data)
  * on 1..16 clips in eval mode).  Five launches per block, each 50..130 workgroups per clip; V = 20, S = 3 (V = 25: the f2v

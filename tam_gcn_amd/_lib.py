@@ -226,6 +226,9 @@ SIGNATURES = {
     'tamgcn_feeder_transform': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     'tamgcn_feeder_draw': (_i, [_p, _ll, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     'tamgcn_feeder_transform_indexed': (_i, [_p, _p, _ll, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    'tamgcn_clip_extent': (_i, [_p, _ll, _i, _i, _i, _i, _p, _p]),
+    'tamgcn_clip_draw': (_i, [_p, _ll, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'tamgcn_clip_transform': (_i, [_p, _ll, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     'tamgcn_f2_e': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2_gcn': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2_gemm': (_i, [C.POINTER(F2GemmDesc), _p]),

@@ -3,6 +3,7 @@
 // bone / motion streams), as one workgroup per clip on the GPU, and the 4-stream derivation of BASELINE.json
 // configs[2] from a joint batch that is already resident in HBM.
 #include "common.h"
+#include "feeder_common.h"
 
 namespace {
 
@@ -38,12 +39,6 @@ struct FeederArgs {
     const long long* clip_ids;  // INDEXED only: [N] clip of every slot, taken modulo n_clips; offs is then the split's [n_clips + 1]
     long long n_clips;
 };
-
-// Python's i % n for n > 0 (the sign of the divisor): what Feeder.batch() does with `repeat`
-__device__ __forceinline__ long long clip_of(long long i, long long n) {
-    const long long r = i % n;
-    return r < 0 ? r + n : r;
-}
 
 __device__ __forceinline__ void rot_point(const double* p, const double* c, const double* R, double* o) {
     const double x = p[0] - c[0], y = p[1] - c[1], z = p[2] - c[2];
@@ -121,19 +116,7 @@ __global__ __launch_bounds__(256) void feeder_transform_kernel(const FeederArgs 
 }
 
 // ---- the train path's draws on the device (Feeder.batch_device) ----------------------------------------------------
-// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> four 32-bit words.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned* w) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-
+// (clip_of and Philox4x32-10: feeder_common.h)
 // o = a . b, 3 x 3 row-major, each entry summed left to right
 __device__ __forceinline__ void mat3(const double* a, const double* b, double* o) {
 #pragma unroll

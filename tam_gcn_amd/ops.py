@@ -1069,6 +1069,81 @@ def feeder_transform_indexed(raw, offsets, clip_ids, rot, idx, parent, V, time_s
     return out
 
 
+# the feeder for fixed-shape arrays (csrc/clipfeeder.hip; include/tamgcn.h has the plan and the draw stream)
+CLIP_SHIFT, CLIP_CHOOSE, CLIP_MOVE = 1, 2, 4
+
+
+def clip_extent(raw):
+    """raw (n_clips, C, T, V, M) fp32 resident split -> extent int32 (n_clips, 2) = (first valid frame, last valid frame + 1)."""
+    _want(raw, 'raw', torch.float32)
+    if raw.dim() != 5 or raw.numel() == 0:
+        raise RuntimeError(f'tam_gcn_amd: clip_extent takes a non-empty (n_clips, C, T, V, M) array, got {tuple(raw.shape)}')
+    n, C_, T, V, M = raw.shape
+    out = torch.empty(n, 2, device=raw.device, dtype=torch.int32)
+    _lib.check(_lib_().tamgcn_clip_extent(_ptr(raw), n, C_, T, V, M, _ptr(out), _stream()), 'tamgcn_clip_extent')
+    return out
+
+
+def clip_draw(extent, clip_ids, state, flags, T, W, num_node=0, candidates=None, labels=None):
+    """One batch's draws on the device (tamgcn_clip_draw).  extent int32 (n_clips, 2), clip_ids int64 [B] (taken modulo
+    n_clips), state int64 [2] = (seed, call) read on the device and advanced by one iff flags != 0; flags = CLIP_SHIFT |
+    CLIP_CHOOSE | CLIP_MOVE.  With CLIP_MOVE: num_node nodes and candidates = (angle, scale, trans), three 1-D fp64 tensors.
+    -> plan int32 (B, 3), draws int32 (B, 2), move_idx int32 (B, num_node, 4) | None, keys fp64 (B, num_node, 4) | None,
+    labels int64 (B,) | None.  No host sync, capturable."""
+    _want(extent, 'extent', torch.int32)
+    _want(clip_ids, 'clip_ids', torch.int64)
+    _want(state, 'state', torch.int64, (2,))
+    if extent.dim() != 2 or extent.shape[1] != 2 or clip_ids.dim() != 1:
+        raise RuntimeError('tam_gcn_amd: clip_draw takes extent (n_clips, 2) and 1-D clip_ids')
+    n_clips, B, dev = extent.shape[0], clip_ids.numel(), extent.device
+    if labels is not None:
+        _want(labels, 'labels', torch.int64, (n_clips,))
+    move_idx = keys = None
+    cand, nc = (None, None, None), (0, 0, 0)
+    if flags & CLIP_MOVE:
+        if candidates is None or len(candidates) != 3:
+            raise RuntimeError('tam_gcn_amd: clip_draw with CLIP_MOVE needs candidates = (angle, scale, trans)')
+        for t, name in zip(candidates, ('angle candidates', 'scale candidates', 'translation candidates')):
+            _want(t, name, torch.float64)
+            if t.dim() != 1 or t.numel() < 1:
+                raise RuntimeError(f'tam_gcn_amd: {name} must be a non-empty 1-D tensor')
+        cand, nc = tuple(candidates), tuple(t.numel() for t in candidates)
+        move_idx = torch.empty(B, num_node, 4, device=dev, dtype=torch.int32)
+        keys = torch.empty(B, num_node, 4, device=dev, dtype=torch.float64)
+    plan = torch.empty(B, 3, device=dev, dtype=torch.int32)
+    draws = torch.empty(B, 2, device=dev, dtype=torch.int32)
+    lab = torch.empty(B, device=dev, dtype=torch.int64) if labels is not None else None
+    _lib.check(_lib_().tamgcn_clip_draw(_ptr(extent), n_clips, _ptr(clip_ids), B, _ptr(labels), _ptr(state), int(flags), T, W, num_node,
+                                        nc[0], nc[1], nc[2], _ptr(cand[0]), _ptr(cand[1]), _ptr(cand[2]), _ptr(plan), _ptr(draws),
+                                        _ptr(move_idx), _ptr(keys), _ptr(lab), _stream()), 'tamgcn_clip_draw')
+    return plan, draws, move_idx, keys, lab
+
+
+def clip_transform(raw, clip_ids, plan, W, node=None, keys=None):
+    """The gather (tamgcn_clip_transform): raw (n_clips, C, T, V, M) fp32, clip_ids int64 [B] (taken modulo n_clips), plan int32
+    (B, 3) = (src0, lo, hi); with the move node int32 [num_node] and keys fp64 (B, num_node, 4) -> (B, C, W, V, M) fp32."""
+    _want(raw, 'raw', torch.float32)
+    _want(clip_ids, 'clip_ids', torch.int64)
+    if raw.dim() != 5 or raw.numel() == 0 or clip_ids.dim() != 1:
+        raise RuntimeError(f'tam_gcn_amd: clip_transform takes a non-empty (n_clips, C, T, V, M) array and 1-D clip_ids, got {tuple(raw.shape)}')
+    n, C_, T, V, M = raw.shape
+    B = clip_ids.numel()
+    _want(plan, 'plan', torch.int32, (B, 3))
+    num_node = 0
+    if (node is None) != (keys is None):
+        raise RuntimeError('tam_gcn_amd: clip_transform takes node and keys together')
+    if node is not None:
+        _want(node, 'node', torch.int32)
+        num_node = node.numel()
+        if node.dim() != 1:
+            raise RuntimeError('tam_gcn_amd: node must be 1-D')
+        _want(keys, 'keys', torch.float64, (B, num_node, 4))
+    out = torch.empty(B, C_, W, V, M, device=raw.device, dtype=torch.float32)
+    _lib.check(_lib_().tamgcn_clip_transform(_ptr(raw), n, _ptr(clip_ids), _ptr(plan), _ptr(node), _ptr(keys), num_node, B, C_, T, W, V, M,
+                                             _ptr(out), _stream()), 'tamgcn_clip_transform')
+    return out
+
+
 # ---------------------------------------------------------------------------
 # loss of the harness step (SURVEY.md §8 f1)
 def ce_fwd(logits, labels):
