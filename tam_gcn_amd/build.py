@@ -29,9 +29,8 @@ def sources():
 def needs_build():
     if not os.path.exists(LIB):
         return True
-    deps = sources() + [os.path.join(HERE, 'csrc', 'common.h'), os.path.join(HERE, 'csrc', 'evalbody.h'), os.path.join(HERE, 'csrc', 'f2s_common.h'),
-                        os.path.join(HERE, 'csrc', 'feeder_common.h'),
-                        os.path.join(HERE, '..', 'include', 'tamgcn.h')]
+    csrc = os.path.join(HERE, 'csrc')
+    deps = sources() + [os.path.join(csrc, h) for h in os.listdir(csrc) if h.endswith('.h')] + [os.path.join(HERE, '..', 'include', 'tamgcn.h')]
     t = os.path.getmtime(LIB)
     return any(os.path.getmtime(d) > t for d in deps)
 

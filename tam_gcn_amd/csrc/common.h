@@ -38,23 +38,6 @@ int tamgcn_split_mode(void);     // TAMGCN_SPLIT_BF16: 0 (default) = exact fp32-
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// Grouped launches of the small-batch eval families (f2.hip, f2v.hip; include/tamgcn.h "grouped").  groups >= 1, N a multiple
-// of it; and where a launch reads a weight array in 16-byte pieces the group stride must keep the pieces aligned.  That second
-// condition cannot fail today -- a vector path needs a row length that is a multiple of 16, and every group stride is a
-// multiple of the row length -- it is checked so that a new vec condition cannot break it silently.
-static inline int tg_groups_ok(int N, int groups, const char* who) {
-    TG_CHECK(groups >= 1 && N % groups == 0, "%s: N=%d is not a multiple of groups=%d", who, N, groups);
-    return 0;
-}
-static inline int tg_group_stride_ok(bool vec, long long stride, const char* who, const char* what) {
-    TG_CHECK(!vec || stride % 4 == 0, "%s: group stride of %s (%lld floats) breaks the 16-byte alignment of its vector path", who, what, stride);
-    return 0;
-}
-static inline int tg_gcn_group_strides_ok(const tamgcn_f2_gcn_desc* d, bool vec12, bool vec4, bool vec3, bool vecd, const char* who) {
-    return tg_group_stride_ok(vec12, (long long)d->S * 2 * d->R * d->Cin, who, "w12") || tg_group_stride_ok(vec4, (long long)d->S * d->Cout * d->R, who, "w4") ||
-           tg_group_stride_ok(vec3, (long long)d->S * d->Cout * d->Cin, who, "w3") || tg_group_stride_ok(vecd, (long long)d->Cout * d->Cin, who, "wd");
-}
-
 constexpr int NTHREADS = 256;    // workgroup of the register-staged GEMM kernels (conv.hip, wgrad.hip)
 
 static inline bool tg_debug_occ() {          // TAMGCN_DEBUG_OCC, read once per process

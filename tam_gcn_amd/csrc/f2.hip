@@ -20,48 +20,23 @@
 // All GEMMs: v_mfma_f32_16x16x4_f32 (exact fp32), A rows straight from global memory (L2-resident weights, 16 bytes per lane
 // and 16-k block, prefetched one block ahead), B = the LDS tile, the K blocks of a product dealt round-robin to the waves and
 // the partial tiles summed through LDS in a fixed order (deterministic).  V = 20 only.
-#include "common.h"
+#include "f2_common.h"
 
 namespace {
 
-constexpr int F2_NT = 256, F2_V = 20, F2_VV = 400, F2_BT = 4, F2_NCT = 5, F2_PB = 84;   // 4 frames x 20 joints = 80 columns = 5 MFMA tiles
+constexpr int F2_V = 20, F2_VV = 400, F2_NCT = 5, F2_PB = 84;   // 4 frames (F2_BT) x 20 joints = 80 columns = 5 MFMA tiles
 // pitch 84: the four k rows (4*kq + i) a fragment read touches sit 4*84 = 16 (mod 64) banks apart: conflict-free
 
-// A fragment of one 16-k block: lane (j, kq) holds A[row j][k0 + 4*kq + i], i = 0..3 (MFMA step i of the block contracts
-// k = k0 + 4*kq + i on BOTH operands: any bijection between (step, kq) and k is a valid K order)
-__device__ __forceinline__ void f2_load_a(const float* arow, int K, int k0, int kq, bool vec, float (&a)[4]) {
-    const int k = k0 + 4 * kq;
-    if (vec) {
-        const float4 t = arow ? *reinterpret_cast<const float4*>(arow + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        a[0] = t.x; a[1] = t.y; a[2] = t.z; a[3] = t.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a[i] = (arow && k + i < K) ? arow[k + i] : 0.f;
-    }
-}
-
-// acc[ct] += A[16 rows][k blocks kb0, kb0 + kbstep, ...] * B, B value for this lane's column of tile ct at row k = bf(k, ct).
-// A fragments are fetched four blocks at a time, one group ahead: with one block in flight the loop was one L2 round trip
-// (~0.8 us) per 20 MFMAs (~0.1 us).
-constexpr int F2_G = 4;
-__device__ __forceinline__ void f2_load_group(const float* arow, int K, bool vec, int kb, int kbstep, int kq, float (&dst)[F2_G][4]) {
-    const int nkb = (K + 15) >> 4;
-#pragma unroll
-    for (int g = 0; g < F2_G; ++g) {
-        const int b = kb + g * kbstep;
-        if (b < nkb) f2_load_a(arow, K, b * 16, kq, vec, dst[g]);
-        else { dst[g][0] = dst[g][1] = dst[g][2] = dst[g][3] = 0.f; }
-    }
-}
-
-// a: the first group (blocks kb0, kb0 + kbstep, ...), already requested by the caller -- before whatever B waits for
+// f2_load_a and f2_load_group are f2_common.h's.  This family's form of its f2_gemm16: the first group of A fragments (blocks
+// kb0, kb0 + kbstep, ...) is in `a` already, requested by the caller ahead of whatever B waits for (the staging of the tile);
+// K is taken whole (nkb blocks).
 template <int NCT, class BF>
 __device__ __forceinline__ void f2_gemm16_pre(f32x4 (&acc)[NCT], float (&a)[F2_G][4], const float* arow, int K, bool vec, int kb0, int kbstep, int kq, BF bf) {
     constexpr int G = F2_G;
     const int nkb = (K + 15) >> 4;
     float an[G][4];
     for (int kb = kb0; kb < nkb; kb += G * kbstep) {
-        f2_load_group(arow, K, vec, kb + G * kbstep, kbstep, kq, an);
+        f2_load_group(arow, K, vec, kb + G * kbstep, nkb, kbstep, kq, an);
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             const int b = kb + g * kbstep;
@@ -81,10 +56,11 @@ __device__ __forceinline__ void f2_gemm16_pre(f32x4 (&acc)[NCT], float (&a)[F2_G
     }
 }
 
+// the whole K of a row of A, nothing requested ahead
 template <int NCT, class BF>
-__device__ __forceinline__ void f2_gemm16(f32x4 (&acc)[NCT], const float* arow, int K, bool vec, int kb0, int kbstep, int kq, BF bf) {
+__device__ __forceinline__ void f2_gemm16_k(f32x4 (&acc)[NCT], const float* arow, int K, bool vec, int kb0, int kbstep, int kq, BF bf) {
     float a[F2_G][4];
-    f2_load_group(arow, K, vec, kb0, kbstep, kq, a);
+    f2_load_group(arow, K, vec, kb0, (K + 15) >> 4, kbstep, kq, a);
     f2_gemm16_pre<NCT>(acc, a, arow, K, vec, kb0, kbstep, kq, bf);
 }
 
@@ -112,28 +88,8 @@ __device__ __forceinline__ void f2_stage(float* Bs, const float* src, long long 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-struct F2GcnArgs {
-    int N, Cin, Cout, T, S, R, res_mode;
-    const float *x, *w12, *b12, *w4, *b4, *A, *alpha, *w3, *b3, *sy, *ty, *wd, *bd, *xpart;
-    float *E, *sum, *diff;
-    int vec12, vec4, vec3, vecd;
-};
-
-// Grouped launches (include/tamgcn.h, "grouped"): samples [g*npg, (g+1)*npg) use the g-th of the parameter arrays that follow
-// one another densely behind group 0's.  g comes from blockIdx.y alone: the offset bases stay scalar.
-__device__ __forceinline__ F2GcnArgs f2_group(F2GcnArgs a, int g) {
-    const long long SC = (long long)a.S * a.Cout;
-    a.w12 += g * (long long)a.S * 2 * a.R * a.Cin; a.b12 += g * a.S * 2 * a.R;
-    a.w4 += g * SC * a.R; a.b4 += g * SC;
-    a.A += g * a.S * F2_VV; a.alpha += g;
-    a.w3 += g * SC * a.Cin; a.b3 += g * SC;
-    a.sy += g * a.Cout; a.ty += g * a.Cout;
-    if (a.res_mode == 2) { a.wd += (long long)g * a.Cout * a.Cin; a.bd += g * a.Cout; }
-    return a;
-}
-
 // ---- E for 16 channels of one (sample, subset)
-constexpr int F2_PX = 36, F2_PD = 404;     // xbar / pq pitch (20 columns in two tiles), D pitch (4*404 = 16 mod 64)
+constexpr int F2_PD = 404;                 // D pitch (4*404 = 16 mod 64)
 
 __device__ __forceinline__ void f2_e_body(const F2GcnArgs& a) {
     constexpr int V = F2_V, VV = F2_VV, NT = F2_NT, PX = F2_PX, PD = F2_PD, NTP = 4;
@@ -155,7 +111,7 @@ __device__ __forceinline__ void f2_e_body(const F2GcnArgs& a) {
     const int prt = wave % nrt, ppart = wave / nrt;
     const float* a12 = ppart < nparts && prt * 16 + j < R2 ? a.w12 + ((long long)s * R2 + prt * 16 + j) * a.Cin : nullptr;
     float a12g[F2_G][4];
-    f2_load_group(a12, a.Cin, a.vec12 != 0, ppart, nparts, kq, a12g);
+    f2_load_group(a12, a.Cin, a.vec12 != 0, ppart, Kp >> 4, nparts, kq, a12g);
     float b12r[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) b12r[i] = tid + i * NT < R2 * V ? a.b12[s * R2 + (tid + i * NT) / V] : 0.f;
@@ -298,10 +254,10 @@ __device__ __forceinline__ void f2_e_body(const F2GcnArgs& a) {
 }
 
 __global__ __launch_bounds__(F2_NT) void f2_e_kernel(const F2GcnArgs a) { f2_e_body(a); }
-__global__ __launch_bounds__(F2_NT) void f2_e_grouped_kernel(const F2GcnArgs a, int npg) { f2_e_body(f2_group(a, blockIdx.y / npg)); }
+__global__ __launch_bounds__(F2_NT) void f2_e_grouped_kernel(const F2GcnArgs a, int npg) { f2_e_body(f2_group(a, blockIdx.y / npg, F2_VV)); }
 
 // ---- x3 GEMM + aggregation + BatchNorm + residual for 8 channels x 4 frames
-constexpr int F2_CT = 8, F2_ES = 3328;     // E run of one subset: 8 * 400 floats = 12.5 DMA pieces of 1 KB, padded to 13
+constexpr int F2_ES = 3328;                // E run of one subset: 8 * 400 floats = 12.5 DMA pieces of 1 KB, padded to 13
 
 __device__ __forceinline__ void f2_gcn_body(const F2GcnArgs& a) {
     constexpr int V = F2_V, VV = F2_VV, NT = F2_NT, PB = F2_PB, CT = F2_CT, ES = F2_ES;
@@ -333,7 +289,7 @@ __device__ __forceinline__ void f2_gcn_body(const F2GcnArgs& a) {
         vec = sidx < 3 ? a.vec3 != 0 : a.vecd != 0;               // (uniform per 8 lanes, both paths are branch-safe)
     }
     float ag[F2_G][4];
-    f2_load_group(arow, a.Cin, vec, kh, 2, kq, ag);                // weights travel under the staging of the tile
+    f2_load_group(arow, a.Cin, vec, kh, Kp >> 4, 2, kq, ag);                // weights travel under the staging of the tile
     f2_stage(Xs, a.x + (long long)n * a.Cin * TV + (long long)t0 * V, TV, a.Cin, Kp, bt, 1, tid);
     __syncthreads();
     {
@@ -391,17 +347,11 @@ __device__ __forceinline__ void f2_gcn_body(const F2GcnArgs& a) {
 }
 
 __global__ __launch_bounds__(F2_NT) void f2_gcn_kernel(const F2GcnArgs a) { f2_gcn_body(a); }
-__global__ __launch_bounds__(F2_NT) void f2_gcn_grouped_kernel(const F2GcnArgs a, int npg) { f2_gcn_body(f2_group(a, blockIdx.y / npg)); }
+__global__ __launch_bounds__(F2_NT) void f2_gcn_grouped_kernel(const F2GcnArgs a, int npg) { f2_gcn_body(f2_group(a, blockIdx.y / npg, F2_VV)); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 16 rows x 4 frames of a pointwise product with the block's epilogues
 // ---------------------------------------------------------------------------------------------------------------------
-struct F2GemmArgs {
-    int N, K, M, T, mode, relu_rows, vec;
-    const float *x, *w, *b, *add;
-    float* out;
-};
-
 __device__ __forceinline__ void f2_gemm_body(const F2GemmArgs& a) {
     constexpr int V = F2_V, NT = F2_NT, PB = F2_PB;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -415,7 +365,7 @@ __device__ __forceinline__ void f2_gemm_body(const F2GemmArgs& a) {
     const long long TV = (long long)a.T * V;
     const float* arow = a.w + (long long)(m0 + j) * a.K;
     float ag[F2_G][4];
-    f2_load_group(arow, a.K, a.vec != 0, wave, 4, kq, ag);         // weights travel under the staging of the tile
+    f2_load_group(arow, a.K, a.vec != 0, wave, Kp >> 4, 4, kq, ag);         // weights travel under the staging of the tile
     f2_stage(Bs, a.x + (long long)n * a.K * TV + (long long)t0 * V, TV, a.K, Kp, bt, 1, tid);
     __syncthreads();
     {
@@ -454,29 +404,12 @@ __device__ __forceinline__ void f2_gemm_body(const F2GemmArgs& a) {
 }
 
 __global__ __launch_bounds__(F2_NT) void f2_gemm_kernel(const F2GemmArgs a) { f2_gemm_body(a); }
-__global__ __launch_bounds__(F2_NT) void f2_gemm_grouped_kernel(const F2GemmArgs a, int npg) {
-    F2GemmArgs b = a;
-    const int g = blockIdx.y / npg;
-    b.w += (long long)g * a.M * a.K;
-    b.b += g * a.M;
-    f2_gemm_body(b);
-}
+__global__ __launch_bounds__(F2_NT) void f2_gemm_grouped_kernel(const F2GemmArgs a, int npg) { f2_gemm_body(f2_group(a, blockIdx.y / npg)); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // MS-TCN after its entry convs + the block's residual and ReLU: 16 output channels x 4 output frames
 // ---------------------------------------------------------------------------------------------------------------------
-struct F2TcnArgs {
-    int N, Cin, Cout, T, T2, stride, Cb, nb, ks, res_mode, vect, vecr;
-    int dil[4];
-    const float* h;                      // (N, Cout, T, V): entry outputs (ReLU applied) of branches 0..nb, then the plain branch
-    const float* wt[4]; const float* bt[4];   // [Cb][Cb*ks] folded, [Cb]
-    const float *sp, *tp;                // pooled branch's BatchNorm as an affine [Cb]
-    const float *x, *wr, *br;            // block input (N, Cin, T, V); folded residual conv [Cout][Cin], [Cout]
-    float* out;                          // (N, Cout, T2, V)
-    float* xpart;                        // NULL | (N, ceil(T2 / 4), Cout, V): sum over each tile's frames of out (the next block's xbar)
-};
-
-constexpr int F2_HF = 15, F2_PH = F2_HF * F2_V + 4;    // halo tile: 3*stride + (ks-1)*dil + 1 <= 15 frames
+constexpr int F2_PH = F2_HF * F2_V + 4;      // halo tile pitch
 
 __device__ __forceinline__ void f2_tcn_body(const F2TcnArgs& a, const int g) {
     constexpr int V = F2_V, NT = F2_NT, PB = F2_PB, PH = F2_PH;
@@ -537,14 +470,14 @@ __device__ __forceinline__ void f2_tcn_body(const F2TcnArgs& a, const int g) {
                 boff[ct] = tl * a.stride * V + v;
             }
             const int K = a.Cb * a.ks;
-            f2_gemm16<F2_NCT>(acc, a.wt[branch] + (long long)g * a.Cb * K + (long long)(cb0 + j) * K, K, a.vect != 0, wave, 4, kq, [&](int k, int ct) {
+            f2_gemm16_k<F2_NCT>(acc, a.wt[branch] + (long long)g * a.Cb * K + (long long)(cb0 + j) * K, K, a.vect != 0, wave, 4, kq, [&](int k, int ct) {
                 const int ci = k / a.ks, tap = k - ci * a.ks;
                 return Hs[ci * PH + tap * d * V + boff[ct]];
             });
         }
         if (a.res_mode == 2)
-            f2_gemm16<F2_NCT>(acc, a.wr + (long long)g * a.Cout * a.Cin + (long long)(c0 + j) * a.Cin, a.Cin, a.vecr != 0, wave, 4, kq,
-                              [&](int k, int ct) { return Xs[k * PB + ct * 16 + j]; });
+            f2_gemm16_k<F2_NCT>(acc, a.wr + (long long)g * a.Cout * a.Cin + (long long)(c0 + j) * a.Cin, a.Cin, a.vecr != 0, wave, 4, kq,
+                                [&](int k, int ct) { return Xs[k * PB + ct * 16 + j]; });
 #pragma unroll
         for (int ct = 0; ct < F2_NCT; ++ct)
 #pragma unroll
@@ -617,48 +550,24 @@ __device__ __forceinline__ void f2_tcn_body(const F2TcnArgs& a, const int g) {
 __global__ __launch_bounds__(F2_NT) void f2_tcn_kernel(const F2TcnArgs a) { f2_tcn_body(a, 0); }
 __global__ __launch_bounds__(F2_NT) void f2_tcn_grouped_kernel(const F2TcnArgs a, int npg) { f2_tcn_body(a, blockIdx.y / npg); }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-size_t f2_e_lds(int Cin, int R) {
-    const int Kp = (Cin + 15) & ~15, R2p = 2 * R < 16 ? 16 : 2 * R, Rp = (R + 15) & ~15;
-    const size_t tail = (size_t)Rp * F2_PD > (size_t)4 * Kp * F2_V ? (size_t)Rp * F2_PD : (size_t)4 * Kp * F2_V;
-    return sizeof(float) * ((size_t)Kp * F2_PX + (size_t)R2p * F2_PX + 64 * F2_PX + tail);
-}
-size_t f2_gcn_lds(int Cin) { return sizeof(float) * ((size_t)((Cin + 15) & ~15) * F2_PB + 2 * 32 * F2_PB + 3 * F2_ES); }
-size_t f2_gemm_lds(int K) { return sizeof(float) * ((size_t)((K + 15) & ~15) * F2_PB + 4 * 16 * F2_PB); }
-size_t f2_tcn_lds(int Cin, int Cb, int res_mode) {
+constexpr size_t f2_e_lds(int Cin, int R) { return f2_e_lds(Cin, R, 4, F2_V, F2_PD); }
+constexpr size_t f2_gcn_lds(int Cin) { return f2_gcn_lds(Cin, 256, F2_PB, F2_ES); }                // the whole K in one chunk
+constexpr size_t f2_gemm_lds(int K) { return f2_gemm_lds(K, F2_PB); }
+size_t f2_tcn_lds(int Cin, int Cb, int res_mode) {                                                 // two regions, side by side
     return sizeof(float) * ((size_t)5 * 16 * F2_PB + (size_t)(res_mode == 2 ? (Cin + 15) & ~15 : 0) * F2_PB + (size_t)Cb * F2_PH);
 }
 
-int f2_fill(const tamgcn_f2_gcn_desc* d, F2GcnArgs* a, const char* who) {
-    TG_CHECK(d && d->x && d->w12 && d->b12 && d->w4 && d->b4 && d->A && d->alpha && d->w3 && d->b3 && d->sy && d->ty && d->E,
-             "%s: null pointer", who);
-    TG_CHECK(d->V == F2_V && d->S == 3, "%s: V=%d S=%d (this family is built for V = 20, S = 3)", who, d->V, d->S);
-    TG_CHECK(d->N > 0 && d->T > 0 && d->Cin > 0 && d->Cin <= 256 && d->Cout > 0 && d->Cout % 16 == 0,
-             "%s: bad shape N=%d T=%d Cin=%d Cout=%d (Cin <= 256, Cout %% 16 == 0)", who, d->N, d->T, d->Cin, d->Cout);
-    TG_CHECK(d->R >= 1 && d->R <= 32, "%s: R=%d outside 1..32", who, d->R);
-    TG_CHECK(d->res_mode >= 0 && d->res_mode <= 2, "%s: res_mode=%d", who, d->res_mode);
-    TG_CHECK(d->res_mode != 1 || d->Cin == d->Cout, "%s: identity residual needs Cin == Cout", who);
-    TG_CHECK(d->res_mode != 2 || (d->wd && d->bd), "%s: convolutional residual without weights", who);
-    TG_CHECK(al16(d->x) && al16(d->E) && (!d->xpart || al16(d->xpart)), "%s: x, E and xpart must be 16-byte aligned", who);
-    a->N = d->N; a->Cin = d->Cin; a->Cout = d->Cout; a->T = d->T; a->S = d->S; a->R = d->R; a->res_mode = d->res_mode;
-    a->x = d->x; a->w12 = d->w12; a->b12 = d->b12; a->w4 = d->w4; a->b4 = d->b4; a->A = d->A; a->alpha = d->alpha;
-    a->w3 = d->w3; a->b3 = d->b3; a->sy = d->sy; a->ty = d->ty; a->wd = d->wd; a->bd = d->bd;
-    a->E = d->E; a->sum = d->sum; a->diff = d->diff; a->xpart = d->xpart;
-    a->vec12 = d->Cin % 16 == 0 && al16(d->w12);
-    a->vec3 = d->Cin % 16 == 0 && al16(d->w3);
-    a->vecd = d->res_mode == 2 && d->Cin % 16 == 0 && al16(d->wd);
-    a->vec4 = d->R % 16 == 0 && al16(d->w4);
-    return 0;
-}
+bool f2_served(int V) { return V == F2_V; }
+// (the gcn descriptors and the pointwise ones have always been told apart in the text of a refused V)
+const F2Family F2_GCN_FAMILY = {f2_served, "this family is built for V = 20, S = 3", "null pointer", 16, "x, E and xpart must be 16-byte aligned", nullptr, true};
+const F2Family F2_FAMILY = {f2_served, "built for V = 20", "null pointer", 16, nullptr, "activations must be 16-byte aligned", false};
 
-// groups == 0: the plain entry point; otherwise the grouped one (common.h: tg_groups_ok, tg_group_stride_ok).
+// groups == 0: the plain entry point; otherwise the grouped one.
 int f2_e_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
     F2GcnArgs a;
-    if (f2_fill(d, &a, who)) return -1;
+    if (f2_gcn_args(d, &a, F2_GCN_FAMILY, false, who) || f2_gcn_groups_ok(a, groups, who)) return -1;
     const dim3 grid(d->S * (d->Cout / 16), d->N);
     if (groups) {
-        if (tg_groups_ok(d->N, groups, who) || tg_gcn_group_strides_ok(d, a.vec12, a.vec4, a.vec3, a.vecd, who)) return -1;
         tg_launch_lds<f2_e_grouped_kernel>(f2_e_lds(256, 32), grid, dim3(F2_NT), f2_e_lds(d->Cin, d->R), (hipStream_t)stream, a, d->N / groups);
         tamgcn_note_kernel("f2_e_grouped_kernel");
     } else {
@@ -671,11 +580,9 @@ int f2_e_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const cha
 
 int f2_gcn_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
     F2GcnArgs a;
-    if (f2_fill(d, &a, who)) return -1;
-    TG_CHECK(d->sum && d->diff && al16(d->sum) && al16(d->diff), "%s: null or misaligned output", who);
+    if (f2_gcn_args(d, &a, F2_GCN_FAMILY, true, who) || f2_gcn_groups_ok(a, groups, who)) return -1;
     const dim3 grid(ceil_div(d->T, F2_BT) * (d->Cout / F2_CT), d->N);
     if (groups) {
-        if (tg_groups_ok(d->N, groups, who) || tg_gcn_group_strides_ok(d, a.vec12, a.vec4, a.vec3, a.vecd, who)) return -1;
         tg_launch_lds<f2_gcn_grouped_kernel>(f2_gcn_lds(256), grid, dim3(F2_NT), f2_gcn_lds(d->Cin), (hipStream_t)stream, a, d->N / groups);
         tamgcn_note_kernel("f2_gcn_grouped_kernel");
     } else {
@@ -687,21 +594,10 @@ int f2_gcn_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const c
 }
 
 int f2_gemm_launch(const tamgcn_f2_gemm_desc* d, int groups, void* stream, const char* who) {
-    TG_CHECK(d && d->x && d->w && d->b && d->out, "%s: null pointer", who);
-    TG_CHECK(d->V == F2_V, "%s: V=%d (built for V = 20)", who, d->V);
-    TG_CHECK(d->N > 0 && d->T > 0 && d->K > 0 && d->K <= 256 && d->M > 0 && d->M % 16 == 0,
-             "%s: bad shape N=%d T=%d K=%d M=%d (K <= 256, M %% 16 == 0)", who, d->N, d->T, d->K, d->M);
-    TG_CHECK(d->mode == 0 || d->mode == 1, "%s: mode=%d", who, d->mode);
-    TG_CHECK(d->mode != 0 || d->add, "%s: mode 0 needs the addend", who);
-    TG_CHECK(al16(d->x) && al16(d->out) && (!d->add || al16(d->add)), "%s: activations must be 16-byte aligned", who);
     F2GemmArgs a;
-    a.N = d->N; a.K = d->K; a.M = d->M; a.T = d->T; a.mode = d->mode; a.relu_rows = d->relu_rows;
-    a.vec = d->K % 16 == 0 && al16(d->w);
-    a.x = d->x; a.w = d->w; a.b = d->b; a.add = d->add; a.out = d->out;
+    if (f2_gemm_args(d, &a, F2_FAMILY, who) || f2_gemm_groups_ok(a, groups, who)) return -1;
     const dim3 grid(ceil_div(d->T, F2_BT) * (d->M / 16), d->N);
     if (groups) {
-        if (tg_groups_ok(d->N, groups, who)) return -1;
-        if (tg_group_stride_ok(a.vec, (long long)d->M * d->K, who, "w")) return -1;
         tg_launch_lds<f2_gemm_grouped_kernel>(f2_gemm_lds(256), grid, dim3(F2_NT), f2_gemm_lds(d->K), (hipStream_t)stream, a, d->N / groups);
         tamgcn_note_kernel("f2_gemm_grouped_kernel");
     } else {
@@ -713,47 +609,17 @@ int f2_gemm_launch(const tamgcn_f2_gemm_desc* d, int groups, void* stream, const
 }
 
 int f2_tcn_launch(const tamgcn_f2_tcn_desc* d, int groups, void* stream, const char* who) {
-    TG_CHECK(d && d->h && d->out && d->sp && d->tp, "%s: null pointer", who);
-    TG_CHECK(d->V == F2_V, "%s: V=%d (built for V = 20)", who, d->V);
-    TG_CHECK(d->N > 0 && d->T > 0 && d->Cout > 0 && d->Cout % 16 == 0 && d->stride >= 1 && d->stride <= 2,
-             "%s: bad shape N=%d T=%d Cout=%d stride=%d", who, d->N, d->T, d->Cout, d->stride);
-    TG_CHECK(d->nb >= 1 && d->nb <= 4 && d->Cb % 16 == 0 && d->Cb <= 64 && (d->nb + 2) * d->Cb == d->Cout,
-             "%s: nb=%d Cb=%d Cout=%d (Cb %% 16 == 0, Cb <= 64, (nb + 2) Cb == Cout)", who, d->nb, d->Cb, d->Cout);
-    TG_CHECK(d->ks >= 1 && d->ks % 2 == 1, "%s: kernel size %d", who, d->ks);
-    for (int b = 0; b < d->nb; ++b) {
-        TG_CHECK(d->wt[b] && d->bt[b] && d->dil[b] >= 1, "%s: branch %d: null weights or dilation %d", who, b, d->dil[b]);
-        TG_CHECK((F2_BT - 1) * d->stride + (d->ks - 1) * d->dil[b] + 1 <= F2_HF, "%s: branch %d: halo of k=%d dilation %d stride %d exceeds %d frames",
-                 who, b, d->ks, d->dil[b], d->stride, F2_HF);
-    }
-    TG_CHECK(d->res_mode >= 0 && d->res_mode <= 2, "%s: res_mode=%d", who, d->res_mode);
-    TG_CHECK(d->res_mode == 0 || d->x, "%s: residual without the block input", who);
-    TG_CHECK(d->res_mode != 1 || (d->Cin == d->Cout && d->stride == 1), "%s: identity residual needs Cin == Cout, stride 1", who);
-    TG_CHECK(d->res_mode != 2 || (d->wr && d->br && d->Cin > 0 && d->Cin <= 256), "%s: convolutional residual: weights / Cin=%d", who, d->Cin);
-    TG_CHECK(al16(d->h) && al16(d->out) && (!d->x || al16(d->x)) && (!d->xpart || al16(d->xpart)), "%s: activations must be 16-byte aligned", who);
     F2TcnArgs a;
-    a.N = d->N; a.Cin = d->Cin; a.Cout = d->Cout; a.T = d->T; a.stride = d->stride; a.T2 = (d->T - 1) / d->stride + 1;
-    a.Cb = d->Cb; a.nb = d->nb; a.ks = d->ks; a.res_mode = d->res_mode;
-    bool vt = (d->Cb * d->ks) % 16 == 0;
-    for (int b = 0; b < 4; ++b) {
-        a.dil[b] = b < d->nb ? d->dil[b] : 1;
-        a.wt[b] = b < d->nb ? d->wt[b] : nullptr;
-        a.bt[b] = b < d->nb ? d->bt[b] : nullptr;
-        if (b < d->nb) vt = vt && al16(d->wt[b]);
-    }
-    a.vect = vt;
-    a.vecr = d->res_mode == 2 && d->Cin % 16 == 0 && al16(d->wr);
-    a.h = d->h; a.sp = d->sp; a.tp = d->tp; a.x = d->x; a.wr = d->wr; a.br = d->br; a.out = d->out; a.xpart = d->xpart;
+    if (f2_tcn_args(d, &a, F2_FAMILY, who)) return -1;
     const size_t lds = f2_tcn_lds(d->Cin, d->Cb, d->res_mode);
-    TG_CHECK(lds <= 160 * 1024, "%s: %zu bytes of LDS", who, lds);
+    TG_CHECK(lds <= F2_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
+    if (f2_tcn_groups_ok(a, groups, who)) return -1;
     const dim3 grid(ceil_div(a.T2, F2_BT) * (d->Cout / 16), d->N);
     if (groups) {
-        if (tg_groups_ok(d->N, groups, who)) return -1;
-        if (tg_group_stride_ok(a.vect, (long long)d->Cb * d->Cb * d->ks, who, "wt")) return -1;
-        if (tg_group_stride_ok(a.vecr, (long long)d->Cout * d->Cin, who, "wr")) return -1;
-        tg_launch_lds<f2_tcn_grouped_kernel>(160 * 1024, grid, dim3(F2_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tg_launch_lds<f2_tcn_grouped_kernel>(F2_LDS_MAX, grid, dim3(F2_NT), lds, (hipStream_t)stream, a, d->N / groups);
         tamgcn_note_kernel("f2_tcn_grouped_kernel");
     } else {
-        tg_launch_lds<f2_tcn_kernel>(160 * 1024, grid, dim3(F2_NT), lds, (hipStream_t)stream, a);
+        tg_launch_lds<f2_tcn_kernel>(F2_LDS_MAX, grid, dim3(F2_NT), lds, (hipStream_t)stream, a);
         tamgcn_note_kernel("f2_tcn_kernel");
     }
     TG_LAUNCH_CHECK(who);
@@ -767,10 +633,6 @@ extern "C" int tamgcn_f2_gcn(const tamgcn_f2_gcn_desc* d, void* stream) { return
 extern "C" int tamgcn_f2_gemm(const tamgcn_f2_gemm_desc* d, void* stream) { return f2_gemm_launch(d, 0, stream, "tamgcn_f2_gemm"); }
 extern "C" int tamgcn_f2_tcn(const tamgcn_f2_tcn_desc* d, void* stream) { return f2_tcn_launch(d, 0, stream, "tamgcn_f2_tcn"); }
 
-static int f2_groups_arg(int groups, const char* who) {
-    TG_CHECK(groups >= 1, "%s: groups=%d", who, groups);
-    return 0;
-}
 extern "C" int tamgcn_f2_e_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream) {
     return f2_groups_arg(groups, "tamgcn_f2_e_grouped") ? -1 : f2_e_launch(d, groups, stream, "tamgcn_f2_e_grouped");
 }

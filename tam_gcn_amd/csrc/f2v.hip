@@ -1,815 +1,131 @@
 // f2v: the small-batch eval-mode TCN_GCN_unit (f2.hip's family: same four stages, same algebra, include/tamgcn.h) for
-// skeletons whose joint count is NOT a multiple of four -- NTU-RGB+D's V = 25, COCO's 17, OpenPose's 18.  A sibling with its
-// own geometry, as ctrgc_tiled.hip is to ctrgc.hip, because three things of the V = 20 kernels do not carry over (told below
-// in the numbers of V = 25, VP = 28; FvGeo<V> has them for every V: at 17 and 18 VP = 20, a frame is five 16-byte pieces, a
-// tile 80 columns = 5 MFMA tiles, and V = 18 keeps TWO lanes of a frame's last piece where 17 and 25 keep one):
-//
-//   alignment   a (n, c) row of T*25 floats starts on a 16-byte boundary only by accident (300 -> 150 -> 75 frames).  Only the
-//               block's input and output keep that contiguous (N, C, T, V) form.  Everything the family allocates for itself
-//               (E, the four workspaces, the frame sums) has frames of VP = 28 floats: every row and every frame is 16-byte
-//               aligned, and the staging of those is f2's float4 copy with 20 -> 28.  The block input is read in 16-byte
-//               pieces from dword-aligned addresses (full rate on gfx950, tools/probes/unaligned_probe.hip), seven per frame; the
-//               seventh reaches 12 bytes past the frame -- into the next one or, at the very end, into the allocator's slack --
-//               and those three lanes are REPLACED by zeros (a select, never a product) before anything consumes them.
-//   tile count  four frames at pitch 28 are 112 columns = exactly 7 MFMA tiles (6.25 at pitch 25).  The 12 pad columns of a tile
-//               hold zeros (or, in the workspaces, finite values that only ever meet other pad columns: every product here keeps
-//               columns apart, the aggregation over joints and the stores to the block output stop at v < V).
-//   LDS         f2's tiling needs 204 KB (gcn, Cin = 256) and 189 KB (tcn, l8).  Here f2v_gcn stages K in chunks of 128 rows
-//               (153 KB with the three E runs of 22 KB) and f2v_tcn runs the convolutional residual and the temporal taps one after the
-//               other through ONE region (152 KB at Cin = 256).  The host computes every request and refuses above 160 KB.
-//
-// Arithmetic: v_mfma_f32_16x16x4_f32 (exact fp32), the K blocks of a product dealt round-robin to the waves, the partial tiles
-// summed through LDS in a fixed order: two runs are bit-equal.  Templated on V; instantiated for every V of FV_JOINTS (the host
-// half at the end of the file: 17 = COCO / YOLO-pose, 18 = OpenPose, 25 = NTU-RGB+D), S = 3.
-#include "common.h"
+// skeletons whose joint count is NOT a multiple of four -- NTU-RGB+D's V = 25, COCO's 17, OpenPose's 18 -- with V a TEMPLATE
+// PARAMETER.  The stage bodies are f2x_body.h's (its header has the layout: frames padded to VP floats, whole MFMA tiles, K in
+// chunks), shared with f2g.hip; this file holds the compile-time geometry FvGeo<V>, under which every geometry value of a
+// body is a constant, the kernels -- plain and grouped -- instantiated for every V of FV_JOINTS (17 = COCO / YOLO-pose,
+// 18 = OpenPose, 25 = NTU-RGB+D), S = 3, and their launches.
+#include "f2x_body.h"
 
 namespace {
 
-constexpr int FV_NT = 256, FV_BT = 4, FV_G = 4, FV_KC = 128, FV_HF = 15, FV_PX = 36, FV_CT = 8;
-
-template <int V> struct FvGeo {
+template <int V_> struct FvGeo {
+    static constexpr bool STATIC_V = true;
+    static constexpr int V = V_;
     static constexpr int VP = (V + 3) & ~3;            // floats per frame in LDS and in the family's own buffers
     static constexpr int QF = VP / 4;                  // 16-byte pieces per frame
-    static constexpr int NC = FV_BT * VP;              // columns of a tile
+    static constexpr int NC = F2_BT * VP;              // columns of a tile
     static constexpr int NCT = NC / 16;                // MFMA column tiles
     static constexpr int PB = NC + 4;                  // tile pitch: the four k rows of a fragment read sit 16 banks apart
     static constexpr int EC = V * VP;                  // floats of one channel of E: rows u of VP
     static constexpr int ECT = (EC + 15) / 16;         // column tiles of the E product
     static constexpr int PD = ECT * 16 + 4;            // D pitch
-    static constexpr int PH = FV_HF * VP + 4;          // halo tile pitch
-    static constexpr int EPC = (FV_CT * EC + 255) / 256;   // 1 KB DMA pieces of one subset's E run
+    static constexpr int PH = F2_HF * VP + 4;          // halo tile pitch
+    static constexpr int EPC = (F2_CT * EC + 255) / 256;   // 1 KB DMA pieces of one subset's E run
     static constexpr int ES = EPC * 256;
+    static constexpr int KC = F2_KC;                   // K rows of a staged chunk of the gcn stage
+    static constexpr int NIT = (ECT + 3) / 4;          // E column tiles per wave
+    static constexpr int NB = (64 * V + F2_NT - 1) / F2_NT;   // pq elements per thread at R = 32
     static_assert(NC % 16 == 0 && V <= 32 && V % 4 != 0, "geometry: whole MFMA tiles, xbar in two tiles, unaligned rows");
     static_assert((4 * PB) % 64 == 16 && (4 * PD) % 64 == 16, "conflict-free pitches");
-    static_assert((EC * 4) % 16 == 0 && FV_CT * EC >= 256, "E runs are 16-byte aligned");
+    static_assert((EC * 4) % 16 == 0 && F2_CT * EC >= 256, "E runs are 16-byte aligned");
 };
 
-__device__ __forceinline__ void fv_load_a(const float* arow, int K, int k0, int kq, bool vec, float (&a)[4]) {
-    const int k = k0 + 4 * kq;
-    if (vec) {
-        const float4 t = arow ? *reinterpret_cast<const float4*>(arow + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        a[0] = t.x; a[1] = t.y; a[2] = t.z; a[3] = t.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a[i] = (arow && k + i < K) ? arow[k + i] : 0.f;
-    }
+template <int V> __global__ __launch_bounds__(F2_NT) void f2v_e_kernel(const F2GcnArgs a) { f2x_e_body(FvGeo<V>(), a); }
+template <int V> __global__ __launch_bounds__(F2_NT) void f2v_e_grouped_kernel(const F2GcnArgs a, int npg) {
+    f2x_e_body(FvGeo<V>(), f2_group(a, blockIdx.y / npg, V * V));
 }
-
-// blocks kb, kb + kbstep, ... (< kbend) of a row of A
-__device__ __forceinline__ void fv_load_group(const float* arow, int K, bool vec, int kb, int kbend, int kbstep, int kq, float (&dst)[FV_G][4]) {
-#pragma unroll
-    for (int g = 0; g < FV_G; ++g) {
-        const int b = kb + g * kbstep;
-        if (b < kbend) fv_load_a(arow, K, b * 16, kq, vec, dst[g]);
-        else { dst[g][0] = dst[g][1] = dst[g][2] = dst[g][3] = 0.f; }
-    }
+template <int V> __global__ __launch_bounds__(F2_NT) void f2v_gcn_kernel(const F2GcnArgs a) { f2x_gcn_body(FvGeo<V>(), a); }
+template <int V> __global__ __launch_bounds__(F2_NT) void f2v_gcn_grouped_kernel(const F2GcnArgs a, int npg) {
+    f2x_gcn_body(FvGeo<V>(), f2_group(a, blockIdx.y / npg, V * V));
 }
-
-// acc[ct] += A[16 rows][16-k blocks kb, kb + kbstep, ... < kbend] * B; this lane's B value for tile ct at row k is bf(k, ct).
-// A fragments travel four blocks at a time, one group ahead (f2.hip).
-template <int NCT, class BF>
-__device__ __forceinline__ void fv_gemm16(f32x4 (&acc)[NCT], const float* arow, int K, bool vec, int kb, int kbend, int kbstep, int kq, BF bf) {
-    constexpr int G = FV_G;
-    float a[G][4], an[G][4];
-    fv_load_group(arow, K, vec, kb, kbend, kbstep, kq, a);
-    for (; kb < kbend; kb += G * kbstep) {
-        fv_load_group(arow, K, vec, kb + G * kbstep, kbend, kbstep, kq, an);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const int b = kb + g * kbstep;
-            if (b < kbend) {                                       // wave-uniform
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int k = b * 16 + 4 * kq + i;
-#pragma unroll
-                    for (int ct = 0; ct < NCT; ++ct) acc[ct] = mfma16(a[g][i], bf(k, ct), acc[ct]);
-                }
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[g][i] = an[g][i];
-    }
+template <int V> __global__ __launch_bounds__(F2_NT) void f2v_gemm_kernel(const F2GemmArgs a) { f2x_gemm_body(FvGeo<V>(), a); }
+template <int V> __global__ __launch_bounds__(F2_NT) void f2v_gemm_grouped_kernel(const F2GemmArgs a, int npg) {
+    f2x_gemm_body(FvGeo<V>(), f2_group(a, blockIdx.y / npg));
 }
-
-// Rows [0, rows) of an LDS tile [rows][PB] <- rows [0, K) of an activation, frames tl*fstep (tl < bt); everything else zero.
-// PADDED: the source has frames of VP floats (the family's own buffers: aligned pieces, pad columns copied as they are).
-// Otherwise frames of V floats from a dword-aligned address: the last piece of a frame keeps its first V - 4 (QF - 1) lanes.
-template <int V, bool PADDED>
-__device__ __forceinline__ void fv_stage(float* Bs, const float* src, long long rs, int K, int rows, int bt, int fstep, int tid) {
-    using G = FvGeo<V>;
-    constexpr int U = 8, QT = FV_BT * G::QF, FP = PADDED ? G::VP : V, LAST = V - 4 * (G::QF - 1);
-    for (int e0 = tid; e0 < rows * QT; e0 += U * FV_NT) {
-        float4 t[U];
-#pragma unroll
-        for (int i = 0; i < U; ++i) {
-            const int e = e0 + i * FV_NT;
-            const int k = e / QT, r = e - k * QT;
-            const int tl = r / G::QF, q = r - tl * G::QF;
-            t[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < rows * QT && k < K && tl < bt) {
-                t[i] = *reinterpret_cast<const float4*>(src + k * rs + (long long)tl * fstep * FP + 4 * q);
-                if (!PADDED && q == G::QF - 1) {                   // lanes past the frame: the next frame or the slack behind the tensor
-                    if (LAST < 2) t[i].y = 0.f;
-                    if (LAST < 3) t[i].z = 0.f;
-                    t[i].w = 0.f;
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < U; ++i) {
-            const int e = e0 + i * FV_NT;
-            const int k = e / QT, r = e - k * QT;
-            if (e < rows * QT) *reinterpret_cast<float4*>(Bs + k * G::PB + 4 * r) = t[i];
-        }
-    }
+template <int V> __global__ __launch_bounds__(F2_NT) void f2v_tcn_kernel(const F2TcnArgs a) { f2x_tcn_body(FvGeo<V>(), a, 0); }
+template <int V> __global__ __launch_bounds__(F2_NT) void f2v_tcn_grouped_kernel(const F2TcnArgs a, int npg) {
+    f2x_tcn_body(FvGeo<V>(), a, blockIdx.y / npg);
 }
-
-// ---------------------------------------------------------------------------------------------------------------------
-struct FvGcnArgs {
-    int N, Cin, Cout, T, S, R, res_mode;
-    const float *x, *w12, *b12, *w4, *b4, *A, *alpha, *w3, *b3, *sy, *ty, *wd, *bd, *xpart;
-    float *E, *sum, *diff;
-    int vec12, vec4, vec3, vecd;
-    int ntp;                             // f2v_e: frame phases of the xbar sum (4, or 2 where 4 partial tiles do not fit LDS)
-};
-
-// Grouped launches (include/tamgcn.h, "grouped"): samples [g*npg, (g+1)*npg) use the g-th of the parameter arrays that follow
-// one another densely behind group 0's.  g comes from blockIdx.y alone: the offset bases stay scalar.
-template <int V>
-__device__ __forceinline__ FvGcnArgs fv_group(FvGcnArgs a, int g) {
-    const long long SC = (long long)a.S * a.Cout;
-    a.w12 += g * (long long)a.S * 2 * a.R * a.Cin; a.b12 += g * a.S * 2 * a.R;
-    a.w4 += g * SC * a.R; a.b4 += g * SC;
-    a.A += g * a.S * V * V; a.alpha += g;
-    a.w3 += g * SC * a.Cin; a.b3 += g * SC;
-    a.sy += g * a.Cout; a.ty += g * a.Cout;
-    if (a.res_mode == 2) { a.wd += (long long)g * a.Cout * a.Cin; a.bd += g * a.Cout; }
-    return a;
-}
-
-// ---- E for 16 channels of one (sample, subset): E[c][u][v] at [c][u * VP + v], pad columns zero
-template <int V>
-__device__ __forceinline__ void f2v_e_body(const FvGcnArgs& a) {
-    using G = FvGeo<V>;
-    constexpr int NT = FV_NT, PX = FV_PX, PD = G::PD, VP = G::VP, QF = G::QF, EC = G::EC, ECT = G::ECT;
-    constexpr int NB = (64 * V + NT - 1) / NT, NIT = (ECT + 3) / 4;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int Kp = (a.Cin + 15) & ~15, R2 = 2 * a.R, R2p = R2 < 16 ? 16 : R2, Rp = (a.R + 15) & ~15;
-    float* XB = smem;                    // [Kp][PX]   xbar, columns >= V zero
-    float* PQ = XB + Kp * PX;            // [R2p][PX]  p rows 0..R-1, q rows R..2R-1
-    float* Pp = PQ + R2p * PX;           // [64][PX]   partial pq tiles
-    float* Ds = Pp + 64 * PX;            // [Rp][PD]   D; before that: [ntp][Kp][VP] partial frame sums
-    const int nct = a.Cout / 16;
-    const int s = blockIdx.x / nct, c0 = (blockIdx.x - s * nct) * 16, n = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kq = lane >> 4;
-    const long long TV = (long long)a.T * V;
-    const int NTP = a.ntp;
-    // pq product: (row tiles x K parts) over the waves; the row tiles round UP, a wave past the K parts multiplies zeros (f2.hip)
-    const int nrt = (R2p + 15) / 16, nparts = 4 / nrt;
-    const int prt = wave % nrt, ppart = wave / nrt;
-    const float* a12 = ppart < nparts && prt * 16 + j < R2 ? a.w12 + ((long long)s * R2 + prt * 16 + j) * a.Cin : nullptr;
-    float b12r[NB];
-#pragma unroll
-    for (int i = 0; i < NB; ++i) b12r[i] = tid + i * NT < R2 * V ? a.b12[s * R2 + (tid + i * NT) / V] : 0.f;
-    const float alpha = a.alpha[0];
-    float aw[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, b4r[4], Avr[NIT];
-    {
-        const float* arow = a.w4 + ((long long)s * a.Cout + c0 + j) * a.R;
-        fv_load_a(arow, a.R, 0, kq, a.vec4 != 0, aw[0]);
-        if (a.R > 16) fv_load_a(arow, a.R, 16, kq, a.vec4 != 0, aw[1]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) b4r[r] = a.b4[s * a.Cout + c0 + kq * 4 + r];
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-            const int col = (wave + 4 * i) * 16 + j, u = col / VP, v = col - u * VP;
-            Avr[i] = (col < EC && v < V) ? a.A[s * V * V + u * V + v] : 0.f;
-        }
-    }
-    // 1. xbar: from the producer's per-tile frame sums ([N][tiles][Cin][VP]) when it left them, else from x.  Fixed order.
-    {
-        float* XP = Ds;
-        const float inv = 1.f / (float)a.T;
-        if (a.xpart) {
-            const int ntt = (a.T + FV_BT - 1) / FV_BT, tpg = (ntt + NTP - 1) / NTP;
-            const float* xp = a.xpart + (long long)n * ntt * a.Cin * VP;
-            const int cnt = NTP * a.Cin * QF;
-            for (int e0 = tid; e0 < cnt; e0 += 8 * NT) {
-                float4 acc[8];
-                int off[8], g8[8];
-#pragma unroll
-                for (int p = 0; p < 8; ++p) {
-                    const int e = e0 + p * NT;
-                    const int g = e / (a.Cin * QF), rem = e - g * a.Cin * QF;
-                    const int ci = rem / QF, v4 = (rem - ci * QF) * 4;
-                    acc[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    off[p] = ci * VP + v4;
-                    g8[p] = e < cnt ? g : NTP;                      // NTP * tpg >= ntt: an out-of-range pair never loads
-                }
-                for (int i = 0; i < tpg; ++i) {
-                    float4 q[8];
-#pragma unroll
-                    for (int p = 0; p < 8; ++p) {
-                        const int tile = g8[p] * tpg + i;
-                        q[p] = tile < ntt ? *reinterpret_cast<const float4*>(xp + (long long)tile * a.Cin * VP + off[p]) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
-#pragma unroll
-                    for (int p = 0; p < 8; ++p) { acc[p].x += q[p].x; acc[p].y += q[p].y; acc[p].z += q[p].z; acc[p].w += q[p].w; }
-                }
-#pragma unroll
-                for (int p = 0; p < 8; ++p) {
-                    const int e = e0 + p * NT;
-                    if (e < cnt) *reinterpret_cast<float4*>(XP + (g8[p] * Kp) * VP + off[p]) = acc[p];
-                }
-            }
-        } else {                                                   // rows of V floats: element loads, four frame phases, frame order
-            const float* xb = a.x + (long long)n * a.Cin * TV;
-            for (int e = tid; e < NTP * a.Cin * VP; e += NT) {
-                const int tp = e / (a.Cin * VP), rem = e - tp * a.Cin * VP;
-                const int ci = rem / VP, v = rem - ci * VP;
-                float acc = 0.f;
-                if (v < V) {
-                    const float* p = xb + ci * TV + v;
-                    for (int t = tp; t < a.T; t += 8 * NTP) {
-                        float q[8];
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) q[i] = t + i * NTP < a.T ? p[(long long)(t + i * NTP) * V] : 0.f;
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) acc += q[i];
-                    }
-                }
-                XP[(tp * Kp + ci) * VP + v] = acc;
-            }
-        }
-        __syncthreads();
-        for (int e = tid; e < Kp * (PX / 4); e += NT) {
-            const int ci = e / (PX / 4), v4 = (e - ci * (PX / 4)) * 4;
-            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ci < a.Cin && v4 < V) {
-                for (int tp = 0; tp < NTP; ++tp) {
-                    const float4 q = *reinterpret_cast<const float4*>(XP + (tp * Kp + ci) * VP + v4);
-                    o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w;
-                }
-                o.x *= inv; o.y *= inv; o.z *= inv; o.w *= inv;
-                if (v4 + 1 >= V) o.y = 0.f;                        // pad joints of a caller's xpart are not trusted
-                if (v4 + 2 >= V) o.z = 0.f;
-                if (v4 + 3 >= V) o.w = 0.f;
-            }
-            *reinterpret_cast<float4*>(XB + ci * PX + v4) = o;
-        }
-        __syncthreads();
-    }
-    // 2. p, q = W12_s xbar + b12_s: (2R x Cin) x (Cin x V)
-    {
-        f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-        fv_gemm16<2>(acc, a12, a.Cin, a.vec12 != 0, ppart, Kp >> 4, nparts, kq, [&](int k, int ct) { return XB[k * PX + ct * 16 + j]; });
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Pp[((ppart * nrt + prt) * 16 + kq * 4 + r) * PX + ct * 16 + j] = acc[ct][r];
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            const int e = tid + i * NT;
-            if (e < R2 * V) {
-                const int row2 = e / V, v = e - row2 * V;
-                const int rt2 = row2 >> 4, rr = row2 & 15;
-                float t = b12r[i];
-                for (int p = 0; p < nparts; ++p) t += Pp[((p * nrt + rt2) * 16 + rr) * PX + v];
-                PQ[row2 * PX + v] = t;
-            }
-        }
-        __syncthreads();
-    }
-    // 3. D[r][u*VP + v] = tanh(p[r][u] - q[r][v]); rows R..Rp, pad joints and the columns up to the last tile's end zero
-    for (int e = tid; e < Rp * ECT * 16; e += NT) {
-        const int r = e / (ECT * 16), uv = e - r * (ECT * 16);
-        const int u = uv / VP, v = uv - u * VP;
-        Ds[r * PD + uv] = (r < a.R && u < V && v < V) ? fast_tanh(PQ[r * PX + u] - PQ[(a.R + r) * PX + v]) : 0.f;
-    }
-    __syncthreads();
-    // 4. E tile = alpha (W4 D + b4) + A: 16 channels x EC, column tiles over the four waves, K = R <= 32
-    {
-        float* Eg = a.E + (((long long)n * a.S + s) * a.Cout + c0) * EC;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int ct = wave + 4 * it;
-            if (ct < ECT) {
-                const int col = ct * 16 + j;
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc = mfma16(aw[0][i], Ds[(4 * kq + i) * PD + col], acc);
-                if (a.R > 16) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc = mfma16(aw[1][i], Ds[(16 + 4 * kq + i) * PD + col], acc);
-                }
-                const bool real = col - (col / VP) * VP < V;
-                if (col < EC) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) Eg[(long long)(kq * 4 + r) * EC + col] = real ? alpha * (acc[r] + b4r[r]) + Avr[it] : 0.f;
-                }
-            }
-        }
-    }
-}
-
-template <int V> __global__ __launch_bounds__(FV_NT) void f2v_e_kernel(const FvGcnArgs a) { f2v_e_body<V>(a); }
-template <int V> __global__ __launch_bounds__(FV_NT) void f2v_e_grouped_kernel(const FvGcnArgs a, int npg) { f2v_e_body<V>(fv_group<V>(a, blockIdx.y / npg)); }
-
-// ---- x3 GEMM + aggregation + BatchNorm + residual for 8 channels x 4 frames; K staged in chunks of FV_KC rows
-template <int V>
-__device__ __forceinline__ void f2v_gcn_body(const FvGcnArgs& a) {
-    using G = FvGeo<V>;
-    constexpr int PB = G::PB, CT = FV_CT, ES = G::ES, EC = G::EC, VP = G::VP, NCT = G::NCT, QF = G::QF;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int Kp = (a.Cin + 15) & ~15, Kc = Kp < FV_KC ? Kp : FV_KC;
-    float* Xs = smem;                    // [Kc][PB]      one K chunk of the x tile
-    float* X3 = Xs + Kc * PB;            // [2][32][PB]   partial products: rows s*8 + c (s < 3), 24 + c = down(x)
-    float* Es = X3 + 2 * 32 * PB;        // [3][ES]       E_s[c][u][VP]
-    const int nct = a.Cout / CT;
-    const int ctile = blockIdx.x % nct, tt = blockIdx.x / nct, n = blockIdx.y;
-    const int c0 = ctile * CT, t0 = tt * FV_BT, bt = min(FV_BT, a.T - t0);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kq = lane >> 4;
-    const long long TV = (long long)a.T * V, TVP = (long long)a.T * VP;
-    // E runs travel by LDS-DMA under the staging and the GEMM (the barriers below drain them)
-    for (int p = wave; p < 3 * G::EPC; p += 4) {
-        const int s = p / G::EPC, q = p - s * G::EPC;
-        int f = q * 256 + lane * 4;
-        if (f > CT * EC - 4) f = CT * EC - 4;                     // lanes past the run re-read its last slot into the padding
-        const float* g = a.E + (((long long)n * a.S + s) * a.Cout + c0) * EC + f;
-        __builtin_amdgcn_global_load_lds((tg_gptr)g, (tg_lptr)(Es + s * ES + q * 256), 16, 0, 0);
-    }
-    const int rt = wave & 1, kh = wave >> 1;
-    const float* arow;
-    bool vec;
-    {
-        const int row = rt * 16 + j, sidx = row >> 3, c = row & 7;
-        arow = sidx < 3 ? a.w3 + ((long long)sidx * a.Cout + c0 + c) * a.Cin
-                        : (a.res_mode == 2 ? a.wd + (long long)(c0 + c) * a.Cin : nullptr);
-        vec = sidx < 3 ? a.vec3 != 0 : a.vecd != 0;
-    }
-    {
-        f32x4 acc[NCT];
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < Kp; k0 += FV_KC) {
-            const int rows = min(FV_KC, Kp - k0);
-            if (k0) __syncthreads();                               // the previous chunk has been consumed
-            fv_stage<V, false>(Xs, a.x + ((long long)n * a.Cin + k0) * TV + (long long)t0 * V, TV, a.Cin - k0, rows, bt, 1, tid);
-            __syncthreads();
-            fv_gemm16<NCT>(acc, arow, a.Cin, vec, (k0 >> 4) + kh, (k0 + rows) >> 4, 2, kq,
-                           [&](int k, int ct) { return Xs[(k - k0) * PB + ct * 16 + j]; });
-        }
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) X3[((kh * 32) + rt * 16 + kq * 4 + r) * PB + ct * 16 + j] = acc[ct][r];
-    }
-    __syncthreads();
-    // aggregation: thread = (channel c, frame t, joint group ug): u = ug, ug + 8, ...
-    {
-        const int c = tid >> 5, t = (tid >> 3) & 3, ug = tid & 7;
-        float x3v[3 * VP];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            const float b = a.b3[s * a.Cout + c0 + c];
-#pragma unroll
-            for (int v4 = 0; v4 < VP; v4 += 4) {
-                const f32x4 p0 = *reinterpret_cast<const f32x4*>(X3 + (s * 8 + c) * PB + t * VP + v4);
-                const f32x4 p1 = *reinterpret_cast<const f32x4*>(X3 + (32 + s * 8 + c) * PB + t * VP + v4);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) x3v[s * VP + v4 + i] = p0[i] + p1[i] + b;
-            }
-        }
-        const float sy = a.sy[c0 + c], ty = a.ty[c0 + c];
-        const float bd = a.res_mode == 2 ? a.bd[c0 + c] : 0.f;
-        if (t < bt) {
-            const long long o0 = ((long long)n * a.Cout + c0 + c) * TVP + (long long)(t0 + t) * VP;
-            for (int u = ug; u < V; u += 8) {
-                float z = 0.f;
-#pragma unroll
-                for (int s = 0; s < 3; ++s) {
-                    const float* er = Es + s * ES + c * EC + u * VP;
-#pragma unroll
-                    for (int v4 = 0; v4 < VP; v4 += 4) {
-                        const f32x4 e = *reinterpret_cast<const f32x4*>(er + v4);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            if (v4 + i < V) z = fmaf(e[i], x3v[s * VP + v4 + i], z);     // (compile-time: the pad joints take no part)
-                    }
-                }
-                const float y = fmaf(sy, z, ty);
-                float res = 0.f;
-                const int col = t * VP + u;
-                if (a.res_mode == 1) res = a.x[((long long)n * a.Cin + c0 + c) * TV + (long long)(t0 + t) * V + u];
-                else if (a.res_mode == 2) res = X3[(24 + c) * PB + col] + X3[(32 + 24 + c) * PB + col] + bd;
-                a.sum[o0 + u] = y + res;
-                a.diff[o0 + u] = res - y;
-            }
-            if (ug < VP - V) {                                     // pad joints of the workspaces: zeros
-                a.sum[o0 + V + ug] = 0.f;
-                a.diff[o0 + V + ug] = 0.f;
-            }
-        }
-    }
-    (void)QF;
-}
-
-template <int V> __global__ __launch_bounds__(FV_NT) void f2v_gcn_kernel(const FvGcnArgs a) { f2v_gcn_body<V>(a); }
-template <int V> __global__ __launch_bounds__(FV_NT) void f2v_gcn_grouped_kernel(const FvGcnArgs a, int npg) { f2v_gcn_body<V>(fv_group<V>(a, blockIdx.y / npg)); }
-
-// ---------------------------------------------------------------------------------------------------------------------
-// 16 rows x 4 frames of a pointwise product with the block's epilogues; x, add and out have frames of VP floats
-// ---------------------------------------------------------------------------------------------------------------------
-struct FvGemmArgs {
-    int N, K, M, T, mode, relu_rows, vec;
-    const float *x, *w, *b, *add;
-    float* out;
-};
-
-template <int V>
-__device__ __forceinline__ void f2v_gemm_body(const FvGemmArgs& a) {
-    using G = FvGeo<V>;
-    constexpr int NT = FV_NT, PB = G::PB, NCT = G::NCT, VP = G::VP, QT = FV_BT * G::QF;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int Kp = (a.K + 15) & ~15;
-    float* Bs = smem;                    // [Kp][PB]
-    float* Pp = Bs + Kp * PB;            // [4][16][PB]
-    const int nmt = a.M / 16;
-    const int mtile = blockIdx.x % nmt, tt = blockIdx.x / nmt, n = blockIdx.y;
-    const int m0 = mtile * 16, t0 = tt * FV_BT, bt = min(FV_BT, a.T - t0);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kq = lane >> 4;
-    const long long TVP = (long long)a.T * VP;
-    const float* arow = a.w + (long long)(m0 + j) * a.K;
-    fv_stage<V, true>(Bs, a.x + (long long)n * a.K * TVP + (long long)t0 * VP, TVP, a.K, Kp, bt, 1, tid);
-    __syncthreads();
-    {
-        f32x4 acc[NCT];
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        fv_gemm16<NCT>(acc, arow, a.K, a.vec != 0, wave, Kp >> 4, 4, kq, [&](int k, int ct) { return Bs[k * PB + ct * 16 + j]; });
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Pp[(wave * 16 + kq * 4 + r) * PB + ct * 16 + j] = acc[ct][r];
-    }
-    __syncthreads();
-    for (int e = tid; e < 16 * QT; e += NT) {
-        const int row = e / QT, c4 = (e - row * QT) * 4;
-        if (c4 >= bt * VP) continue;
-        f32x4 v = *reinterpret_cast<const f32x4*>(Pp + row * PB + c4);
-#pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            const f32x4 p = *reinterpret_cast<const f32x4*>(Pp + (w * 16 + row) * PB + c4);
-            v += p;
-        }
-        const float b = a.b[m0 + row];
-        const long long o = ((long long)n * a.M + m0 + row) * TVP + (long long)t0 * VP + c4;
-        float4 r;
-        if (a.mode == 0) {
-            const float4 ad = *reinterpret_cast<const float4*>(a.add + o);
-            r.x = fmaxf(ad.x + fast_tanh(v[0] + b), 0.f); r.y = fmaxf(ad.y + fast_tanh(v[1] + b), 0.f);
-            r.z = fmaxf(ad.z + fast_tanh(v[2] + b), 0.f); r.w = fmaxf(ad.w + fast_tanh(v[3] + b), 0.f);
-        } else {
-            const float lo = (m0 + row < a.relu_rows) ? 0.f : -__builtin_inff();
-            r.x = fmaxf(v[0] + b, lo); r.y = fmaxf(v[1] + b, lo); r.z = fmaxf(v[2] + b, lo); r.w = fmaxf(v[3] + b, lo);
-        }
-        *reinterpret_cast<float4*>(a.out + o) = r;
-    }
-}
-
-template <int V> __global__ __launch_bounds__(FV_NT) void f2v_gemm_kernel(const FvGemmArgs a) { f2v_gemm_body<V>(a); }
-template <int V> __global__ __launch_bounds__(FV_NT) void f2v_gemm_grouped_kernel(const FvGemmArgs a, int npg) {
-    FvGemmArgs b = a;
-    const int g = blockIdx.y / npg;
-    b.w += (long long)g * a.M * a.K;
-    b.b += g * a.M;
-    f2v_gemm_body<V>(b);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// MS-TCN after its entry convs + the block's residual and ReLU: 16 output channels x 4 output frames.  h has frames of VP
-// floats; the block input x and the output are contiguous (N, C, T, V).
-// ---------------------------------------------------------------------------------------------------------------------
-struct FvTcnArgs {
-    int N, Cin, Cout, T, T2, stride, Cb, nb, ks, res_mode, vect, vecr;
-    int dil[4];
-    const float* h;
-    const float* wt[4]; const float* bt[4];
-    const float *sp, *tp;
-    const float *x, *wr, *br;
-    float* out;
-    float* xpart;                        // NULL | (N, ceil(T2 / 4), Cout, VP): sum over each tile's frames of out, pad joints zero
-};
-
-template <int V>
-__device__ __forceinline__ void f2v_tcn_body(const FvTcnArgs& a, const int g) {
-    using G = FvGeo<V>;
-    constexpr int NT = FV_NT, PB = G::PB, PH = G::PH, NCT = G::NCT, VP = G::VP, QF = G::QF, QT = FV_BT * G::QF;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int Kp = a.res_mode == 2 ? (a.Cin + 15) & ~15 : 0;
-    float* Pp = smem;                    // [4][16][PB]
-    float* Ot = Pp + 4 * 16 * PB;        // [16][PB]      finished tile
-    float* Us = Ot + 16 * PB;            // first [Kp][PB]: strided frames of the block input (convolutional residual), then
-                                         // [Cb][PH]: this branch's entry output with the temporal halo
-    const int nmt = a.Cout / 16;
-    const int mtile = blockIdx.x % nmt, tt = blockIdx.x / nmt, n = blockIdx.y;
-    const int c0 = mtile * 16, t0 = tt * FV_BT, bt = min(FV_BT, a.T2 - t0);
-    const int branch = c0 / a.Cb, cb0 = c0 - branch * a.Cb;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kq = lane >> 4;
-    const long long TV = (long long)a.T * V, TVP = (long long)a.T * VP, TV2 = (long long)a.T2 * V;
-    const bool temporal = branch < a.nb;
-    f32x4 acc[NCT];
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (a.res_mode == 2) {
-        fv_stage<V, false>(Us, a.x + (long long)n * a.Cin * TV + (long long)t0 * a.stride * V, TV, a.Cin, Kp, bt, a.stride, tid);
-        __syncthreads();
-        fv_gemm16<NCT>(acc, a.wr + (long long)g * a.Cout * a.Cin + (long long)(c0 + j) * a.Cin, a.Cin, a.vecr != 0, wave, Kp >> 4, 4, kq,
-                       [&](int k, int ct) { return Us[k * PB + ct * 16 + j]; });
-        if (temporal) __syncthreads();                             // (block-uniform) the region is staged again below
-    }
-    if (temporal) {
-        const int d = a.dil[branch];
-        const int pad = ((a.ks - 1) * d) / 2, tlo = t0 * a.stride - pad;
-        const int nfr = (FV_BT - 1) * a.stride + (a.ks - 1) * d + 1;
-        const float* hb = a.h + ((long long)n * a.Cout + branch * a.Cb) * TVP;
-        const int cnt = a.Cb * nfr * QF;
-        for (int e0 = tid; e0 < cnt; e0 += 8 * NT) {
-            float4 q[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int e = e0 + i * NT;
-                const int ci = e / (nfr * QF), rem = e - ci * nfr * QF;
-                const int f = rem / QF, v4 = (rem - f * QF) * 4;
-                const int t = tlo + f;
-                q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (e < cnt && t >= 0 && t < a.T) q[i] = *reinterpret_cast<const float4*>(hb + ci * TVP + (long long)t * VP + v4);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int e = e0 + i * NT;
-                const int ci = e / (nfr * QF), rem = e - ci * nfr * QF;
-                if (e < cnt) *reinterpret_cast<float4*>(Us + ci * PH + rem * 4) = q[i];
-            }
-        }
-        __syncthreads();
-        int boff[NCT];                                             // this lane's columns: (frame tl, joint v) of tile ct -> tap 0 inside a halo row
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-            const int col = ct * 16 + j, tl = col / VP, v = col - tl * VP;
-            boff[ct] = tl * a.stride * VP + v;
-        }
-        const int K = a.Cb * a.ks;
-        fv_gemm16<NCT>(acc, a.wt[branch] + (long long)g * a.Cb * K + (long long)(cb0 + j) * K, K, a.vect != 0, wave, (K + 15) >> 4, 4, kq, [&](int k, int ct) {
-            const int kk = k < K ? k : 0;                          // (the A element is zero there)
-            const int ci = kk / a.ks, tap = kk - ci * a.ks;
-            return Us[ci * PH + tap * d * VP + boff[ct]];
-        });
-    }
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Pp[(wave * 16 + kq * 4 + r) * PB + ct * 16 + j] = acc[ct][r];
-    __syncthreads();
-    const int Ch = (a.nb + 1) * a.Cb;
-    for (int e = tid; e < 16 * QT; e += NT) {
-        const int row = e / QT, c4 = (e - row * QT) * 4;
-        const int tl = c4 / VP, v = c4 - tl * VP;
-        if (tl >= bt) continue;
-        f32x4 sum = *reinterpret_cast<const f32x4*>(Pp + row * PB + c4);
-#pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            const f32x4 p = *reinterpret_cast<const f32x4*>(Pp + (w * 16 + row) * PB + c4);
-            sum += p;
-        }
-        const int c = c0 + row, cb = cb0 + row, tq = t0 + tl, ts = tq * a.stride;
-        f32x4 val;
-        if (temporal) {
-            const float b = a.bt[branch][g * a.Cb + cb];
-            val = (f32x4){b, b, b, b};
-        } else if (branch == a.nb) {                               // MaxPool2d((3,1), stride, pad 1) of the ReLU'd entry output, then its BatchNorm
-            const float* hp = a.h + ((long long)n * a.Cout + c) * TVP + v;
-            f32x4 m = *reinterpret_cast<const f32x4*>(hp + (long long)ts * VP);
-            if (ts - 1 >= 0) {
-                const f32x4 q = *reinterpret_cast<const f32x4*>(hp + (long long)(ts - 1) * VP);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) m[i] = fmaxf(m[i], q[i]);
-            }
-            if (ts + 1 < a.T) {
-                const f32x4 q = *reinterpret_cast<const f32x4*>(hp + (long long)(ts + 1) * VP);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) m[i] = fmaxf(m[i], q[i]);
-            }
-            const float sp = a.sp[g * a.Cb + cb], tp = a.tp[g * a.Cb + cb];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) val[i] = fmaf(sp, m[i], tp);
-        } else {                                                   // plain branch: computed with the entry convs (rows >= Ch of h)
-            val = *reinterpret_cast<const f32x4*>(a.h + ((long long)n * a.Cout + Ch + cb) * TVP + (long long)ts * VP + v);
-        }
-        val += sum;
-        if (a.res_mode == 1) {                                     // rows of V floats: elements, none past the frame
-            const float* xr = a.x + ((long long)n * a.Cin + c) * TV + (long long)tq * V + v;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (v + i < V) val[i] += xr[i];
-        } else if (a.res_mode == 2) {
-            const float b = a.br[g * a.Cout + c];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) val[i] += b;
-        }
-        float4 r = make_float4(fmaxf(val[0], 0.f), v + 1 < V ? fmaxf(val[1], 0.f) : 0.f, v + 2 < V ? fmaxf(val[2], 0.f) : 0.f,
-                               v + 3 < V ? fmaxf(val[3], 0.f) : 0.f);
-        *reinterpret_cast<float4*>(Ot + row * PB + c4) = r;
-    }
-    __syncthreads();
-    for (int e = tid; e < 16 * bt * V; e += NT) {                  // the block output: contiguous rows, element stores
-        const int row = e / (bt * V), rem = e - row * (bt * V);
-        const int tl = rem / V, v = rem - tl * V;
-        a.out[((long long)n * a.Cout + c0 + row) * TV2 + (long long)t0 * V + rem] = Ot[row * PB + tl * VP + v];
-    }
-    if (a.xpart && tid < 16 * QF) {
-        const int row = tid / QF, v4 = (tid - row * QF) * 4;
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int tl = 0; tl < bt; ++tl) {
-            const float4 q = *reinterpret_cast<const float4*>(Ot + row * PB + tl * VP + v4);
-            o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w;
-        }
-        const int ntt = (a.T2 + FV_BT - 1) / FV_BT;
-        *reinterpret_cast<float4*>(a.xpart + (((long long)n * ntt + tt) * a.Cout + c0 + row) * VP + v4) = o;
-    }
-}
-
-template <int V> __global__ __launch_bounds__(FV_NT) void f2v_tcn_kernel(const FvTcnArgs a) { f2v_tcn_body<V>(a, 0); }
-template <int V> __global__ __launch_bounds__(FV_NT) void f2v_tcn_grouped_kernel(const FvTcnArgs a, int npg) { f2v_tcn_body<V>(a, blockIdx.y / npg); }
 
 // ---- host -----------------------------------------------------------------------------------------------------------
 // The joint counts the family is instantiated for: THE list (tam_gcn_amd/f2v.py mirrors it as JOINTS).  Serving another
-// skeleton with V % 4 != 0 is one more X(..) here -- after reading FvGeo's asserts and fv_stage's LAST for that V.
+// skeleton with V % 4 != 0 is one more X(..) here -- after reading FvGeo's asserts and f2x_stage's `last` for that V.
 #define FV_JOINTS(X) X(17) X(18) X(25)
 
-constexpr int FV_V = 25;                               // the widest geometry of the list: what FV_LDS_MAX has to hold (asserted below)
-constexpr size_t FV_LDS_MAX = 160 * 1024;
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+constexpr int FV_V = 25;                               // the widest geometry of the list: what F2_LDS_MAX has to hold (asserted below)
 
 #define FV_JOINT_TXT(v) " V = " #v ","
 #define FV_BUILT_FOR "this family is built for" FV_JOINTS(FV_JOINT_TXT) " S = 3"
 
 // Everything of the host half that depends on the geometry: the LDS requests and the launches, per served V.
+// groups == 0: the plain entry point; otherwise the grouped one.
 template <int V> struct FvHost {
 using GV = FvGeo<V>;
 
-static constexpr size_t fv_e_lds(int Cin, int R, int ntp) {
-    const int Kp = (Cin + 15) & ~15, R2p = 2 * R < 16 ? 16 : 2 * R, Rp = (R + 15) & ~15;
-    const size_t d = (size_t)Rp * GV::PD, xp = (size_t)ntp * Kp * GV::VP;
-    return sizeof(float) * ((size_t)Kp * FV_PX + (size_t)R2p * FV_PX + 64 * FV_PX + (d > xp ? d : xp));
-}
-static constexpr size_t fv_gcn_lds(int Cin) {
-    const int Kp = (Cin + 15) & ~15;
-    return sizeof(float) * ((size_t)(Kp < FV_KC ? Kp : FV_KC) * GV::PB + 2 * 32 * GV::PB + 3 * GV::ES);
-}
-static constexpr size_t fv_gemm_lds(int K) { return sizeof(float) * ((size_t)((K + 15) & ~15) * GV::PB + 4 * 16 * GV::PB); }
-static constexpr size_t fv_tcn_lds(int Cin, int Cb, int res_mode) {
-    const size_t xs = (size_t)(res_mode == 2 ? (Cin + 15) & ~15 : 0) * GV::PB, hs = (size_t)Cb * GV::PH;
-    return sizeof(float) * ((size_t)5 * 16 * GV::PB + (xs > hs ? xs : hs));
-}
+static constexpr size_t fv_e_lds(int Cin, int R, int ntp) { return f2_e_lds(Cin, R, ntp, GV::VP, GV::PD); }
+static constexpr size_t fv_gcn_lds(int Cin) { return f2_gcn_lds(Cin, GV::KC, GV::PB, GV::ES); }
+static constexpr size_t fv_gemm_lds(int K) { return f2_gemm_lds(K, GV::PB); }
+static constexpr size_t fv_tcn_lds(int Cin, int Cb, int res_mode) { return f2_tcn_lds(Cin, Cb, res_mode, GV::PB, GV::PH); }
 
-static int fv_fill(const tamgcn_f2_gcn_desc* d, FvGcnArgs* a, const char* who) {
-    TG_CHECK(d && d->x && d->w12 && d->b12 && d->w4 && d->b4 && d->A && d->alpha && d->w3 && d->b3 && d->sy && d->ty && d->E,
-             "%s: null pointer", who);
-    TG_CHECK(d->V == V && d->S == 3, "%s: V=%d S=%d (" FV_BUILT_FOR ")", who, d->V, d->S);
-    TG_CHECK(d->N > 0 && d->T > 0 && d->Cin > 0 && d->Cin <= 256 && d->Cout > 0 && d->Cout % 16 == 0,
-             "%s: bad shape N=%d T=%d Cin=%d Cout=%d (Cin <= 256, Cout %% 16 == 0)", who, d->N, d->T, d->Cin, d->Cout);
-    TG_CHECK(d->R >= 1 && d->R <= 32, "%s: R=%d outside 1..32", who, d->R);
-    TG_CHECK(d->res_mode >= 0 && d->res_mode <= 2, "%s: res_mode=%d", who, d->res_mode);
-    TG_CHECK(d->res_mode != 1 || d->Cin == d->Cout, "%s: identity residual needs Cin == Cout", who);
-    TG_CHECK(d->res_mode != 2 || (d->wd && d->bd), "%s: convolutional residual without weights", who);
-    TG_CHECK(al4(d->x) && al16(d->E) && (!d->xpart || al16(d->xpart)), "%s: x must be 4-byte, E and xpart 16-byte aligned", who);
-    a->N = d->N; a->Cin = d->Cin; a->Cout = d->Cout; a->T = d->T; a->S = d->S; a->R = d->R; a->res_mode = d->res_mode;
-    a->x = d->x; a->w12 = d->w12; a->b12 = d->b12; a->w4 = d->w4; a->b4 = d->b4; a->A = d->A; a->alpha = d->alpha;
-    a->w3 = d->w3; a->b3 = d->b3; a->sy = d->sy; a->ty = d->ty; a->wd = d->wd; a->bd = d->bd;
-    a->E = d->E; a->sum = d->sum; a->diff = d->diff; a->xpart = d->xpart;
-    a->vec12 = d->Cin % 16 == 0 && al16(d->w12);
-    a->vec3 = d->Cin % 16 == 0 && al16(d->w3);
-    a->vecd = d->res_mode == 2 && d->Cin % 16 == 0 && al16(d->wd);
-    a->vec4 = d->R % 16 == 0 && al16(d->w4);
-    a->ntp = 4;
-    return 0;
-}
-
-// groups == 0: the plain entry point; otherwise the grouped one (common.h: tg_groups_ok, tg_group_stride_ok).
-static int fv_e_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
-    FvGcnArgs a;
-    if (fv_fill(d, &a, who)) return -1;
-    a.ntp = fv_e_lds(d->Cin, d->R, 4) <= FV_LDS_MAX ? 4 : 2;
-    const size_t lds = fv_e_lds(d->Cin, d->R, a.ntp);
-    TG_CHECK(lds <= FV_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
-    const dim3 grid(d->S * (d->Cout / 16), d->N);
+static int fv_e_launch(F2GcnArgs& a, int groups, void* stream, const char* who) {
+    a.ntp = fv_e_lds(a.Cin, a.R, 4) <= F2_LDS_MAX ? 4 : 2;
+    const size_t lds = fv_e_lds(a.Cin, a.R, a.ntp);
+    TG_CHECK(lds <= F2_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
+    if (f2_gcn_groups_ok(a, groups, who)) return -1;
+    const dim3 grid(a.S * (a.Cout / 16), a.N);
     if (groups) {
-        if (tg_groups_ok(d->N, groups, who) || tg_gcn_group_strides_ok(d, a.vec12, a.vec4, a.vec3, a.vecd, who)) return -1;
-        tg_launch_lds<f2v_e_grouped_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tg_launch_lds<f2v_e_grouped_kernel<V>>(F2_LDS_MAX, grid, dim3(F2_NT), lds, (hipStream_t)stream, a, a.N / groups);
         tamgcn_note_kernel("f2v_e_grouped_kernel");
     } else {
-        tg_launch_lds<f2v_e_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tg_launch_lds<f2v_e_kernel<V>>(F2_LDS_MAX, grid, dim3(F2_NT), lds, (hipStream_t)stream, a);
         tamgcn_note_kernel("f2v_e_kernel");
     }
     TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-static int fv_gcn_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
-    FvGcnArgs a;
-    if (fv_fill(d, &a, who)) return -1;
-    TG_CHECK(d->sum && d->diff && al16(d->sum) && al16(d->diff), "%s: null or misaligned output", who);
-    const size_t lds = fv_gcn_lds(d->Cin);
-    TG_CHECK(lds <= FV_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
-    const dim3 grid(ceil_div(d->T, FV_BT) * (d->Cout / FV_CT), d->N);
+static int fv_gcn_launch(F2GcnArgs& a, int groups, void* stream, const char* who) {
+    const size_t lds = fv_gcn_lds(a.Cin);
+    TG_CHECK(lds <= F2_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
+    if (f2_gcn_groups_ok(a, groups, who)) return -1;
+    const dim3 grid(ceil_div(a.T, F2_BT) * (a.Cout / F2_CT), a.N);
     if (groups) {
-        if (tg_groups_ok(d->N, groups, who) || tg_gcn_group_strides_ok(d, a.vec12, a.vec4, a.vec3, a.vecd, who)) return -1;
-        tg_launch_lds<f2v_gcn_grouped_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tg_launch_lds<f2v_gcn_grouped_kernel<V>>(F2_LDS_MAX, grid, dim3(F2_NT), lds, (hipStream_t)stream, a, a.N / groups);
         tamgcn_note_kernel("f2v_gcn_grouped_kernel");
     } else {
-        tg_launch_lds<f2v_gcn_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tg_launch_lds<f2v_gcn_kernel<V>>(F2_LDS_MAX, grid, dim3(F2_NT), lds, (hipStream_t)stream, a);
         tamgcn_note_kernel("f2v_gcn_kernel");
     }
     TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-static int fv_gemm_launch(const tamgcn_f2_gemm_desc* d, int groups, void* stream, const char* who) {
-    TG_CHECK(d && d->x && d->w && d->b && d->out, "%s: null pointer", who);
-    TG_CHECK(d->V == V, "%s: V=%d (" FV_BUILT_FOR ")", who, d->V);
-    TG_CHECK(d->N > 0 && d->T > 0 && d->K > 0 && d->K <= 256 && d->M > 0 && d->M % 16 == 0,
-             "%s: bad shape N=%d T=%d K=%d M=%d (K <= 256, M %% 16 == 0)", who, d->N, d->T, d->K, d->M);
-    TG_CHECK(d->mode == 0 || d->mode == 1, "%s: mode=%d", who, d->mode);
-    TG_CHECK(d->mode != 0 || d->add, "%s: mode 0 needs the addend", who);
-    TG_CHECK(al16(d->x) && al16(d->out) && (!d->add || al16(d->add)), "%s: activations must be 16-byte aligned", who);
-    FvGemmArgs a;
-    a.N = d->N; a.K = d->K; a.M = d->M; a.T = d->T; a.mode = d->mode; a.relu_rows = d->relu_rows;
-    a.vec = d->K % 16 == 0 && al16(d->w);
-    a.x = d->x; a.w = d->w; a.b = d->b; a.add = d->add; a.out = d->out;
-    const size_t lds = fv_gemm_lds(d->K);
-    TG_CHECK(lds <= FV_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
-    const dim3 grid(ceil_div(d->T, FV_BT) * (d->M / 16), d->N);
+static int fv_gemm_launch(F2GemmArgs& a, int groups, void* stream, const char* who) {
+    const size_t lds = fv_gemm_lds(a.K);
+    TG_CHECK(lds <= F2_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
+    if (f2_gemm_groups_ok(a, groups, who)) return -1;
+    const dim3 grid(ceil_div(a.T, F2_BT) * (a.M / 16), a.N);
     if (groups) {
-        if (tg_groups_ok(d->N, groups, who)) return -1;
-        if (tg_group_stride_ok(a.vec, (long long)d->M * d->K, who, "w")) return -1;
-        tg_launch_lds<f2v_gemm_grouped_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tg_launch_lds<f2v_gemm_grouped_kernel<V>>(F2_LDS_MAX, grid, dim3(F2_NT), lds, (hipStream_t)stream, a, a.N / groups);
         tamgcn_note_kernel("f2v_gemm_grouped_kernel");
     } else {
-        tg_launch_lds<f2v_gemm_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tg_launch_lds<f2v_gemm_kernel<V>>(F2_LDS_MAX, grid, dim3(F2_NT), lds, (hipStream_t)stream, a);
         tamgcn_note_kernel("f2v_gemm_kernel");
     }
     TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-static int fv_tcn_launch(const tamgcn_f2_tcn_desc* d, int groups, void* stream, const char* who) {
-    TG_CHECK(d && d->h && d->out && d->sp && d->tp, "%s: null pointer", who);
-    TG_CHECK(d->V == V, "%s: V=%d (" FV_BUILT_FOR ")", who, d->V);
-    TG_CHECK(d->N > 0 && d->T > 0 && d->Cout > 0 && d->Cout % 16 == 0 && d->stride >= 1 && d->stride <= 2,
-             "%s: bad shape N=%d T=%d Cout=%d stride=%d", who, d->N, d->T, d->Cout, d->stride);
-    TG_CHECK(d->nb >= 1 && d->nb <= 4 && d->Cb % 16 == 0 && d->Cb <= 64 && (d->nb + 2) * d->Cb == d->Cout,
-             "%s: nb=%d Cb=%d Cout=%d (Cb %% 16 == 0, Cb <= 64, (nb + 2) Cb == Cout)", who, d->nb, d->Cb, d->Cout);
-    TG_CHECK(d->ks >= 1 && d->ks % 2 == 1, "%s: kernel size %d", who, d->ks);
-    for (int b = 0; b < d->nb; ++b) {
-        TG_CHECK(d->wt[b] && d->bt[b] && d->dil[b] >= 1, "%s: branch %d: null weights or dilation %d", who, b, d->dil[b]);
-        TG_CHECK((FV_BT - 1) * d->stride + (d->ks - 1) * d->dil[b] + 1 <= FV_HF, "%s: branch %d: halo of k=%d dilation %d stride %d exceeds %d frames",
-                 who, b, d->ks, d->dil[b], d->stride, FV_HF);
-    }
-    TG_CHECK(d->res_mode >= 0 && d->res_mode <= 2, "%s: res_mode=%d", who, d->res_mode);
-    TG_CHECK(d->res_mode == 0 || d->x, "%s: residual without the block input", who);
-    TG_CHECK(d->res_mode != 1 || (d->Cin == d->Cout && d->stride == 1), "%s: identity residual needs Cin == Cout, stride 1", who);
-    TG_CHECK(d->res_mode != 2 || (d->wr && d->br && d->Cin > 0 && d->Cin <= 256), "%s: convolutional residual: weights / Cin=%d", who, d->Cin);
-    TG_CHECK(al16(d->h) && al4(d->out) && (!d->x || al4(d->x)) && (!d->xpart || al16(d->xpart)),
-             "%s: h and xpart must be 16-byte, x and out 4-byte aligned", who);
-    FvTcnArgs a;
-    a.N = d->N; a.Cin = d->Cin; a.Cout = d->Cout; a.T = d->T; a.stride = d->stride; a.T2 = (d->T - 1) / d->stride + 1;
-    a.Cb = d->Cb; a.nb = d->nb; a.ks = d->ks; a.res_mode = d->res_mode;
-    bool vt = (d->Cb * d->ks) % 16 == 0;
-    for (int b = 0; b < 4; ++b) {
-        a.dil[b] = b < d->nb ? d->dil[b] : 1;
-        a.wt[b] = b < d->nb ? d->wt[b] : nullptr;
-        a.bt[b] = b < d->nb ? d->bt[b] : nullptr;
-        if (b < d->nb) vt = vt && al16(d->wt[b]);
-    }
-    a.vect = vt;
-    a.vecr = d->res_mode == 2 && d->Cin % 16 == 0 && al16(d->wr);
-    a.h = d->h; a.sp = d->sp; a.tp = d->tp; a.x = d->x; a.wr = d->wr; a.br = d->br; a.out = d->out; a.xpart = d->xpart;
-    const size_t lds = fv_tcn_lds(d->Cin, d->Cb, d->res_mode);
-    TG_CHECK(lds <= FV_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
-    const dim3 grid(ceil_div(a.T2, FV_BT) * (d->Cout / 16), d->N);
+static int fv_tcn_launch(F2TcnArgs& a, int groups, void* stream, const char* who) {
+    const size_t lds = fv_tcn_lds(a.Cin, a.Cb, a.res_mode);
+    TG_CHECK(lds <= F2_LDS_MAX, "%s: %zu bytes of LDS", who, lds);
+    if (f2_tcn_groups_ok(a, groups, who)) return -1;
+    const dim3 grid(ceil_div(a.T2, F2_BT) * (a.Cout / 16), a.N);
     if (groups) {
-        if (tg_groups_ok(d->N, groups, who)) return -1;
-        if (tg_group_stride_ok(a.vect, (long long)d->Cb * d->Cb * d->ks, who, "wt")) return -1;
-        if (tg_group_stride_ok(a.vecr, (long long)d->Cout * d->Cin, who, "wr")) return -1;
-        tg_launch_lds<f2v_tcn_grouped_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a, d->N / groups);
+        tg_launch_lds<f2v_tcn_grouped_kernel<V>>(F2_LDS_MAX, grid, dim3(F2_NT), lds, (hipStream_t)stream, a, a.N / groups);
         tamgcn_note_kernel("f2v_tcn_grouped_kernel");
     } else {
-        tg_launch_lds<f2v_tcn_kernel<V>>(FV_LDS_MAX, grid, dim3(FV_NT), lds, (hipStream_t)stream, a);
+        tg_launch_lds<f2v_tcn_kernel<V>>(F2_LDS_MAX, grid, dim3(F2_NT), lds, (hipStream_t)stream, a);
         tamgcn_note_kernel("f2v_tcn_kernel");
     }
     TG_LAUNCH_CHECK(who);
@@ -817,18 +133,18 @@ static int fv_tcn_launch(const tamgcn_f2_tcn_desc* d, int groups, void* stream, 
 }
 };  // FvHost
 
-static_assert(FvHost<FV_V>::fv_e_lds(256, 32, 2) <= FV_LDS_MAX && FvHost<FV_V>::fv_gcn_lds(256) <= FV_LDS_MAX &&
-              FvHost<FV_V>::fv_gemm_lds(256) <= FV_LDS_MAX && FvHost<FV_V>::fv_tcn_lds(256, 64, 2) <= FV_LDS_MAX,
+static_assert(FvHost<FV_V>::fv_e_lds(256, 32, 2) <= F2_LDS_MAX && FvHost<FV_V>::fv_gcn_lds(256) <= F2_LDS_MAX &&
+              FvHost<FV_V>::fv_gemm_lds(256) <= F2_LDS_MAX && FvHost<FV_V>::fv_tcn_lds(256, 64, 2) <= F2_LDS_MAX,
               "the widest served geometry fits the LDS cap at the stock model's widest layers");
 
-// One row of launchers per served joint count; the entry points pick theirs by d->V.  Any other V is refused here, on the
-// host, before a pointer of the descriptor is looked at.
+// One row of launchers per served joint count; the entry points pick theirs by d->V.  Any other V is refused on the host
+// (f2_common.h: right after the null descriptor, before a pointer of the descriptor is looked at).
 struct FvRow {
     int V;
-    int (*e)(const tamgcn_f2_gcn_desc*, int, void*, const char*);
-    int (*gcn)(const tamgcn_f2_gcn_desc*, int, void*, const char*);
-    int (*gemm)(const tamgcn_f2_gemm_desc*, int, void*, const char*);
-    int (*tcn)(const tamgcn_f2_tcn_desc*, int, void*, const char*);
+    int (*e)(F2GcnArgs&, int, void*, const char*);
+    int (*gcn)(F2GcnArgs&, int, void*, const char*);
+    int (*gemm)(F2GemmArgs&, int, void*, const char*);
+    int (*tcn)(F2TcnArgs&, int, void*, const char*);
 };
 #define FV_ROW(v) {v, FvHost<v>::fv_e_launch, FvHost<v>::fv_gcn_launch, FvHost<v>::fv_gemm_launch, FvHost<v>::fv_tcn_launch},
 const FvRow FV_ROWS[] = {FV_JOINTS(FV_ROW)};
@@ -838,28 +154,24 @@ const FvRow* fv_row(int V) {
         if (r.V == V) return &r;
     return nullptr;
 }
+bool fv_served(int V) { return fv_row(V) != nullptr; }
+const F2Family FV_FAMILY = {fv_served, FV_BUILT_FOR, "null pointer", 4, F2_GCN_ALIGN4_TXT, F2_TCN_ALIGN4_TXT, false};
 
-template <class D> const FvRow* fv_pick(const D* d, const char* who) {
-    if (!d) { tamgcn_set_error("%s: null pointer", who); return nullptr; }
-    const FvRow* r = fv_row(d->V);
-    if (!r) tamgcn_set_error("%s: V=%d (" FV_BUILT_FOR ")", who, d->V);
-    return r;
-}
 int fv_e_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
-    const FvRow* r = fv_pick(d, who);
-    return r ? r->e(d, groups, stream, who) : -1;
+    F2GcnArgs a;
+    return f2_gcn_args(d, &a, FV_FAMILY, false, who) ? -1 : fv_row(d->V)->e(a, groups, stream, who);
 }
 int fv_gcn_launch(const tamgcn_f2_gcn_desc* d, int groups, void* stream, const char* who) {
-    const FvRow* r = fv_pick(d, who);
-    return r ? r->gcn(d, groups, stream, who) : -1;
+    F2GcnArgs a;
+    return f2_gcn_args(d, &a, FV_FAMILY, true, who) ? -1 : fv_row(d->V)->gcn(a, groups, stream, who);
 }
 int fv_gemm_launch(const tamgcn_f2_gemm_desc* d, int groups, void* stream, const char* who) {
-    const FvRow* r = fv_pick(d, who);
-    return r ? r->gemm(d, groups, stream, who) : -1;
+    F2GemmArgs a;
+    return f2_gemm_args(d, &a, FV_FAMILY, who) ? -1 : fv_row(d->V)->gemm(a, groups, stream, who);
 }
 int fv_tcn_launch(const tamgcn_f2_tcn_desc* d, int groups, void* stream, const char* who) {
-    const FvRow* r = fv_pick(d, who);
-    return r ? r->tcn(d, groups, stream, who) : -1;
+    F2TcnArgs a;
+    return f2_tcn_args(d, &a, FV_FAMILY, who) ? -1 : fv_row(d->V)->tcn(a, groups, stream, who);
 }
 
 }  // namespace
@@ -869,19 +181,15 @@ extern "C" int tamgcn_f2v_gcn(const tamgcn_f2_gcn_desc* d, void* stream) { retur
 extern "C" int tamgcn_f2v_gemm(const tamgcn_f2_gemm_desc* d, void* stream) { return fv_gemm_launch(d, 0, stream, "tamgcn_f2v_gemm"); }
 extern "C" int tamgcn_f2v_tcn(const tamgcn_f2_tcn_desc* d, void* stream) { return fv_tcn_launch(d, 0, stream, "tamgcn_f2v_tcn"); }
 
-static int fv_groups_arg(int groups, const char* who) {
-    TG_CHECK(groups >= 1, "%s: groups=%d", who, groups);
-    return 0;
-}
 extern "C" int tamgcn_f2v_e_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream) {
-    return fv_groups_arg(groups, "tamgcn_f2v_e_grouped") ? -1 : fv_e_launch(d, groups, stream, "tamgcn_f2v_e_grouped");
+    return f2_groups_arg(groups, "tamgcn_f2v_e_grouped") ? -1 : fv_e_launch(d, groups, stream, "tamgcn_f2v_e_grouped");
 }
 extern "C" int tamgcn_f2v_gcn_grouped(const tamgcn_f2_gcn_desc* d, int groups, void* stream) {
-    return fv_groups_arg(groups, "tamgcn_f2v_gcn_grouped") ? -1 : fv_gcn_launch(d, groups, stream, "tamgcn_f2v_gcn_grouped");
+    return f2_groups_arg(groups, "tamgcn_f2v_gcn_grouped") ? -1 : fv_gcn_launch(d, groups, stream, "tamgcn_f2v_gcn_grouped");
 }
 extern "C" int tamgcn_f2v_gemm_grouped(const tamgcn_f2_gemm_desc* d, int groups, void* stream) {
-    return fv_groups_arg(groups, "tamgcn_f2v_gemm_grouped") ? -1 : fv_gemm_launch(d, groups, stream, "tamgcn_f2v_gemm_grouped");
+    return f2_groups_arg(groups, "tamgcn_f2v_gemm_grouped") ? -1 : fv_gemm_launch(d, groups, stream, "tamgcn_f2v_gemm_grouped");
 }
 extern "C" int tamgcn_f2v_tcn_grouped(const tamgcn_f2_tcn_desc* d, int groups, void* stream) {
-    return fv_groups_arg(groups, "tamgcn_f2v_tcn_grouped") ? -1 : fv_tcn_launch(d, groups, stream, "tamgcn_f2v_tcn_grouped");
+    return f2_groups_arg(groups, "tamgcn_f2v_tcn_grouped") ? -1 : fv_tcn_launch(d, groups, stream, "tamgcn_f2v_tcn_grouped");
 }

@@ -42,12 +42,12 @@ F64 = torch.float64
 NAN = float('nan')
 S = 3
 
-# ---- the kernel geometry this file mirrors (csrc/f2.hip, csrc/f2v.hip; tests/test_f2_ref_cpu.py reads the source text) -----
-BT = 4                    # frames of a tile (F2_BT, FV_BT)
-HF = 15                   # frames of a halo tile (F2_HF, FV_HF)
-KC = 128                  # K rows of a staged chunk of f2v_gcn (FV_KC)
+# ---- the kernel geometry this file mirrors (csrc/f2_common.h, f2.hip, f2v.hip; tests/test_f2_ref_cpu.py reads the source text)
+BT = 4                    # frames of a tile (F2_BT)
+HF = 15                   # frames of a halo tile (F2_HF)
+KC = 128                  # K rows of a staged chunk of f2v_gcn (F2_KC)
 VP25 = 28                 # floats of a frame in the f2v family's own buffers
-PX = 36                   # xbar / pq pitch (F2_PX, FV_PX)
+PX = 36                   # xbar / pq pitch (F2_PX)
 LDS_MAX = 160 * 1024
 FAMILIES = {'f2': 20, 'f2v': 25}
 
@@ -57,7 +57,7 @@ def vp(V):
 
 
 def fv_e_lds(Cin, R, ntp, V=25):
-    """fv_e_lds of csrc/f2v.hip in bytes"""
+    """FvHost<V>::fv_e_lds of csrc/f2v.hip (f2_e_lds of csrc/f2_common.h at FvGeo<V>'s pitches) in bytes"""
     Kp, R2p, Rp = (Cin + 15) & ~15, max(16, 2 * R), (R + 15) & ~15
     PD = ((V * vp(V) + 15) // 16) * 16 + 4
     return 4 * (Kp * PX + R2p * PX + 64 * PX + max(Rp * PD, ntp * Kp * vp(V)))

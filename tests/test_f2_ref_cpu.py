@@ -1,5 +1,5 @@
 """The fp64 references of the small-batch eval stages (tests/f2_ref.py) without a GPU: anchored to the fp64 oracle on block
-geometries the stock model never has, their mirrored constants held to the source text of csrc/f2.hip / f2v.hip, the ledger's
+geometries the stock model never has, their mirrored constants held to the source text of csrc/f2_common.h, f2x_body.h, f2.hip and f2v.hip, the ledger's
 table held to the list of code paths it must reach, and the bars shown to pass a correct fp32 evaluation and to fail three
 planted defects (a dropped tap, a zero-padded pooled maximum, the floor division of the p/q row tiles)."""
 import os
@@ -138,27 +138,48 @@ def _const(text, name):
     return int(m.group(1))
 
 
+def _defined_once(name, home, others):
+    """the value of a constant that f2_common.h (or another one file) defines and no other source of the family does"""
+    for text in others:
+        assert not re.search(r'\b' + name + r'\s*=[^=]', text), f'{name} is defined a second time'
+    return _const(home, name)
+
+
 def test_mirrored_constants_match_the_kernels():
-    f2, fv = _src('f2.hip'), _src('f2v.hip')
-    assert _const(f2, 'F2_BT') == R.BT == _const(fv, 'FV_BT')
-    assert _const(f2, 'F2_HF') == R.HF == _const(fv, 'FV_HF')
-    assert _const(f2, 'F2_PX') == R.PX == _const(fv, 'FV_PX')
-    assert _const(fv, 'FV_KC') == R.KC
-    assert _const(f2, 'F2_V') == R.FAMILIES['f2'] and _const(fv, 'FV_V') == R.FAMILIES['f2v']
+    f2, fv, fg, cm, body = (_src(n) for n in ('f2.hip', 'f2v.hip', 'f2g.hip', 'f2_common.h', 'f2x_body.h'))
+    rest = (f2, fv, fg, body)
+    assert _defined_once('F2_BT', cm, rest) == R.BT
+    assert _defined_once('F2_HF', cm, rest) == R.HF
+    assert _defined_once('F2_PX', cm, rest) == R.PX
+    assert _defined_once('F2_KC', cm, rest) == R.KC
+    for text in rest + (cm,):                                      # the per-family copies of those constants are gone
+        assert not re.search(r'\bF[VG]_(NT|BT|G|KC|HF|PX|CT|LDS_MAX)\b', text)
+    assert _defined_once('F2_V', f2, (fv, fg, cm, body)) == R.FAMILIES['f2']
+    assert _defined_once('FV_V', fv, (f2, fg, cm, body)) == R.FAMILIES['f2v']
     assert 'VP = (V + 3) & ~3' in fv and R.vp(25) == R.VP25 == 28 and R.vp(20) == 20
-    assert 'FV_LDS_MAX = 160 * 1024' in fv and 'lds <= 160 * 1024' in f2 and R.LDS_MAX == 160 * 1024
-    # the halo guard and the formula that switches f2v_e between 4 and 2 frame phases, as f2_ref restates them
-    for text, pre in ((f2, 'F2'), (fv, 'FV')):
-        assert f'({pre}_BT - 1) * d->stride + (d->ks - 1) * d->dil[b] + 1 <= {pre}_HF' in text
+    assert 'F2_LDS_MAX = 160 * 1024' in cm and R.LDS_MAX == 160 * 1024
+    for text in (f2, fv, fg):                                      # one cap, by its name, in front of every launch that can pass it
+        assert 'lds <= F2_LDS_MAX' in text and '160 * 1024' not in text
+    assert '160 * 1024' not in body
+    # the halo guard and the formula that switches f2v_e between 4 and 2 frame phases, as f2_ref restates them: one copy each
+    assert '(F2_BT - 1) * d->stride + (d->ks - 1) * d->dil[b] + 1 <= F2_HF' in cm
+    for text in rest:
+        assert 'd->dil[b] + 1 <=' not in text and 'R2p = 2 * R' not in text
     for frag in ('EC = V * VP', 'ECT = (EC + 15) / 16', 'PD = ECT * 16 + 4',
-                 'const int Kp = (Cin + 15) & ~15, R2p = 2 * R < 16 ? 16 : 2 * R, Rp = (R + 15) & ~15;',
-                 'const size_t d = (size_t)Rp * GV::PD, xp = (size_t)ntp * Kp * GV::VP;',
-                 'return sizeof(float) * ((size_t)Kp * FV_PX + (size_t)R2p * FV_PX + 64 * FV_PX + (d > xp ? d : xp));',
-                 'a.ntp = fv_e_lds(d->Cin, d->R, 4) <= FV_LDS_MAX ? 4 : 2;'):
+                 'static constexpr size_t fv_e_lds(int Cin, int R, int ntp) { return f2_e_lds(Cin, R, ntp, GV::VP, GV::PD); }',
+                 'a.ntp = fv_e_lds(a.Cin, a.R, 4) <= F2_LDS_MAX ? 4 : 2;'):
         assert frag in fv, frag
-    # the p/q product: row tiles rounded UP (2R = 24 needs two, 40 three, 56 four), K parts = 4 / row tiles
-    for text in (f2, fv):
+    for frag in ('constexpr size_t f2_e_lds(int Cin, int R, int ntp, int VP, int PD) {',
+                 'const int Kp = (Cin + 15) & ~15, R2p = 2 * R < 16 ? 16 : 2 * R, Rp = (R + 15) & ~15;',
+                 'const size_t d = (size_t)Rp * PD, xp = (size_t)ntp * Kp * VP;',
+                 'return sizeof(float) * ((size_t)Kp * F2_PX + (size_t)R2p * F2_PX + 64 * F2_PX + (d > xp ? d : xp));'):
+        assert frag in cm, frag
+    # the p/q product: row tiles rounded UP (2R = 24 needs two, 40 three, 56 four), K parts = 4 / row tiles -- in f2's body and
+    # in the one body f2v and f2g share
+    for text in (f2, body):
         assert 'nrt = (R2p + 15) / 16, nparts = 4 / nrt' in text
+    for text in (fv, fg, cm):
+        assert 'nparts' not in text
 
 
 def test_f2v_e_phase_switch_sides():

@@ -24,8 +24,8 @@ UCLA = dict(num_class=10, num_point=20, num_person=1, graph='graph.ucla.Graph', 
 NTU = dict(num_class=60, num_point=25, num_person=2, graph='graph.ntu_rgb_d.Graph', graph_args=dict(labeling_mode='spatial'))
 
 
-def _src():
-    with open(os.path.join(ROOT, 'tam_gcn_amd', 'csrc', 'f2v.hip')) as f:
+def _src(name='f2v.hip'):
+    with open(os.path.join(ROOT, 'tam_gcn_amd', 'csrc', name)) as f:
         return f.read()
 
 
@@ -35,8 +35,10 @@ def test_joints_mirror_the_instantiation_list_of_the_source():
     assert len(lists) == 1, 'the joint counts are kept in ONE place'
     joints = tuple(int(v) for v in re.findall(r'X\((\d+)\)', lists[0]))
     assert joints == f2v.JOINTS == (17, 18, 25)
-    # nothing is instantiated past the list: no kernel or host template is named with a literal joint count
-    assert not re.search(r'_kernel<\s*\d+\s*>', src) and not re.search(r'FvHost<\s*\d+\s*>', src)
+    # nothing is instantiated past the list: no kernel, host template or geometry is named with a literal joint count -- in
+    # f2v.hip or in the bodies it shares with f2g.hip
+    for text in (src, _src('f2x_body.h'), _src('f2_common.h')):
+        assert not re.search(r'_kernel<\s*\d+\s*>', text) and not re.search(r'FvHost<\s*\d+\s*>', text) and not re.search(r'FvGeo<\s*\d+\s*>', text)
     assert all(v % 4 for v in joints)                            # V % 4 != 0 stays asserted in FvGeo
     assert 'V % 4 != 0' in src
 
@@ -179,7 +181,7 @@ def test_fp32_evaluation_passes_every_bar_of_the_ledger(stage, V):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the host LDS requests, restated from the geometry (FvGeo and the fv_*_lds formulas of csrc/f2v.hip)
+# the host LDS requests, restated from the geometry (FvGeo of csrc/f2v.hip and the f2_*_lds formulas of csrc/f2_common.h)
 # ---------------------------------------------------------------------------------------------------------------------
 def _geo(V):
     VP = (V + 3) & ~3
