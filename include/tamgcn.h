@@ -610,6 +610,47 @@ int tamgcn_clip_draw(const int* extent, long long n_clips, const long long* clip
 int tamgcn_clip_transform(const float* raw, long long n_clips, const long long* clip_ids, const int* plan, const int* node,
                           const double* keys, int num_node, int B, int C, int T, int W, int V, int M, float* out, void* stream);
 
+/* ---- the same feeder's crop-and-resize mode: the pipeline CTR-GCN was published with (its feeders/tools.py valid_crop_resize
+ * and random_rot) -- a share p of the clip's valid frames, resized linearly in time to W frames, then one 3-D rotation per clip.
+ * Added in ABI 401 without a version bump: new entry points only.
+ *
+ * With (begin, end) from _clip_extent and valid = end - begin >= 1, the CROP of a slot is two integers (start, L):
+ *   one p (flag 1 clear, p = p0):  bias = trunc((1.0 - p) * valid / 2) in fp64, then bias = min(bias, (valid - 1) / 2);
+ *                                  start = begin + bias, L = valid - 2 bias            (the centre crop; L >= 1 for every p)
+ *   p drawn (flag 1):              p = p0 + u (p1 - p0) with u = w0 2^-32, fp64, no contraction;
+ *                                  L = min(max(floor(valid p), min_crop), valid);  bias = mulhi(w1, valid - L + 1);
+ *                                  start = begin + bias
+ *   rotation (flag 2):             a_k = theta (2 (w_k 2^-32) - 1) in fp64, no contraction, k = x, y, z;
+ *                                  R = (Rz(a_z) . Ry(a_y)) . Rx(a_x),  Rx = [[1,0,0],[0,c,s],[0,-s,c]],
+ *                                  Ry = [[c,0,-s],[0,1,0],[s,0,c]],  Rz = [[c,s,0],[-s,c,0],[0,0,1]], all in fp64, every entry
+ *                                  of a product summed over k = 0, 1, 2 left to right, rounded to fp32 once
+ * The draw stream is the one above (same key, same counter layout): block 0 gives w0 for p and w1 for bias, block 1 gives
+ * w0 .. w2 for the x, y and z angles.  The call counter advances by one after the draw iff flags != 0.
+ * This is the published pipeline wherever a clip's valid frames are a prefix without all-zero gaps (begin = 0, and valid = the
+ * number of non-zero frames, which is what the published code counts) -- how the NTU data tools write their clips.
+ *
+ * The RESIZE of output frame t in 0 .. W - 1, in fp32 and without contraction -- torch.nn.functional.interpolate(mode='bilinear',
+ * align_corners=False) on the time axis alone:
+ *     scale = (float)L / (float)W
+ *     src   = max(scale * (t + 0.5f) - 0.5f, 0)
+ *     i0    = min((int)src, L - 1);   i1 = min(i0 + 1, L - 1)
+ *     l1    = src - i0;               l0 = 1 - l1
+ *     y[c]  = l0 * x[c][start + i0] + l1 * x[c][start + i1]
+ * then with a rotation out[c] = R[c][0] y[0] + R[c][1] y[1] + R[c][2] y[2] (left to right, C = 3), and without one out = y
+ * with no further arithmetic.  L = W gives l1 = 0: the source frames themselves; L = 2 W gives l0 = l1 = 1/2: the once-rounded
+ * mean of two frames.
+ *
+ * _clip_crop_draw  flags = 1 random crop | 2 rotation; 0 < p0 <= p1 <= 1, min_crop >= 1, theta finite and >= 0.  -> crop int32
+ *                  [B][2] = (start, L), drawn fp64 [B][4] = (p, a_x, a_y, a_z) (angles 0 without flag 2), rot fp32 [B][9]
+ *                  row-major (written with flag 2 only; may be NULL without it), labels_out as _clip_draw.  One thread per slot.
+ * _clip_resize     out (B, C, W, V, M) from raw, clip_ids and crop; rot fp32 [B][9] or NULL (none).  L is clamped to 1 .. T and
+ *                  start to 0 .. T - L, so no value of crop reads out of bounds.  No atomics: two calls give the same bits. */
+int tamgcn_clip_crop_draw(const int* extent, long long n_clips, const long long* clip_ids, int B, const long long* labels,
+                          long long* state, int flags, double p0, double p1, int min_crop, double theta, int* crop, double* drawn,
+                          float* rot, long long* labels_out, void* stream);
+int tamgcn_clip_resize(const float* raw, long long n_clips, const long long* clip_ids, const int* crop, const float* rot /* NULL: none */,
+                       int B, int C, int T, int W, int V, int M, float* out, void* stream);
+
 /* ---- f2: the eval-mode TCN_GCN_unit for small batches (callers: reference
  * ensemble/ensemble_ctrgcn_resnet_eval.py:147-183, models/resnet_gcn_attention.py:82-85, visual.py:53-55 -- model(data)
  * on 1..16 clips in eval mode).  Five launches per block, each 50..130 workgroups per clip; V = 20, S = 3 (V = 25: the f2v

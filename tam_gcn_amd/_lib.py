@@ -229,6 +229,8 @@ SIGNATURES = {
     'tamgcn_clip_extent': (_i, [_p, _ll, _i, _i, _i, _i, _p, _p]),
     'tamgcn_clip_draw': (_i, [_p, _ll, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     'tamgcn_clip_transform': (_i, [_p, _ll, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    'tamgcn_clip_crop_draw': (_i, [_p, _ll, _p, _i, _p, _p, _i, _d, _d, _i, _d, _p, _p, _p, _p, _p]),
+    'tamgcn_clip_resize': (_i, [_p, _ll, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     'tamgcn_f2_e': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2_gcn': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2_gemm': (_i, [C.POINTER(F2GemmDesc), _p]),

@@ -3,7 +3,9 @@
 // feeder/feeder_nucla_fusion.py:95-106 through feeder/tools.py (random_shift :118-130, random_choose / auto_pading :39-62, the
 // centre crop, random_move :65-115).  Shift and window compose to three integers per batch slot (the "plan": output frame t is
 // raw frame src0 + t for lo <= t < hi and zero elsewhere), so no intermediate clip exists; the move is a per-frame 2 x 2 map of
-// the x and y planes in fp64.  include/tamgcn.h has the contract and the definition of the draw stream.
+// the x and y planes in fp64.  A second mode, not from the reference, is the pipeline CTR-GCN was published with: a crop (start, L)
+// of the valid frames resized linearly in time to the window, then one 3-D rotation per clip (clip_crop_draw_kernel,
+// clip_resize_kernel).  include/tamgcn.h has the contract and the definition of the draw stream.
 #include "common.h"
 #include "feeder_common.h"
 
@@ -238,6 +240,182 @@ __global__ __launch_bounds__(256) void clip_transform_kernel(const ClipXfArgs a)
     store_span<VEC>(o + rowlen, y);
 }
 
+// ---- crop-and-resize mode: the draws --------------------------------------------------------------------------------------------
+// The pipeline CTR-GCN was published with: a share p of the clip's valid frames, cropped at the centre (one p) or at a drawn
+// place (p drawn on [p0, p1)), resized linearly to W frames, then one rotation per clip.  include/tamgcn.h has the definition.
+struct ClipCropArgs {
+    const int* extent;          // [n_clips][2]
+    const long long* clip_ids;  // [B], taken modulo n_clips
+    const long long* labels;    // [n_clips] or null
+    const long long* state;     // [2] = (seed, call counter)
+    long long n_clips;
+    int B, flags, min_crop;
+    double p0, p1, theta;
+    int* crop;                  // [B][2] = (start, L)
+    double* drawn;              // [B][4] = (p, a_x, a_y, a_z)
+    float* rot;                 // [B][9] (flag 2 only)
+    long long* labels_out;      // [B] or null
+};
+
+// o = a . b, 3 x 3 row-major, every entry summed over k = 0, 1, 2 left to right
+__device__ __forceinline__ void mat3_mul(const double* a, const double* b, double* o) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[3 * r + c] = a[3 * r] * b[c] + a[3 * r + 1] * b[3 + c] + a[3 * r + 2] * b[6 + c];
+}
+
+__global__ __launch_bounds__(64) void clip_crop_draw_kernel(const ClipCropArgs a) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.B) return;
+    const long long clip = clip_of(a.clip_ids[b], a.n_clips);
+    if (a.labels_out) a.labels_out[b] = a.labels[clip];
+    const unsigned long long seed = (unsigned long long)a.state[0], call = (unsigned long long)a.state[1];
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32), cl = (unsigned)call, ch = (unsigned)(call >> 32);
+    const int begin = a.extent[2 * clip];
+    const int valid = max(a.extent[2 * clip + 1] - begin, 1);          // tamgcn_clip_extent gives >= 1
+    unsigned w[4];
+    double p = a.p0;
+    int bias, L;
+    if (a.flags & 1) {
+        philox4x32_10(cl, ch, (unsigned)b, 0u, k0, k1, w);
+        const double u = (double)w[0] * 0x1p-32;
+        p = a.p0 + u * (a.p1 - a.p0);
+        L = min(max((int)floor((double)valid * p), a.min_crop), valid);
+        bias = (int)__umulhi(w[1], (unsigned)(valid - L + 1));
+    } else {
+        bias = min((int)((1.0 - p) * (double)valid / 2.0), (valid - 1) / 2);
+        L = valid - 2 * bias;
+    }
+    a.crop[2 * b + 0] = begin + bias;
+    a.crop[2 * b + 1] = L;
+    double ang[3] = {0.0, 0.0, 0.0};
+    if (a.flags & 2) {
+        philox4x32_10(cl, ch, (unsigned)b, 1u, k0, k1, w);
+        double s[3], c[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            ang[k] = a.theta * (2.0 * ((double)w[k] * 0x1p-32) - 1.0);
+            sincos(ang[k], &s[k], &c[k]);
+        }
+        const double rx[9] = {1.0, 0.0, 0.0, 0.0, c[0], s[0], 0.0, -s[0], c[0]};
+        const double ry[9] = {c[1], 0.0, -s[1], 0.0, 1.0, 0.0, s[1], 0.0, c[1]};
+        const double rz[9] = {c[2], s[2], 0.0, -s[2], c[2], 0.0, 0.0, 0.0, 1.0};
+        double zy[9], r[9];
+        mat3_mul(rz, ry, zy);
+        mat3_mul(zy, rx, r);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) a.rot[9 * (long long)b + k] = (float)r[k];
+    }
+    a.drawn[4 * (long long)b + 0] = p;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) a.drawn[4 * (long long)b + 1 + k] = ang[k];
+}
+
+// ---- crop-and-resize mode: the gather -------------------------------------------------------------------------------------------
+struct ClipRsArgs {
+    const float* raw;           // (n_clips, C, T, V, M)
+    const long long* clip_ids;  // [B], taken modulo n_clips
+    const int* crop;            // [B][2] = (start, L)
+    const float* rot;           // [B][9] or null
+    long long n_clips;
+    int B, C, T, W, VM, tiles, G;
+    float* out;                 // (B, C, W, V, M)
+};
+
+// The two source frames of output frame t and their weights: F.interpolate(mode='bilinear', align_corners=False) on the time
+// axis, in fp32 and without contraction.  o0, o1 are element offsets into a channel plane of the clip.
+struct Tap { int o0, o1; float l0, l1; };
+
+__device__ __forceinline__ Tap resize_tap(int t, int start, int L, float scale, int VM) {
+#pragma clang fp contract(off)
+    const float src = fmaxf(scale * ((float)t + 0.5f) - 0.5f, 0.f);
+    const int i0 = min((int)src, L - 1), i1 = min(i0 + 1, L - 1);
+    const float l1 = src - (float)i0;
+    Tap tp;
+    tp.o0 = (start + i0) * VM; tp.o1 = (start + i1) * VM; tp.l0 = 1.f - l1; tp.l1 = l1;
+    return tp;
+}
+
+// VEC consecutive floats at p: one 16-byte access where p allows it (a source frame starts at a multiple of V M floats, which
+// for NTU's 50 is 16-byte aligned on every other frame only), dword accesses otherwise
+template <int VEC>
+__device__ __forceinline__ void load_vec(const float* __restrict__ p, float* v) {
+    if (VEC == 4 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) v[j] = q[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) v[j] = p[j];
+    }
+}
+
+// One thread per VEC consecutive positions of an output row of W VM floats; blockIdx.x = ((slot, group), tile of 256 VEC
+// positions).  Without the rotation a group is a channel; with it there is one group, and a thread reads, blends, maps and
+// writes the three channels of its positions.  Positions inside one output frame share their two source frames, so the span is
+// two VEC-wide loads per channel; a span that crosses into the next frame (VM % VEC != 0) goes position by position.  start and
+// L are clamped into the clip: whatever crop holds, every frame read is one of the clip's own T.
+template <int VEC, bool ROT>
+__global__ __launch_bounds__(256) void clip_resize_kernel(const ClipRsArgs a) {
+#pragma clang fp contract(off)
+    constexpr int NC = ROT ? 3 : 1;
+    const unsigned blk = blockIdx.x;
+    const int tile = (int)(blk % (unsigned)a.tiles), sg = (int)(blk / (unsigned)a.tiles);
+    const int g = sg % a.G, b = sg / a.G;
+    const int rowlen = a.W * a.VM;
+    const int i = (tile * 256 + (int)threadIdx.x) * VEC;
+    if (i >= rowlen) return;
+    const long long clip = clip_of(a.clip_ids[b], a.n_clips);
+    const int L = min(max(a.crop[2 * b + 1], 1), a.T);
+    const int start = min(max(a.crop[2 * b], 0), a.T - L);
+    const float scale = (float)L / (float)a.W;
+    const int plane = a.T * a.VM;
+    const int c0 = ROT ? 0 : g;
+    const float* src = a.raw + (clip * a.C + c0) * (long long)plane;
+    float* o = a.out + ((long long)b * a.C + c0) * rowlen + i;
+    float y[NC][VEC];
+    const int t = i / a.VM, vm = i - t * a.VM;
+    if (VEC == 1 || vm + VEC <= a.VM) {
+        const Tap tp = resize_tap(t, start, L, scale, a.VM);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            float x0[VEC], x1[VEC];
+            load_vec<VEC>(src + (long long)c * plane + tp.o0 + vm, x0);
+            load_vec<VEC>(src + (long long)c * plane + tp.o1 + vm, x1);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) y[c][j] = tp.l0 * x0[j] + tp.l1 * x1[j];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            const int tj = (i + j) / a.VM, vj = i + j - tj * a.VM;
+            const Tap tp = resize_tap(tj, start, L, scale, a.VM);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const float* q = src + (long long)c * plane + vj;
+                y[c][j] = tp.l0 * q[tp.o0] + tp.l1 * q[tp.o1];
+            }
+        }
+    }
+    if constexpr (ROT) {
+        float r[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) r[k] = a.rot[9 * (long long)b + k];
+        float z[3][VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) z[c][j] = r[3 * c] * y[0][j] + r[3 * c + 1] * y[1][j] + r[3 * c + 2] * y[2][j];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) store_span<VEC>(o + (long long)c * rowlen, z[c]);
+    } else {
+        store_span<VEC>(o, y[0]);
+    }
+}
+
 }  // namespace
 
 extern "C" int tamgcn_clip_extent(const float* raw, long long n_clips, int C, int T, int V, int M, int* extent, void* stream) {
@@ -310,5 +488,56 @@ extern "C" int tamgcn_clip_transform(const float* raw, long long n_clips, const 
     else hipLaunchKernelGGL((clip_transform_kernel<1, false>), grid, block, 0, (hipStream_t)stream, a);
     tamgcn_note_kernel("clip_transform_kernel<%d, %s>", vec ? 4 : 1, move ? "move" : "copy");
     TG_LAUNCH_CHECK("tamgcn_clip_transform");
+    return 0;
+}
+
+extern "C" int tamgcn_clip_crop_draw(const int* extent, long long n_clips, const long long* clip_ids, int B, const long long* labels,
+                                     long long* state, int flags, double p0, double p1, int min_crop, double theta, int* crop,
+                                     double* drawn, float* rot, long long* labels_out, void* stream) {
+    TG_CHECK(extent && clip_ids && state && crop && drawn, "tamgcn_clip_crop_draw: null pointer");
+    TG_CHECK(B > 0 && n_clips > 0, "tamgcn_clip_crop_draw: bad dims B=%d n_clips=%lld", B, n_clips);
+    TG_CHECK(flags >= 0 && flags <= 3, "tamgcn_clip_crop_draw: flags %d (1 random crop | 2 rotation)", flags);
+    TG_CHECK(p0 > 0.0 && p0 <= p1 && p1 <= 1.0, "tamgcn_clip_crop_draw: p0=%g p1=%g outside 0 < p0 <= p1 <= 1", p0, p1);   // NaN fails too
+    TG_CHECK(min_crop >= 1, "tamgcn_clip_crop_draw: min_crop %d below 1", min_crop);
+    TG_CHECK(theta >= 0.0 && theta <= 1.79e308, "tamgcn_clip_crop_draw: theta=%g must be finite and >= 0", theta);
+    TG_CHECK(!(flags & 2) || rot, "tamgcn_clip_crop_draw: the rotation needs rot");
+    TG_CHECK((labels == nullptr) == (labels_out == nullptr), "tamgcn_clip_crop_draw: labels and labels_out go together");
+    ClipCropArgs a;
+    a.extent = extent; a.clip_ids = clip_ids; a.labels = labels; a.state = state; a.n_clips = n_clips; a.B = B; a.flags = flags;
+    a.min_crop = min_crop; a.p0 = p0; a.p1 = p1; a.theta = theta; a.crop = crop; a.drawn = drawn; a.rot = rot; a.labels_out = labels_out;
+    hipLaunchKernelGGL(clip_crop_draw_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, (hipStream_t)stream, a);
+    tamgcn_note_kernel("clip_crop_draw_kernel");
+    TG_LAUNCH_CHECK("tamgcn_clip_crop_draw");
+    if (flags) {                                        // nothing random: nothing of the stream is consumed
+        hipLaunchKernelGGL(clip_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state);
+        TG_LAUNCH_CHECK("tamgcn_clip_crop_draw (advance)");
+    }
+    return 0;
+}
+
+extern "C" int tamgcn_clip_resize(const float* raw, long long n_clips, const long long* clip_ids, const int* crop, const float* rot, int B,
+                                  int C, int T, int W, int V, int M, float* out, void* stream) {
+    TG_CHECK(raw && clip_ids && crop && out, "tamgcn_clip_resize: null pointer");
+    TG_CHECK(B > 0 && n_clips > 0 && C > 0 && T > 0 && W > 0 && V > 0 && M > 0, "tamgcn_clip_resize: bad dims B=%d n_clips=%lld C=%d T=%d W=%d V=%d M=%d",
+             B, n_clips, C, T, W, V, M);
+    TG_CHECK((long long)T * V * M <= (1LL << 30) && (long long)W * V * M <= (1LL << 30), "tamgcn_clip_resize: a channel plane above 2^30 elements (T=%d W=%d V=%d M=%d)",
+             T, W, V, M);
+    TG_CHECK(!rot || C == 3, "tamgcn_clip_resize: the rotation maps three channels, C=%d", C);
+    const int rowlen = W * V * M;
+    const bool vec = rowlen % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    ClipRsArgs a;
+    a.raw = raw; a.clip_ids = clip_ids; a.crop = crop; a.rot = rot; a.n_clips = n_clips;
+    a.B = B; a.C = C; a.T = T; a.W = W; a.VM = V * M; a.out = out;
+    a.tiles = ceil_div(rowlen, 256 * (vec ? 4 : 1));
+    a.G = rot ? 1 : C;
+    const long long blocks = (long long)B * a.G * a.tiles;
+    TG_CHECK(blocks < (1LL << 31), "tamgcn_clip_resize: %lld workgroups", blocks);
+    const dim3 grid((unsigned)blocks), block(256);
+    if (vec && rot) hipLaunchKernelGGL((clip_resize_kernel<4, true>), grid, block, 0, (hipStream_t)stream, a);
+    else if (vec) hipLaunchKernelGGL((clip_resize_kernel<4, false>), grid, block, 0, (hipStream_t)stream, a);
+    else if (rot) hipLaunchKernelGGL((clip_resize_kernel<1, true>), grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((clip_resize_kernel<1, false>), grid, block, 0, (hipStream_t)stream, a);
+    tamgcn_note_kernel("clip_resize_kernel<%d, %s>", vec ? 4 : 1, rot ? "rot" : "plain");
+    TG_LAUNCH_CHECK("tamgcn_clip_resize");
     return 0;
 }

@@ -22,6 +22,22 @@ the reference's draws).  ``batch_device(indices)`` takes the indices as an int64
 defined in include/tamgcn.h and INTEGRATION.md): no host work, no synchronisation, capturable -- ``GraphedBatch``,
 ``CapturedEval`` and ``CapturedStep`` take this feeder as they take the N-UCLA one.  ``normalization=True`` is accepted and
 does nothing, as in the reference (``get_mean_map`` at :34-35 is empty).  RGB loading is the other modality: not here.
+
+``p_interval=`` switches to a second pipeline, the one CTR-GCN was published with for NTU-style arrays (its
+``feeders/tools.py``: ``valid_crop_resize`` and ``random_rot``), in place of steps 1 to 3:
+
+  a. crop a share ``p`` of the clip's valid frames: ``p_interval=[p]`` the centre crop (evaluation), ``p_interval=[p0, p1]``
+     a share drawn per sample at a drawn place, at least ``min_crop`` frames long (training);
+  b. resize the crop linearly in time to ``window_size`` frames (``F.interpolate(mode='bilinear', align_corners=False)`` on
+     the time axis alone);
+  c. ``random_rot``: one rotation per clip, ``Rz Ry Rx`` with the three angles uniform on ``[-rot_theta, rot_theta)``.
+
+``stream`` is derived last, as above.  The valid frames are those of the clip's extent, ``begin .. end``: this is the published
+pipeline wherever a clip's valid frames are a prefix without all-zero gaps, which is how the NTU data tools write them.
+include/tamgcn.h has the arithmetic.  ``batch()`` draws as the published code does -- per sample ``np.random.rand(1)`` then
+``np.random.randint(0, valid - L + 1)`` for a two-element interval, then ``torch.zeros(3).uniform_(-theta, theta)`` for the
+rotation -- and ``batch_device()`` on the device; ``last_draws`` then holds ``crop`` int32 (B, 2) = (start, L), ``drawn`` fp64
+(B, 4) = (p, a_x, a_y, a_z) and ``rot`` fp32 (B, 3, 3) or None.
 """
 import pickle
 import random
@@ -51,6 +67,28 @@ def make_plan(begin, end, T, W, bias, d):
     return d - bias + begin, max(0, bias - d), min(W, bias + (end - begin) - d)
 
 
+def crop_of(valid, p):
+    """(bias, L) of the centre crop of share ``p`` out of ``valid`` frames (CTR-GCN feeders/tools.py valid_crop_resize, the
+    one-element p_interval), kept to L >= 1."""
+    bias = min(int((1.0 - p) * valid / 2), (valid - 1) // 2)
+    return bias, valid - 2 * bias
+
+
+def rot_matrix(angles):
+    """R = (Rz(a_z) . Ry(a_y)) . Rx(a_x) of CTR-GCN's random_rot for angles = (a_x, a_y, a_z) in radians: fp64, every entry of a
+    product summed over k = 0, 1, 2 left to right (what the draw kernel does), rounded to fp32 once."""
+    ax, ay, az = (np.float64(a) for a in angles)
+    one, zero = np.float64(1.0), np.float64(0.0)
+    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    rx = [[one, zero, zero], [zero, cx, sx], [zero, -sx, cx]]
+    ry = [[cy, zero, -sy], [zero, one, zero], [sy, zero, cy]]
+    rz = [[cz, sz, zero], [-sz, cz, zero], [zero, zero, one]]
+
+    def mul(a, b):
+        return [[a[r][0] * b[0][c] + a[r][1] * b[1][c] + a[r][2] * b[2][c] for c in range(3)] for r in range(3)]
+    return np.array(mul(mul(rz, ry), rx), dtype=np.float64).astype(np.float32)
+
+
 def _candidates(values, default, what):
     v = np.asarray(default if values is None else values, dtype=np.float64)
     if v.ndim != 1 or v.size < 1 or not np.isfinite(v).all():
@@ -62,7 +100,7 @@ class Feeder(Dataset):
     def __init__(self, data_path, label_path, random_choose=False, random_shift=False, random_move=False, window_size=-1,
                  normalization=False, debug=False, use_mmap=True, split='train', stream='joint', parent=None, move_time=1,
                  angle_candidate=None, scale_candidate=None, transform_candidate=None, data=None, labels=None, device='cuda',
-                 seed=0):
+                 seed=0, p_interval=None, min_crop=64, random_rot=False, rot_theta=0.3):
         self.data_path, self.label_path, self.split = data_path, label_path, split
         self.random_choose, self.random_shift, self.random_move = bool(random_choose), bool(random_shift), bool(random_move)
         self.normalization, self.debug, self.use_mmap = normalization, debug, use_mmap
@@ -82,11 +120,14 @@ class Feeder(Dataset):
         self.seed, self.last_draws = self._check_seed(seed, 'seed'), None
         self.flags = ((ops.CLIP_SHIFT if self.random_shift else 0) | (ops.CLIP_CHOOSE if self.random_choose else 0)
                       | (ops.CLIP_MOVE if self.random_move else 0))
+        self._check_crop_mode(p_interval, min_crop, random_rot, rot_theta)
         # CapturedEval asks for 'val': a feeder whose batches are a function of the indices alone
-        self.train_val = 'train' if self.flags else 'val'
+        self.train_val = 'train' if self.flags or self.crop_flags else 'val'
         self.device = torch.device(device)
         self.load_data(data, labels)
         N, C, T, V, M = self.data.shape
+        if self.random_rot and C != 3:
+            raise ValueError(f'Feeder: random_rot maps three channels; the clips have C = {C}')
         self.T, self.W = T, (self.window_size if self.window_size > 0 else T)
         if max(T, self.W) * V * M > 2 ** 30:
             raise ValueError(f'Feeder: a channel plane of {max(T, self.W)} x {V} x {M} elements is above 2^30')
@@ -103,6 +144,34 @@ class Feeder(Dataset):
         self._upload(parent)
         if normalization:
             self.get_mean_map()
+
+    def _check_crop_mode(self, p_interval, min_crop, random_rot, rot_theta):
+        self.random_rot = bool(random_rot)
+        if isinstance(min_crop, bool) or not isinstance(min_crop, (int, np.integer)) or min_crop < 1:
+            raise ValueError(f'Feeder: min_crop = {min_crop!r} must be an integer >= 1')
+        self.min_crop = int(min_crop)
+        if isinstance(rot_theta, bool) or not isinstance(rot_theta, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(rot_theta) or rot_theta < 0:
+            raise ValueError(f'Feeder: rot_theta = {rot_theta!r} must be a finite number >= 0')
+        self.rot_theta = float(rot_theta)
+        if p_interval is not None:
+            try:
+                p = [float(v) for v in p_interval]
+            except (TypeError, ValueError):
+                p = []
+            if len(p) not in (1, 2) or not 0 < p[0] <= p[-1] <= 1:                     # NaN fails the comparison too
+                raise ValueError(f'Feeder: p_interval = {p_interval!r} must be one or two numbers, 0 < p0 <= p1 <= 1')
+            if self.window_size <= 0:
+                raise ValueError('Feeder: p_interval resizes the crop to window_size frames: window_size must be > 0')
+            if self.flags:
+                raise ValueError('Feeder: p_interval excludes random_shift, random_choose and random_move')
+            p_interval = tuple(p)
+        elif self.random_rot:
+            raise ValueError('Feeder: random_rot needs p_interval (the rotation follows the resize)')
+        self.p_interval = p_interval
+        self.crop_flags = 0
+        if p_interval is not None:
+            self.crop_flags = (ops.CLIP_CROP_RANDOM if len(p_interval) == 2 else 0) | (ops.CLIP_ROT if self.random_rot else 0)
 
     # ---- reference :37-38, and the ST-GCN / CTR-GCN data tools' files ---------------------------------------------------
     def load_data(self, data=None, labels=None):
@@ -175,6 +244,33 @@ class Feeder(Dataset):
         cand = (self.angle_candidate, self.scale_candidate, self.transform_candidate, self.transform_candidate)
         return np.stack([c[move[..., q]] for q, c in enumerate(cand)], axis=-1)
 
+    def _draw_crop(self, index):
+        """(start, L), (p, a_x, a_y, a_z), R | None of one sample in the crop-and-resize mode: the published pipeline's RNG
+        consumption, call for call."""
+        begin, end = (int(v) for v in self._extent_cpu[index])
+        valid = max(end - begin, 1)
+        p = self.p_interval[0]
+        if len(self.p_interval) == 2:
+            p = float(np.random.rand(1)[0] * (self.p_interval[1] - self.p_interval[0]) + self.p_interval[0])
+            L = min(max(int(np.floor(valid * p)), self.min_crop), valid)
+            bias = int(np.random.randint(0, valid - L + 1))
+        else:
+            bias, L = crop_of(valid, p)
+        ang, rot = (0.0, 0.0, 0.0), None
+        if self.random_rot:
+            ang = tuple(float(a) for a in torch.zeros(3).uniform_(-self.rot_theta, self.rot_theta))
+            rot = rot_matrix(ang)
+        return (begin + bias, L), (p,) + ang, rot
+
+    def _batch_crop(self, indices):
+        crops, drawn, rots = zip(*(self._draw_crop(i) for i in indices))
+        dev = self.device
+        crop = torch.tensor(crops, dtype=torch.int32, device=dev)
+        rot = torch.from_numpy(np.stack(rots)).to(dev) if self.random_rot else None
+        out = ops.clip_resize(self._raw, torch.tensor(indices, dtype=torch.int64, device=dev), crop, self.W, rot)
+        self.last_draws = {'crop': crop, 'drawn': torch.tensor(drawn, dtype=torch.float64, device=dev), 'rot': rot}
+        return out
+
     def _finish(self, out):
         return ops.stream_derive(out, self._parent, self.stream) if self._parent is not None else out
 
@@ -184,8 +280,11 @@ class Feeder(Dataset):
         indices = [int(i) % len(self.label) for i in indices]
         if not indices:
             raise ValueError('Feeder.batch: no indices')
-        plans, shifts, moves = zip(*(self._draw(i) for i in indices))
         dev = self.device
+        if self.p_interval is not None:
+            out = self._batch_crop(indices)
+            return self._finish(out), torch.tensor([self.label[i] for i in indices], dtype=torch.int64, device=dev), indices
+        plans, shifts, moves = zip(*(self._draw(i) for i in indices))
         plan = torch.tensor(plans, dtype=torch.int32, device=dev)
         node = keys = move = None
         if self.random_move:
@@ -204,12 +303,20 @@ class Feeder(Dataset):
         on by one iff a random flag is set.  Two launches (three with a counter advance, one more for a derived stream) on
         the current stream, no copy from the host, no synchronisation: capturable.  ``last_draws`` keeps what the launch
         drew: ``plan`` int32 (B, 3) = (src0, lo, hi), ``shift`` int32 (B, 2) = (bias, d), ``move`` int32 (B, num_node, 4) =
-        indices into the angle, scale, translation and translation candidates (None without random_move)."""
+        indices into the angle, scale, translation and translation candidates (None without random_move).  With p_interval:
+        ``crop`` int32 (B, 2) = (start, L), ``drawn`` fp64 (B, 4) = (p, a_x, a_y, a_z), ``rot`` fp32 (B, 3, 3) or None; the
+        counter moves on iff the interval has two elements or random_rot is set."""
         if not (isinstance(indices, torch.Tensor) and indices.dtype == torch.int64 and indices.dim() == 1
                 and indices.device == self._raw.device and indices.numel() > 0):
             raise ValueError('Feeder.batch_device: indices must be a non-empty 1-D int64 tensor on the feeder\'s device '
                              '(batch() takes host indices)')
         indices = indices.contiguous()
+        if self.p_interval is not None:
+            crop, drawn, rot, lab = ops.clip_crop_draw(self._extent, indices, self._rng, self.crop_flags, self.p_interval[0],
+                                                       self.p_interval[-1], self.min_crop, self.rot_theta, labels=self._labels)
+            out = ops.clip_resize(self._raw, indices, crop, self.W, rot)
+            self.last_draws = {'crop': crop, 'drawn': drawn, 'rot': rot}
+            return self._finish(out), lab
         plan, shift, move, keys, lab = ops.clip_draw(self._extent, indices, self._rng, self.flags, self.T, self.W, len(self.node),
                                                      self._cand if self.random_move else None, labels=self._labels)
         out = ops.clip_transform(self._raw, indices, plan, self.W, self._node if self.random_move else None, keys)

@@ -1144,6 +1144,52 @@ def clip_transform(raw, clip_ids, plan, W, node=None, keys=None):
     return out
 
 
+# the same feeder's crop-and-resize mode (include/tamgcn.h has the crop, the rotation and the resize)
+CLIP_CROP_RANDOM, CLIP_ROT = 1, 2
+
+
+def clip_crop_draw(extent, clip_ids, state, flags, p0, p1, min_crop=64, theta=0.3, labels=None):
+    """One batch's crops and rotations on the device (tamgcn_clip_crop_draw).  extent int32 (n_clips, 2), clip_ids int64 [B]
+    (taken modulo n_clips), state int64 [2] = (seed, call) read on the device and advanced by one iff flags != 0; flags =
+    CLIP_CROP_RANDOM | CLIP_ROT; 0 < p0 <= p1 <= 1 (without CLIP_CROP_RANDOM the centre crop of share p0).
+    -> crop int32 (B, 2) = (start, L), drawn fp64 (B, 4) = (p, a_x, a_y, a_z), rot fp32 (B, 3, 3) | None, labels int64 (B,) |
+    None.  No host sync, capturable."""
+    _want(extent, 'extent', torch.int32)
+    _want(clip_ids, 'clip_ids', torch.int64)
+    _want(state, 'state', torch.int64, (2,))
+    if extent.dim() != 2 or extent.shape[1] != 2 or clip_ids.dim() != 1:
+        raise RuntimeError('tam_gcn_amd: clip_crop_draw takes extent (n_clips, 2) and 1-D clip_ids')
+    n_clips, B, dev = extent.shape[0], clip_ids.numel(), extent.device
+    if labels is not None:
+        _want(labels, 'labels', torch.int64, (n_clips,))
+    crop = torch.empty(B, 2, device=dev, dtype=torch.int32)
+    drawn = torch.empty(B, 4, device=dev, dtype=torch.float64)
+    rot = torch.empty(B, 3, 3, device=dev, dtype=torch.float32) if flags & CLIP_ROT else None
+    lab = torch.empty(B, device=dev, dtype=torch.int64) if labels is not None else None
+    _lib.check(_lib_().tamgcn_clip_crop_draw(_ptr(extent), n_clips, _ptr(clip_ids), B, _ptr(labels), _ptr(state), int(flags), float(p0),
+                                             float(p1), int(min_crop), float(theta), _ptr(crop), _ptr(drawn), _ptr(rot), _ptr(lab),
+                                             _stream()), 'tamgcn_clip_crop_draw')
+    return crop, drawn, rot, lab
+
+
+def clip_resize(raw, clip_ids, crop, W, rot=None):
+    """The crop-and-resize gather (tamgcn_clip_resize): raw (n_clips, C, T, V, M) fp32, clip_ids int64 [B] (taken modulo n_clips),
+    crop int32 (B, 2) = (start, L) (clamped into the clip), rot fp32 (B, 3, 3) | None (C = 3) -> (B, C, W, V, M) fp32."""
+    _want(raw, 'raw', torch.float32)
+    _want(clip_ids, 'clip_ids', torch.int64)
+    if raw.dim() != 5 or raw.numel() == 0 or clip_ids.dim() != 1:
+        raise RuntimeError(f'tam_gcn_amd: clip_resize takes a non-empty (n_clips, C, T, V, M) array and 1-D clip_ids, got {tuple(raw.shape)}')
+    n, C_, T, V, M = raw.shape
+    B = clip_ids.numel()
+    _want(crop, 'crop', torch.int32, (B, 2))
+    if rot is not None:
+        _want(rot, 'rot', torch.float32, (B, 3, 3))
+    out = torch.empty(B, C_, W, V, M, device=raw.device, dtype=torch.float32)
+    _lib.check(_lib_().tamgcn_clip_resize(_ptr(raw), n, _ptr(clip_ids), _ptr(crop), _ptr(rot), B, C_, T, W, V, M, _ptr(out), _stream()),
+               'tamgcn_clip_resize')
+    return out
+
+
 # ---------------------------------------------------------------------------
 # loss of the harness step (SURVEY.md §8 f1)
 def ce_fwd(logits, labels):

@@ -6,6 +6,13 @@
         device, (b) Feeder.batch_device() launched eagerly, (c) a GraphedBatch replay; legs alternated, three repeats.
         Then the transform alone: `batches` launches held in one HIP graph between two device events, and the bytes the
         gather needs (read: the copied spans; written: the whole batch) over that time.
+    python tools/clip_feeder_bench.py resize [batches] [steps]
+        the crop-and-resize mode (profiles/clip_resize_bench.txt): 128 x (3, 300, 25, 2) at W = 64, p_interval = [0.5, 1], with
+        and without the rotation -- ms per batch of (a) the published pipeline's own host operations (per sample the crop, torch's
+        F.interpolate and the matrix product, with the draws of tests/clip_resize_ref.py) plus the copy, (b) batch_device() eagerly, (c) a GraphedBatch replay; then the resize kernel alone in one HIP graph and the bytes
+        it needs (read: the source frames its taps name; written: the whole batch), beside clip_transform's centre crop of the
+        same split to the same window measured the same way; then one CapturedStep of the NTU model fed by a GraphedBatch at
+        W = 64 (this mode) and at W = 300 (the padded clips), `steps` steps per leg, legs alternated.
     python tools/clip_feeder_bench.py trace [batches]
         `batches` eager batch_device calls per configuration -- run it under rocprofv3 --kernel-trace
     python tools/clip_feeder_bench.py report <kernel_trace.csv> [batches]
@@ -144,6 +151,137 @@ def time_batches(batches=200):
               f'(launch gaps included; the kernel trace has the kernel\'s own time)')
 
 
+def _alone(launch, batches):
+    """us per launch of `launch()`, `batches` of them held in one HIP graph between two device events."""
+    import torch
+    for _ in range(3):
+        launch()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(batches):
+            launch()
+    g.replay()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / batches
+
+
+def _resize_bytes(R, crop, C, W, VM):
+    """Bytes one resize launch has to move: the distinct source frames its taps name read once, the whole batch written."""
+    import numpy as np
+    frames = 0
+    for _, L in crop:
+        i0, i1, _ = R.taps(int(L), W)
+        frames += len(np.union1d(i0, i1))
+    return 4 * C * VM * (frames + len(crop) * W)
+
+
+def _host_resize_batch(R, data, ext, ids, call, W, flags, p, min_crop, theta):
+    """The published pipeline's own operations on the host -- per sample the crop, F.interpolate(bilinear) over time, the fp32
+    matrix product -- with the restatement's draws, and the batch's copy to the device."""
+    import numpy as np
+    import torch
+    crop, drawn = R.crop_draws(1, call, ext[ids], flags, p[0], p[-1], min_crop, theta)
+    C, _, V, M = data.shape[1:]
+    out = torch.empty((len(ids), C, W, V, M), dtype=torch.float32)
+    for b, i in enumerate(ids):
+        x = torch.from_numpy(data[i][:, crop[b, 0]:crop[b, 0] + crop[b, 1]])
+        x = x.permute(0, 2, 3, 1).contiguous().view(C * V * M, -1)[None, None]
+        y = torch.nn.functional.interpolate(x, size=(C * V * M, W), mode='bilinear', align_corners=False).squeeze()
+        y = y.contiguous().view(C, V, M, W).permute(0, 3, 1, 2).contiguous()
+        if flags & R.ROT:
+            rot = torch.from_numpy(R.rot_matrix(drawn[b, 1:]).astype(np.float32))
+            y = torch.matmul(rot, y.view(C, -1)).view(C, W, V, M)
+        out[b] = y
+    return out.to(DEV)
+
+
+def _ntu_step(batch, W):
+    sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
+    from params import fill_state_, make_input, make_labels
+    from tam_gcn_amd.distributed import ParamArena
+    from tam_gcn_amd.functional import CrossEntropyLoss
+    from tam_gcn_amd.models.ctrgcn import Model
+    from tam_gcn_amd.optim import FusedSGD
+    from tam_gcn_amd.training import CapturedStep
+    m = Model(num_class=60, num_point=25, num_person=2, graph='graph.ntu_rgb_d.Graph', graph_args=dict(labeling_mode='spatial'))
+    fill_state_(m.state_dict(), seed=0)
+    m = m.to(DEV).train()
+    arena = ParamArena(m)
+    bucket = arena.grad_bucket()
+    opt = FusedSGD(arena, bucket, lr=0.01, momentum=0.9, nesterov=True, weight_decay=1e-4)
+    x, y = make_input((batch, 3, W, 25, 2), 4).to(DEV), make_labels(batch, 60, 5).to(DEV)
+    return CapturedStep(m, CrossEntropyLoss(), opt, arena, bucket, x, y)
+
+
+def time_resize(batches=200, steps=10):
+    import numpy as np
+    import torch
+    import clip_resize_ref as R
+    from tam_gcn_amd import ops
+    from tam_gcn_amd.feeder.clip_feeder import Feeder
+    from tam_gcn_amd.feeder.feeder_nucla_gcn import GraphedBatch
+    torch.manual_seed(0)
+    batch, n, shape, W, p, min_crop, theta = 128, 2048, (3, 300, 25, 2), 64, (0.5, 1.0), 64, 0.3
+    data = _data(n, shape)
+    labels = np.arange(n) % 60
+    perm = torch.randperm(n, device=DEV)
+    perm_host = perm.cpu().numpy()
+    n_pos = n - batch + 1
+    print(f'{batch} x {shape} of a split of {n} clips, W = {W}, p_interval = {list(p)}, min_crop = {min_crop}; {batches} batches per device leg, '
+          f'{HOST_BATCHES} per host leg, 3 repeats, legs alternated')
+    feeders = {}
+    for rot in (True, False):
+        fd = Feeder(None, None, data=data, labels=labels, window_size=W, p_interval=list(p), min_crop=min_crop, random_rot=rot,
+                    rot_theta=theta, device=DEV, seed=1)
+        feeders[rot] = fd
+        gb = GraphedBatch(fd, batch)
+        ext, flags = fd._extent_cpu.astype(np.int64), fd.crop_flags
+        legs = {'host torch pipeline + copy': lambda i: _host_resize_batch(R, data, ext, perm_host[(i * batch) % n_pos:][:batch], i, W, flags, p, min_crop, theta),
+                'batch_device eager': lambda i: fd.batch_device(perm[(i * batch) % n_pos:][:batch]),
+                'GraphedBatch replay': lambda i: gb(perm[(i * batch) % n_pos:][:batch])}
+        print(f'rotation {"on" if rot else "off"}')
+        ms = {name: [] for name in legs}
+        for rep in range(3):
+            for name, fn in legs.items():
+                k = HOST_BATCHES if name.startswith('host') else batches
+                _timed(fn, 1 if name.startswith('host') else 5)
+                ms[name].append(1e3 * _timed(fn, k))
+                print(f'  repeat {rep}: {name:26s} {ms[name][-1]:10.4f} ms/batch')
+        for name in list(legs)[1:]:
+            print(f'  {name}: slowest repeat {max(ms[name]):.4f} ms against the host leg\'s fastest {min(ms["host torch pipeline + copy"]):.3f} ms')
+        ids = perm[:batch].contiguous()
+        crop, _, rmat, _ = ops.clip_crop_draw(fd._extent, ids, fd._rng.clone(), flags, p[0], p[1], min_crop, theta)
+        us = _alone(lambda: ops.clip_resize(fd._raw, ids, crop, W, rmat), batches)
+        nbytes = _resize_bytes(R, crop.cpu().numpy(), shape[0], W, shape[2] * shape[3])
+        print(f'  resize alone, {batches} launches in one graph: {us:.2f} us per launch, {nbytes / 1e6:.2f} MB needed -> {nbytes / us / 1e6:.3f} TB/s '
+              f'(launch gaps included)')
+    # the yardstick: clip_transform's centre crop of the same split to the same window, measured the same way
+    fc = _feeder(data, W, 0)
+    ids = perm[:batch].contiguous()
+    plan, _, _, _, _ = ops.clip_draw(fc._extent, ids, fc._rng.clone(), 0, fc.T, fc.W, len(fc.node), None)
+    us = _alone(lambda: ops.clip_transform(fc._raw, ids, plan, fc.W, None, None), batches)
+    nbytes = _gather_bytes(plan.cpu().numpy(), shape[0], fc.T, fc.W, shape[2] * shape[3])
+    print(f'clip_transform (centre crop, no flags) alone, {batches} launches in one graph: {us:.2f} us per launch, {nbytes / 1e6:.2f} MB needed -> '
+          f'{nbytes / us / 1e6:.3f} TB/s (launch gaps included)')
+    # one captured training step of the NTU model fed by a GraphedBatch: this mode's 64-frame windows beside the padded 300 frames
+    fd300 = _feeder(data, -1, 0)
+    sets = {64: (_ntu_step(batch, 64), GraphedBatch(feeders[True], batch)), 300: (_ntu_step(batch, 300), GraphedBatch(fd300, batch))}
+    print(f'CapturedStep of the NTU model (CTR-GCN, 25 joints, 2 persons, batch {batch}, FusedSGD) fed by GraphedBatch; {steps} steps per leg, 3 repeats, legs alternated')
+    loss = {}
+    for rep in range(3):
+        for w, (train, gb) in sets.items():
+            def step(i, train=train, gb=gb):
+                loss[w] = train.step(*gb(perm[(i * batch) % n_pos:][:batch]))
+            _timed(step, 2)
+            print(f'  repeat {rep}: W = {w:3d}  {1e3 * _timed(step, steps):9.3f} ms/step (batch + step), last loss {float(loss[w]):.4f}')
+
+
 def trace(batches=50):
     import torch
     cache = {}
@@ -187,6 +325,8 @@ if __name__ == '__main__':
     mode = sys.argv[1] if len(sys.argv) > 1 else 'time'
     if mode == 'time':
         time_batches(*(int(a) for a in sys.argv[2:3]))
+    elif mode == 'resize':
+        time_resize(*(int(a) for a in sys.argv[2:4]))
     elif mode == 'trace':
         trace(*(int(a) for a in sys.argv[2:3]))
     elif mode == 'report':
