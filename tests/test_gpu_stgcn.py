@@ -1,5 +1,6 @@
 """-m gpu: the ST-GCN block and model on the HIP path (the spatial graph convolution runs on the fused
-CTRGC kernels with a static topology) against the CPU oracle and the vectors generated from the reference's models/stgcn.py."""
+CTRGC kernels with a static topology) against the CPU oracle and the vectors generated from the reference's models/stgcn.py.
+The strict, teacher-forced fp64 check of every block at fp32-rounding bars is tests/test_gpu_stgcn_blocks.py."""
 import os
 
 import numpy as np
