@@ -477,6 +477,50 @@ int tamgcn_head_fc_bwd(const float* dlogits, const float* pooled, const float* W
 int tamgcn_ce_fwd(const float* logits, const long long* labels, int N, int K, float* loss, float* g, void* stream);
 int tamgcn_ce_bwd(const float* g, const float* dloss, int N, int K, float* dlogits, void* stream);
 
+/* ---- the same loss with torch.nn.CrossEntropyLoss's options (added in ABI 401 without a version bump; csrc/celoss.hip) ----
+ * Notation per row n: logp = l - lse(l), p = softmax(l), w_k the class weight (1 when weight is NULL), Wsum = sum_k w_k,
+ * eps = label_smoothing.  Exactly one of labels / probs is given.
+ *   labels (N) int64   a row is KEPT iff labels[n] != ignore_index (any integer, a valid class id included; that class still
+ *                      takes part in the other rows' smoothing sums).
+ *                        L_n = (1 - eps) w_y (-logp_y) + (eps / K) sum_k w_k (-logp_k);   0 on ignored rows
+ *                        dL_n/dl_j = p_j [(1 - eps) w_y + (eps / K) Wsum] - (1 - eps) w_y [j = y] - (eps / K) w_j;   exactly 0 on ignored rows
+ *                      eps = 0 does not evaluate the smoothing sum (no 0 * inf).  'mean' divides both by W = sum over the kept
+ *                      rows of w_y, with or without weights and smoothing: no kept row, or kept weights that sum to 0, give NaN.
+ *                      A label outside [0, K) that is not ignore_index follows tamgcn_ce_fwd: the reduced loss is NaN, with 'none'
+ *                      that row's loss is NaN, that row of g is 0, the row counts nothing towards W and nothing outside the
+ *                      row is touched.
+ *   probs (N, K) fp32  t' = (1 - eps) t + eps / K;  L_n = -sum_k w_k t'_k logp_k;  dL_n/dl_j = p_j sum_k w_k t'_k - w_j t'_j;
+ *                      'mean' divides by N; ignore_index plays no part.
+ *   reduction          TAMGCN_CE_MEAN: loss[0] = sum_n L_n / W;  TAMGCN_CE_SUM: loss[0] = sum_n L_n;  TAMGCN_CE_NONE: loss[n] = L_n.
+ *   g (N, K)           the final gradient for dloss = 1 (the division by W or N included).  The backward is one product per
+ *                      element: tamgcn_ce_bwd (g * dloss[0]) for 'mean' / 'sum', tamgcn_ce_opts_bwd_rows (g[n][k] * dloss[n]) for 'none'.
+ * One wave per row, lanes striding over k; the max and expf(l_k - max) in fp32, the shifted sum, lse, p, every weighted sum over
+ * k, the row loss and g's arithmetic in fp64 (lane partials in ascending k, then the xor butterfly 1, 2, .., 32), one rounding to
+ * fp32.  The sums
+ * over rows (the loss terms, W) are fp64 in a fixed order (thread t of 256 takes rows t, t + 256, ..; tree): no floating-point
+ * atomics, two runs are bit-equal.  W is computed on the device from the labels of the launch at hand, so a graph replay with
+ * other labels is normalised by its own W.  Launches: 'none' one; 'mean' / 'sum' two (rows, then one workgroup that reduces).
+ * workspace: tamgcn_ce_opts_workspace_bytes(d) bytes of device memory (8 N for 'mean' / 'sum', 0 for 'none': NULL is taken then),
+ * 8-byte aligned, overwritten by every call.  _workspace_bytes returns -1 for a descriptor _fwd would reject.
+ * Rejected before any launch, with the entry point and the offending value in tamgcn_last_error(): null pointers, both or
+ * neither of labels / probs, N or K < 1, label_smoothing outside [0, 1], an unknown reduction, N * K >= 2^31. */
+#define TAMGCN_CE_MEAN 0
+#define TAMGCN_CE_SUM 1
+#define TAMGCN_CE_NONE 2
+typedef struct tamgcn_ce_desc {
+    const float* logits;            /* (N, K) */
+    const long long* labels;        /* (N) class indices, or NULL */
+    const float* probs;             /* (N, K) class probabilities, or NULL */
+    const float* weight;            /* (K) class weights, or NULL */
+    long long ignore_index;
+    double label_smoothing;
+    int reduction;                  /* TAMGCN_CE_* */
+    int N, K;
+} tamgcn_ce_desc;
+long long tamgcn_ce_opts_workspace_bytes(const tamgcn_ce_desc* d);
+int tamgcn_ce_opts_fwd(const tamgcn_ce_desc* d, float* loss, float* g, void* workspace, void* stream);
+int tamgcn_ce_opts_bwd_rows(const float* g, const float* dloss, int N, int K, float* dlogits, void* stream);
+
 /* ---- score-level ensemble of the evaluation scripts ----
  * fused (N, K) = sum_s weights[s] * scores[s]  (softmax = 0: reference ensemble/ensemble_resnet_ctrgcn.py:50-54, score_a + alpha * score_b)
  *             or sum_s weights[s] * softmax_k(scores[s])  (softmax = 1: ensemble/ensemble_ctrgcn_resnet_eval.py:99-106);

@@ -142,6 +142,11 @@ class OptimDesc(C.Structure):
                 ('beta1', C.c_double), ('beta2', C.c_double)]
 
 
+class CeDesc(C.Structure):
+    _fields_ = [('logits', C.c_void_p), ('labels', C.c_void_p), ('probs', C.c_void_p), ('weight', C.c_void_p),
+                ('ignore_index', C.c_longlong), ('label_smoothing', C.c_double), ('reduction', C.c_int), ('N', C.c_int), ('K', C.c_int)]
+
+
 class GradGuard(C.Structure):
     _fields_ = [('max_norm', C.c_float), ('skip_nonfinite', C.c_int), ('partial', C.c_void_p), ('n_partial', C.c_int),
                 ('stat', C.c_void_p), ('skipped', C.c_void_p)]
@@ -220,6 +225,9 @@ SIGNATURES = {
     'tamgcn_score_fuse': (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     'tamgcn_ce_fwd': (_i, [_p, _p, _i, _i, _p, _p, _p]),
     'tamgcn_ce_bwd': (_i, [_p, _p, _i, _i, _p, _p]),
+    'tamgcn_ce_opts_workspace_bytes': (_ll, [C.POINTER(CeDesc)]),
+    'tamgcn_ce_opts_fwd': (_i, [C.POINTER(CeDesc), _p, _p, _p, _p]),
+    'tamgcn_ce_opts_bwd_rows': (_i, [_p, _p, _i, _i, _p, _p]),
     'tamgcn_eval_accumulate': (_i, [_p, _p, _p, _i, _i, _i, _p, C.POINTER(C.c_int), _i, _ll, _ll, _p, _p, _p, _p, _p]),
     'tamgcn_score_sweep': (_i, [_p, _p, C.POINTER(C.c_float), _i, _i, _i, _i, _p, _p, _p]),
     'tamgcn_stream_derive': (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _p]),

@@ -995,15 +995,47 @@ class CrossEntropyFn(_Fn):
 
 
 class CrossEntropyLoss(torch.nn.Module):
-    """Drop-in for the ``nn.CrossEntropyLoss()`` the reference's processors build (default arguments: mean reduction, no
-    class weights, no label smoothing, no ignore_index hits): two HIP launches instead of four aten kernels."""
+    """``nn.CrossEntropyLoss`` on the device for (N, K) fp32 logits, with torch's arguments and semantics: ``weight`` (K,) fp32 class
+    weights (a buffer: ``.to(device)`` moves it), ``ignore_index`` (any integer), ``reduction`` 'mean' | 'sum' | 'none',
+    ``label_smoothing`` in [0, 1]; the target is (N,) int64 class indices or (N, K) fp32 class probabilities (which receive no
+    gradient).  'mean' over class indices divides by the sum of the kept rows' class weights, computed on the device from the
+    labels at hand, so a graph replay with other labels is normalised by its own sum.
 
-    def forward(self, logits, labels):
-        if logits.dim() != 2 or labels.dim() != 1 or labels.dtype != torch.int64 or logits.dtype != torch.float32:
-            raise RuntimeError('tam_gcn_amd.CrossEntropyLoss: expected (N, K) fp32 logits and (N,) int64 class indices')
-        if not logits.is_cuda:
+    With default arguments and class indices this is the ``nn.CrossEntropyLoss()`` the reference's processors build, on the two
+    launches of ``torch.ops.tamgcn.cross_entropy``, unchanged; anything else runs ``torch.ops.tamgcn.cross_entropy_opts`` (one wave
+    per row, fp64 sums in a fixed order; include/tamgcn.h).  A label outside [0, K) other than ``ignore_index`` makes the loss
+    NaN and zeroes that row's gradient where torch raises a device assert."""
+
+    def __init__(self, weight=None, ignore_index=-100, reduction='mean', label_smoothing=0.0):
+        super().__init__()
+        if reduction not in ('mean', 'sum', 'none'):
+            raise ValueError(f"tam_gcn_amd.CrossEntropyLoss: unknown reduction {reduction!r} (expected 'mean', 'sum' or 'none')")
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError(f'tam_gcn_amd.CrossEntropyLoss: label_smoothing = {label_smoothing} outside [0, 1]')
+        if weight is not None and (not isinstance(weight, torch.Tensor) or weight.dim() != 1 or weight.dtype != torch.float32):
+            raise ValueError('tam_gcn_amd.CrossEntropyLoss: weight must be a (K,) fp32 tensor')
+        self.register_buffer('weight', weight)
+        self.ignore_index, self.reduction, self.label_smoothing = int(ignore_index), reduction, float(label_smoothing)
+
+    def forward(self, logits, target):
+        if logits.dim() != 2 or logits.dtype != torch.float32:
+            raise RuntimeError(f'tam_gcn_amd.CrossEntropyLoss: expected (N, K) fp32 logits, got {tuple(logits.shape)} {logits.dtype}')
+        index = target.dtype == torch.int64
+        if not ((index and tuple(target.shape) == (logits.shape[0],)) or
+                (target.dtype == torch.float32 and tuple(target.shape) == tuple(logits.shape))):
+            raise RuntimeError('tam_gcn_amd.CrossEntropyLoss: expected (N, K) fp32 logits and (N,) int64 class indices or (N, K) fp32 '
+                               f'class probabilities, got a target {tuple(target.shape)} {target.dtype}')
+        if not logits.is_cuda or not target.is_cuda:
             raise RuntimeError('tam_gcn_amd: the loss runs on MI355X only (got a CPU tensor); there is no CPU fallback')
-        return torch.ops.tamgcn.cross_entropy(logits, labels)[0]        # tam_gcn_amd.torch_ops
+        if target.requires_grad:
+            raise RuntimeError('tam_gcn_amd.CrossEntropyLoss: the target receives no gradient (detach the class probabilities)')
+        w = self.weight
+        if w is not None and (tuple(w.shape) != (logits.shape[1],) or w.dtype != torch.float32 or w.device != logits.device):
+            raise RuntimeError(f'tam_gcn_amd.CrossEntropyLoss: weight must be ({logits.shape[1]},) fp32 on {logits.device}, got '
+                               f'{tuple(w.shape)} {w.dtype} on {w.device}')
+        if index and w is None and self.ignore_index == -100 and self.reduction == 'mean' and self.label_smoothing == 0.0:
+            return torch.ops.tamgcn.cross_entropy(logits, target)[0]        # tam_gcn_amd.torch_ops
+        return torch.ops.tamgcn.cross_entropy_opts(logits, target, w, self.ignore_index, self.label_smoothing, self.reduction)[0]
 
 
 # ===========================================================================

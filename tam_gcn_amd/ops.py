@@ -1281,6 +1281,39 @@ def ce_bwd(g, dloss):
     return dl
 
 
+CE_REDUCTIONS = {'mean': 0, 'sum': 1, 'none': 2}          # include/tamgcn.h TAMGCN_CE_*
+
+
+def ce_opts_fwd(logits, target, weight, ignore_index, label_smoothing, reduction):
+    """logits (N, K) fp32; target (N,) int64 class indices or (N, K) fp32 class probabilities; weight (K,) fp32 | None;
+    reduction a key of CE_REDUCTIONS -> loss (() or (N,)), g (N, K): tamgcn_ce_opts_fwd, one or two launches on the current
+    stream, the workspace from torch's allocator."""
+    N, K = logits.shape
+    d = _lib.CeDesc()
+    d.logits, d.weight = _ptr(logits), _ptr(weight)
+    if target.dtype == torch.int64:
+        d.labels = _ptr(target)
+    else:
+        d.probs = _ptr(target)
+    d.ignore_index, d.label_smoothing, d.reduction, d.N, d.K = int(ignore_index), float(label_smoothing), CE_REDUCTIONS[reduction], N, K
+    nbytes = _lib_().tamgcn_ce_opts_workspace_bytes(C.byref(d))
+    if nbytes < 0:
+        _lib.check(-1, 'tamgcn_ce_opts_workspace_bytes')
+    ws = torch.empty(nbytes // 8, device=logits.device, dtype=torch.float64) if nbytes else None
+    loss = torch.empty((N,) if reduction == 'none' else (), device=logits.device, dtype=torch.float32)
+    g = torch.empty_like(logits)
+    _lib.check(_lib_().tamgcn_ce_opts_fwd(C.byref(d), _ptr(loss), _ptr(g), _ptr(ws), _stream()), 'tamgcn_ce_opts_fwd')
+    return loss, g
+
+
+def ce_opts_bwd_rows(g, dloss):
+    """dlogits[n][k] = g[n][k] * dloss[n]"""
+    N, K = g.shape
+    dl = torch.empty_like(g)
+    _lib.check(_lib_().tamgcn_ce_opts_bwd_rows(_ptr(g), _ptr(dloss), N, K, _ptr(dl), _stream()), 'tamgcn_ce_opts_bwd_rows')
+    return dl
+
+
 def _optim_desc(fn, p, g, s0, s1, lr, step, scal, mode, momentum, dampening, nesterov, weight_decay, beta1, beta2, eps):
     for name, t in (('p', p), ('g', g), ('s0', s0), ('s1', s1), ('scal', scal)):
         if t is not None and t.dtype != torch.float32:

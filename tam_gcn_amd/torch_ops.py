@@ -7,6 +7,8 @@ backward is itself a registered op:
     tamgcn::ctrgc(x, A, alpha, w1, b1, w2, b2, w3, b3, w4, b4) -> y          reference models/ctrgcn.py:172-177
     tamgcn::ctrgc_backward(dy, x, A, alpha, w1, ..., b4) -> 11 gradients
     tamgcn::cross_entropy(logits, labels) -> (loss, g);  tamgcn::cross_entropy_backward(g, dloss) -> dlogits
+    tamgcn::cross_entropy_opts(logits, target, weight | None, ignore_index, label_smoothing, reduction) -> (loss, g);
+    tamgcn::cross_entropy_opts_backward(g, dloss, reduction) -> dlogits       torch.nn.CrossEntropyLoss's options
     tamgcn::pointwise_conv(x, w, b) -> y;  tamgcn::pointwise_conv_backward(dy, x, w) -> (dx, dw, db)
     tamgcn::head(x, W, b, M) -> logits;  tamgcn::head_backward(dlogits, x, W, M) -> (dx, dW, db)        models/ctrgcn.py:343-348
     tamgcn::head_pooled(x, rowmean, W, b, M): the same with the row means of x already taken by the producer of x
@@ -28,6 +30,8 @@ The TRAINING block-level nodes (unit_gcn / MultiScale_TemporalConv / TCN_GCN_uni
 BatchNorm running statistics in place, keep ~20 intermediate tensors between forward and backward and take their
 configuration from the nn.Module; the modules ``CTRGC``, ``CrossEntropyLoss``, the ST-GCN per-position classifier and the
 model heads call the registered ops."""
+from typing import Optional
+
 import torch
 from torch import Tensor
 
@@ -139,6 +143,45 @@ def _ce_bwd(ctx, dloss, dg):
 
 
 cross_entropy.register_autograd(_ce_bwd, setup_context=_ce_setup)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# cross-entropy with torch's options: class weights, ignore_index, label smoothing, the three reductions; target = class
+# indices (N,) int64 or class probabilities (N, K) fp32.  g is the final gradient for dloss = 1.
+# ---------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op('tamgcn::cross_entropy_opts', mutates_args=())
+def cross_entropy_opts(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, label_smoothing: float,
+                       reduction: str) -> tuple[Tensor, Tensor]:
+    return ops.ce_opts_fwd(_c(logits), _c(target), None if weight is None else _c(weight), ignore_index, label_smoothing, reduction)
+
+
+@cross_entropy_opts.register_fake
+def _(logits, target, weight, ignore_index, label_smoothing, reduction):
+    return logits.new_empty((logits.shape[0],) if reduction == 'none' else ()), torch.empty_like(logits)
+
+
+@torch.library.custom_op('tamgcn::cross_entropy_opts_backward', mutates_args=())
+def cross_entropy_opts_backward(g: Tensor, dloss: Tensor, reduction: str) -> Tensor:
+    dloss = dloss.to(torch.float32).contiguous()
+    return ops.ce_opts_bwd_rows(_c(g), dloss) if reduction == 'none' else ops.ce_bwd(_c(g), dloss)
+
+
+@cross_entropy_opts_backward.register_fake
+def _(g, dloss, reduction):
+    return torch.empty_like(g)
+
+
+def _ce_opts_setup(ctx, inputs, output):
+    ctx.reduction = inputs[5]
+    ctx.save_for_backward(output[1])
+
+
+def _ce_opts_bwd(ctx, dloss, dg):
+    (g,) = ctx.saved_tensors
+    return torch.ops.tamgcn.cross_entropy_opts_backward(g, dloss, ctx.reduction), None, None, None, None, None
+
+
+cross_entropy_opts.register_autograd(_ce_opts_bwd, setup_context=_ce_opts_setup)
 
 
 # ---------------------------------------------------------------------------------------------------------------
