@@ -21,13 +21,13 @@
 // Per (n, c) the aggregation moves 3*T*V*4 (x3) + T*V*4 (y) + 48 KB (E) bytes for 2*T*V*3V flops: 24 FLOP/B at V = 64,
 // right at the fp32 ridge (157 TFLOP/s / 8 TB/s = 20): both roofs ~5 ms for 256 clips x 256 channels x T = 512.
 //
-// LDS images.  A-type operands (rows = MFMA row index i, contraction along the row) use pitch V + 2 (16 rows x 2 k hit 32
-// distinct banks with ds_read_b32); B-type operands of [k][j] form use pitch == 16 (mod 32).
-#include "common.h"
+// The three streaming kernels (ctrgc_agg_fwd, ctrgc_agg_bwd, ctrgc_de_acc_mfma) are the bodies of ctrgc_stream_body.h under the
+// compile-time policy TlGeo<V>, for V in {20, 25, 32, 64}; vgen.hip runs the same bodies with V a kernel argument.  The LDS
+// images, the wave map and the chunk loop are described there; this file keeps their __global__ functions and dispatch, the
+// E builder and the tail.
+#include "ctrgc_stream_body.h"
 
 namespace {
-
-constexpr int TL_BT = 32;            // frames per chunk of the streaming kernels
 
 // ---------------------------------------------------------------------------------------------------------------
 // E for (n, s, rows u0..u0+UT-1), every channel
@@ -86,366 +86,35 @@ __global__ __launch_bounds__(512) void ctrgc_E_tiled_kernel(const ETArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The three streaming kernels below are generic in (V, VP): V joints in HBM, VP = V rounded up to a multiple of 16 in LDS
-// (zero padding), so that skeletons that do not tile into 16x16 MFMA shapes run on the same code: NTU's V = 25 as VP = 32
-// (78 % of the matrix work is real; the kernels are HBM-bound).  Rows of V floats need no alignment (16-byte accesses from
-// dword-aligned addresses run at full rate on gfx950, tools/probes/unaligned_probe.hip); a row's last 16-byte piece may read
-// <= 12 bytes into the next row: x3 / E / dy come from the ops' allocator, which keeps that slack behind every tensor.
+// The three streaming kernels: the body fragments of ctrgc_stream_body.h under the compile-time policy TlGeo<V>, pasted into
+// the __global__ functions (the device code is, instruction for instruction, what these kernels were with a text of their own:
+// profiles/ctrgc_stream_merge_resources.txt).  They are generic in
+// (V, VP): V joints in HBM, VP = V rounded up to a multiple of 16 in LDS (zero padding), so that skeletons that do not tile
+// into 16x16 MFMA shapes run on the same code: NTU's V = 25 as VP = 32 (78 % of the matrix work is real; the kernels are
+// HBM-bound).
 // ---------------------------------------------------------------------------------------------------------------
-template <int V> struct TlGeo {
-    static constexpr int VP = (V + 15) & ~15;          // joints in LDS
-    static constexpr int PE = VP + 2;                  // A-type pitch
-    static constexpr int K4 = (V + 3) / 4;             // contraction steps over joints (pads are zero)
-    static constexpr int NUT = VP / 16;                // 16-wide joint tiles
-    static constexpr bool AL = (V % 4) == 0;
-};
-
-// float4 of a contiguous [rows][V] run starting at flat index f -> LDS image with row pitch P (rows of V real + zero pads)
-template <int V>
-__device__ __forceinline__ void scatter4(float* img, int P, int f, const float4& t) {
-    if constexpr ((V & 3) == 0) {
-        const int r = f / V, c = f - r * V;
-        float2* d = reinterpret_cast<float2*>(img + r * P + c);
-        d[0] = make_float2(t.x, t.y);
-        d[1] = make_float2(t.z, t.w);
-    } else {
-        const float vals[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const int r = (f + k) / V, c = (f + k) - r * V; img[r * P + c] = vals[k]; }
-    }
-}
-
-// E_c of every subset -> LDS, rows u (TRANSPOSE = false: Es[s][u][v]) or rows v (true: Es[s][v][u]), pitch VP + 2, pads zero
-template <int V, int ST, bool TRANSPOSE>
-__device__ __forceinline__ void stage_E(const float* __restrict__ Eg, int Cout, int n, int c, float* Es) {
-    using G = TlGeo<V>;
-    constexpr int VV = V * V, PE = G::PE, VP = G::VP;
-    if constexpr (VP != V) {
-        for (int e = threadIdx.x; e < ST * VP * PE; e += 256) Es[e] = 0.f;
-        __syncthreads();
-    }
-    if constexpr (G::AL) {
-        constexpr int NV4 = ST * VV / 4, NL = (NV4 + 255) / 256;
-        float4 t[NL];
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int e = threadIdx.x + i * 256, ec = e < NV4 ? e : 0, s = ec / (VV / 4), r = ec - s * (VV / 4);
-            t[i] = reinterpret_cast<const float4*>(Eg + (((long long)n * ST + s) * Cout + c) * VV)[r];
-        }
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int e = threadIdx.x + i * 256, s = e / (VV / 4), r = e - s * (VV / 4);
-            if (e < NV4) {
-                const int u = (r * 4) / V, v = (r * 4) - u * V;
-                if constexpr (!TRANSPOSE) {
-                    float2* d = reinterpret_cast<float2*>(Es + (s * VP + u) * PE + v);
-                    d[0] = make_float2(t[i].x, t[i].y);
-                    d[1] = make_float2(t[i].z, t[i].w);
-                } else {
-                    float* d = Es + (s * VP + v) * PE + u;
-                    d[0] = t[i].x; d[PE] = t[i].y; d[2 * PE] = t[i].z; d[3 * PE] = t[i].w;
-                }
-            }
-        }
-    } else {
-        constexpr int NE = ST * VV, NL = (NE + 255) / 256;
-        float t[NL];
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int e = threadIdx.x + i * 256, ec = e < NE ? e : 0, s = ec / VV, r = ec - s * VV;
-            t[i] = Eg[(((long long)n * ST + s) * Cout + c) * VV + r];
-        }
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int e = threadIdx.x + i * 256, s = e / VV, r = e - s * VV;
-            if (e < NE) {
-                const int u = r / V, v = r - u * V;
-                Es[TRANSPOSE ? (s * VP + v) * PE + u : (s * VP + u) * PE + v] = t[i];
-            }
-        }
-    }
-}
-
-// aggregation, forward: workgroup = (n, c)
 template <int V, int ST>
 __global__ __launch_bounds__(256, 2) void ctrgc_agg_fwd_kernel(int N, int Cout, int T, const float* __restrict__ x3, const float* __restrict__ E,
                                                                float* __restrict__ y, float* __restrict__ stats_part) {
     using G = TlGeo<V>;
-    constexpr int PE = G::PE, VP = G::VP, UW = G::NUT / 2, BT = TL_BT, CH4 = BT * V / 4, NPF = (ST * CH4 + 255) / 256;
-    static_assert(G::NUT % 2 == 0 && (BT * V) % 4 == 0, "tile geometry");
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ float red[2][4];
-    float* Es = smem;                         // [ST][VP][PE]
-    float* Xs = Es + ST * VP * PE;            // [ST][BT][PE]
-    const int n = blockIdx.x / Cout, c = blockIdx.x - n * Cout;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kq = lane >> 4;
-    const int tt = wave >> 1, ub = (wave & 1) * UW;
-    const long long TV = (long long)T * V;
-    if constexpr (VP != V) for (int e = tid; e < ST * BT * PE; e += 256) Xs[e] = 0.f;     // joint pads stay zero
-    stage_E<V, ST, false>(E, Cout, n, c, Es);
-
-    float4 pre[NPF];
-    auto prefetch = [&](int t0) {
-#pragma unroll
-        for (int i = 0; i < NPF; ++i) {
-            const int e = tid + i * 256, ec = e < ST * CH4 ? e : 0, s = ec / CH4, r = ec - s * CH4;
-            const bool ok = e < ST * CH4 && t0 + (r * 4) / V < T;
-            pre[i] = ok ? reinterpret_cast<const float4*>(x3 + (((long long)n * ST + s) * Cout + c) * TV + (long long)t0 * V)[r]
-                        : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    prefetch(0);
-    float s1 = 0.f, s2 = 0.f;
-    float* yrow = y + ((long long)n * Cout + c) * TV;
-    for (int t0 = 0; t0 < T; t0 += BT) {
-        __syncthreads();                      // previous chunk's MFMAs are done with Xs (first pass: E staged, pads zeroed)
-        const int valid = min(BT, T - t0) * V;   // a piece that starts inside the clip may run past its end: those floats belong to
-#pragma unroll                                   // the next row and must not enter the sum: cut per element
-        for (int i = 0; i < NPF; ++i) {
-            const int e = tid + i * 256, s = e / CH4, r = e - s * CH4;
-            if (e < ST * CH4) {
-                float4 t = pre[i];
-                if (r * 4 + 3 >= valid) { if (r * 4 + 0 >= valid) t.x = 0.f; if (r * 4 + 1 >= valid) t.y = 0.f; if (r * 4 + 2 >= valid) t.z = 0.f; t.w = 0.f; }
-                scatter4<V>(Xs + s * BT * PE, PE, r * 4, t);
-            }
-        }
-        __syncthreads();
-        if (t0 + BT < T) prefetch(t0 + BT);   // in flight under the MFMAs
-        f32x4 acc[UW];
-#pragma unroll
-        for (int u = 0; u < UW; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < ST; ++s) {
-            const float* ar = Xs + (s * BT + tt * 16 + j) * PE + kq;
-            const float* br = Es + (s * VP + ub * 16 + j) * PE + kq;
-#pragma unroll
-            for (int k4 = 0; k4 < G::K4; ++k4) {
-                const float av = ar[k4 * 4];
-#pragma unroll
-                for (int u = 0; u < UW; ++u) acc[u] = mfma16(av, br[u * 16 * PE + k4 * 4], acc[u]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int t = t0 + tt * 16 + kq * 4 + r;
-            if (t < T) {
-#pragma unroll
-                for (int u = 0; u < UW; ++u) {
-                    const int uu = (ub + u) * 16 + j;
-                    if (VP == V || uu < V) {
-                        const float v = acc[u][r];
-                        yrow[(long long)t * V + uu] = v;
-                        s1 += v;
-                        s2 = fmaf(v, v, s2);
-                    }
-                }
-            }
-        }
-    }
-    if (stats_part) {
-        s1 = wave_sum64(s1); s2 = wave_sum64(s2);
-        if (lane == 0) { red[0][wave] = s1; red[1][wave] = s2; }
-        __syncthreads();
-        if (tid < 2) stats_part[((long long)tid * Cout + c) * N + n] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
-    }
+    const G g{};
+#include "ctrgc_stream_agg_fwd.h"
 }
 
-// aggregation, backward w.r.t. x3: dx3_s[t][v] = sum_u dy[t][u] E_s[u][v]
 template <int V, int ST>
 __global__ __launch_bounds__(256, 2) void ctrgc_agg_bwd_kernel(int N, int Cout, int T, const SrcDev dy, const float* __restrict__ E,
                                                                float* __restrict__ dx3, float* __restrict__ db3_part) {
     using G = TlGeo<V>;
-    constexpr int PE = G::PE, VP = G::VP, VW = G::NUT / 2, BT = TL_BT, CH4 = BT * V / 4, NPF = (CH4 + 255) / 256;
-    static_assert(G::NUT % 2 == 0 && (BT * V) % 4 == 0, "tile geometry");
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ float red[ST][4];
-    float* Es = smem;                         // [ST][v][PE] (transposed)
-    float* Zs = Es + ST * VP * PE;            // [BT][PE]
-    const int n = blockIdx.x / Cout, c = blockIdx.x - n * Cout;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kq = lane >> 4;
-    const int tt = wave >> 1, vb = (wave & 1) * VW;
-    const long long TV = (long long)T * V;
-    if constexpr (VP != V) for (int e = tid; e < BT * PE; e += 256) Zs[e] = 0.f;
-    stage_E<V, ST, true>(E, Cout, n, c, Es);
-    const int ch = dy.coff + c;
-    const float c1 = dy.coef ? dy.coef[ch] : 1.f;
-    const float c2 = (dy.coef && dy.x2) ? dy.coef[dy.ctot + ch] : 0.f;
-    const float c0 = dy.coef ? dy.coef[2 * dy.ctot + ch] : 0.f;
-    const long long dyb = ((long long)n * dy.ctot + ch) * TV;
-
-    float4 p1[NPF], p2[NPF];
-    auto prefetch = [&](int t0) {
-#pragma unroll
-        for (int i = 0; i < NPF; ++i) {
-            const int r = tid + i * 256;
-            const bool ok = r < CH4 && t0 + (r * 4) / V < T;
-            p1[i] = ok ? reinterpret_cast<const float4*>(dy.x1 + dyb + (long long)t0 * V)[r] : make_float4(0.f, 0.f, 0.f, 0.f);
-            p2[i] = (ok && dy.x2) ? reinterpret_cast<const float4*>(dy.x2 + dyb + (long long)t0 * V)[r] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    prefetch(0);
-    float sb[ST];
-#pragma unroll
-    for (int s = 0; s < ST; ++s) sb[s] = 0.f;
-    for (int t0 = 0; t0 < T; t0 += BT) {
-        __syncthreads();
-        const int valid = min(BT, T - t0) * V;
-#pragma unroll
-        for (int i = 0; i < NPF; ++i) {
-            const int r = tid + i * 256;
-            if (r < CH4) {
-                float o[4] = {fmaf(c1, p1[i].x, fmaf(c2, p2[i].x, c0)), fmaf(c1, p1[i].y, fmaf(c2, p2[i].y, c0)),
-                              fmaf(c1, p1[i].z, fmaf(c2, p2[i].z, c0)), fmaf(c1, p1[i].w, fmaf(c2, p2[i].w, c0))};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {       // rows past T are zero (the prologue's constant must not leak in)
-                    if (dy.act == 1) o[k] = fmaxf(o[k], 0.f);
-                    if (r * 4 + k >= valid) o[k] = 0.f;
-                }
-                scatter4<V>(Zs, PE, r * 4, make_float4(o[0], o[1], o[2], o[3]));
-            }
-        }
-        __syncthreads();
-        if (t0 + BT < T) prefetch(t0 + BT);
-        f32x4 acc[ST][VW];
-#pragma unroll
-        for (int s = 0; s < ST; ++s)
-#pragma unroll
-            for (int v = 0; v < VW; ++v) acc[s][v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const float* ar = Zs + (tt * 16 + j) * PE + kq;
-#pragma unroll
-        for (int k4 = 0; k4 < G::K4; ++k4) {
-            const float av = ar[k4 * 4];
-#pragma unroll
-            for (int s = 0; s < ST; ++s)
-#pragma unroll
-                for (int v = 0; v < VW; ++v) acc[s][v] = mfma16(av, Es[(s * VP + (vb + v) * 16 + j) * PE + k4 * 4 + kq], acc[s][v]);
-        }
-#pragma unroll
-        for (int s = 0; s < ST; ++s) {
-            float* orow = dx3 + (((long long)n * ST + s) * Cout + c) * TV;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int t = t0 + tt * 16 + kq * 4 + r;
-                if (t < T) {
-#pragma unroll
-                    for (int v = 0; v < VW; ++v) {
-                        const int vv = (vb + v) * 16 + j;
-                        if (VP == V || vv < V) {
-                            orow[(long long)t * V + vv] = acc[s][v][r];
-                            sb[s] += acc[s][v][r];
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (db3_part) {
-#pragma unroll
-        for (int s = 0; s < ST; ++s) {
-            const float t = wave_sum64(sb[s]);
-            if (lane == 0) red[s][wave] = t;
-        }
-        __syncthreads();
-        if (tid < ST) db3_part[(long long)n * ST * Cout + tid * Cout + c] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
-    }
+    const G g{};
+#include "ctrgc_stream_agg_bwd.h"
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// dE_s[u][v] = sum_t dy[t][u] x3_s[t][v]: workgroup = (n, c)
-// ---------------------------------------------------------------------------------------------------------------
 template <int V, int ST>
 __global__ __launch_bounds__(256) void ctrgc_de_acc_mfma_kernel(int N, int Cout, int T, const float* __restrict__ x3, const SrcDev dy,
                                                                 float* __restrict__ dE) {
     using G = TlGeo<V>;
-    constexpr int VP = G::VP, P = VP + 16, NUT = G::NUT, UW = NUT < 4 ? NUT : 4, VWAVES = 4 / UW, VPW = NUT / VWAVES, BT = TL_BT;
-    constexpr int CH4 = BT * V / 4, NPX = (ST * CH4 + 255) / 256, NPY = (CH4 + 255) / 256, VV = V * V;
-    static_assert((BT * V) % 4 == 0, "tile geometry");
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Zs = smem;                         // [BT][P]      dy chunk (prologue applied)
-    float* Xs = Zs + BT * P;                  // [ST][BT][P]
-    const int n = blockIdx.x / Cout, c = blockIdx.x - n * Cout;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kq = lane >> 4;
-    const int ut = wave % UW, vb = (wave / UW) * VPW;
-    const long long TV = (long long)T * V;
-    const int ch = dy.coff + c;
-    const float c1 = dy.coef ? dy.coef[ch] : 1.f;
-    const float c2 = (dy.coef && dy.x2) ? dy.coef[dy.ctot + ch] : 0.f;
-    const float c0 = dy.coef ? dy.coef[2 * dy.ctot + ch] : 0.f;
-    const long long dyb = ((long long)n * dy.ctot + ch) * TV;
-    if constexpr (VP != V) for (int e = tid; e < (ST + 1) * BT * P; e += 256) smem[e] = 0.f;   // joint pads stay zero
-
-    float4 px[NPX], p1[NPY], p2[NPY];
-    auto prefetch = [&](int t0) {
-#pragma unroll
-        for (int i = 0; i < NPX; ++i) {
-            const int e = tid + i * 256, ec = e < ST * CH4 ? e : 0, s = ec / CH4, r = ec - s * CH4;
-            const bool ok = e < ST * CH4 && t0 + (r * 4) / V < T;
-            px[i] = ok ? reinterpret_cast<const float4*>(x3 + (((long long)n * ST + s) * Cout + c) * TV + (long long)t0 * V)[r]
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int i = 0; i < NPY; ++i) {
-            const int r = tid + i * 256;
-            const bool ok = r < CH4 && t0 + (r * 4) / V < T;
-            p1[i] = ok ? reinterpret_cast<const float4*>(dy.x1 + dyb + (long long)t0 * V)[r] : make_float4(0.f, 0.f, 0.f, 0.f);
-            p2[i] = (ok && dy.x2) ? reinterpret_cast<const float4*>(dy.x2 + dyb + (long long)t0 * V)[r] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    prefetch(0);
-    f32x4 acc[ST][VPW];
-#pragma unroll
-    for (int s = 0; s < ST; ++s)
-#pragma unroll
-        for (int v = 0; v < VPW; ++v) acc[s][v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int t0 = 0; t0 < T; t0 += BT) {
-        __syncthreads();
-        const int valid = min(BT, T - t0) * V;
-#pragma unroll
-        for (int i = 0; i < NPX; ++i) {
-            const int e = tid + i * 256, s = e / CH4, r = e - s * CH4;
-            if (e < ST * CH4) {
-                float4 t = px[i];
-                if (r * 4 + 3 >= valid) { if (r * 4 + 0 >= valid) t.x = 0.f; if (r * 4 + 1 >= valid) t.y = 0.f; if (r * 4 + 2 >= valid) t.z = 0.f; t.w = 0.f; }
-                if constexpr (G::AL) { const int tl = (r * 4) / V, v = (r * 4) - tl * V; *reinterpret_cast<float4*>(Xs + (s * BT + tl) * P + v) = t; }
-                else scatter4<V>(Xs + s * BT * P, P, r * 4, t);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NPY; ++i) {
-            const int r = tid + i * 256;
-            if (r < CH4) {
-                float o[4] = {fmaf(c1, p1[i].x, fmaf(c2, p2[i].x, c0)), fmaf(c1, p1[i].y, fmaf(c2, p2[i].y, c0)),
-                              fmaf(c1, p1[i].z, fmaf(c2, p2[i].z, c0)), fmaf(c1, p1[i].w, fmaf(c2, p2[i].w, c0))};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { if (dy.act == 1) o[k] = fmaxf(o[k], 0.f); if (r * 4 + k >= valid) o[k] = 0.f; }
-                const float4 t = make_float4(o[0], o[1], o[2], o[3]);
-                if constexpr (G::AL) { const int tl = (r * 4) / V, u = (r * 4) - tl * V; *reinterpret_cast<float4*>(Zs + tl * P + u) = t; }
-                else scatter4<V>(Zs, P, r * 4, t);
-            }
-        }
-        __syncthreads();
-        if (t0 + BT < T) prefetch(t0 + BT);
-#pragma unroll
-        for (int k4 = 0; k4 < BT / 4; ++k4) {
-            const float av = Zs[(k4 * 4 + kq) * P + ut * 16 + j];          // A[i = u][k = t]
-#pragma unroll
-            for (int s = 0; s < ST; ++s)
-#pragma unroll
-                for (int v = 0; v < VPW; ++v)
-                    acc[s][v] = mfma16(av, Xs[(s * BT + k4 * 4 + kq) * P + (vb + v) * 16 + j], acc[s][v]);   // B[k = t][j = v]
-        }
-    }
-#pragma unroll
-    for (int s = 0; s < ST; ++s) {
-        float* o = dE + (((long long)n * ST + s) * Cout + c) * VV;
-#pragma unroll
-        for (int v = 0; v < VPW; ++v)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int uu = ut * 16 + kq * 4 + r, vv = (vb + v) * 16 + j;
-                if (VP == V || (uu < V && vv < V)) o[uu * V + vv] = acc[s][v][r];
-            }
-    }
+    const G g{};
+#include "ctrgc_stream_de_acc.h"
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -630,11 +299,6 @@ __global__ __launch_bounds__(512) void ctrgc_de_tail_tiled_kernel(const TTArgs a
     }
 }
 
-template <int V>
-constexpr size_t agg_lds(int ST, bool bwd) {
-    return sizeof(float) * (size_t)(ST * TlGeo<V>::VP * TlGeo<V>::PE + (bwd ? 1 : ST) * TL_BT * TlGeo<V>::PE);
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -651,7 +315,7 @@ extern "C" int tamgcn_ctrgc_tiled_supported(int V) { return tiled_v_ok(V) ? 1 : 
 int tamgcn_ctrgc_tiled_lds_bytes(int S, int V, int R) {
     if (!tiled_v_ok(V) || !(S == 1 || S == 3) || R < 4 || R > 32 || R % 4) return -1;
     const int UT = 512 / V, RT = R <= 16 ? 1 : 2;
-    const size_t agg = sizeof(float) * (size_t)(S * V * (V + 2) + S * TL_BT * (V + 2));
+    const size_t agg = stream_agg_lds(V, S, false);
     const size_t tail = sizeof(float) * ((size_t)(R + 16) * (512 + 2) + 8 * 16 * RT * 16 + (size_t)R * (UT + V));
     const size_t et = sizeof(float) * ((size_t)R * (512 + 16) + (size_t)R * (UT + V));
     size_t m = agg > tail ? agg : tail;
@@ -699,14 +363,14 @@ extern "C" int tamgcn_ctrgc_tiled_agg_fwd(const tamgcn_ctrgc_desc* d, const floa
     if (tiled_common_check(d, "tamgcn_ctrgc_tiled_agg_fwd")) return -1;
     TG_CHECK(x3 && E && y, "tamgcn_ctrgc_tiled_agg_fwd: null pointer");
     bool launched = false;
-    TL_CASE(ctrgc_agg_fwd_kernel, 64, 3, agg_lds<64>(3, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
-    else TL_CASE(ctrgc_agg_fwd_kernel, 64, 1, agg_lds<64>(1, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
-    else TL_CASE(ctrgc_agg_fwd_kernel, 32, 3, agg_lds<32>(3, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
-    else TL_CASE(ctrgc_agg_fwd_kernel, 32, 1, agg_lds<32>(1, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
-    else TL_CASE(ctrgc_agg_fwd_kernel, 25, 3, agg_lds<25>(3, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
-    else TL_CASE(ctrgc_agg_fwd_kernel, 25, 1, agg_lds<25>(1, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
-    else TL_CASE(ctrgc_agg_fwd_kernel, 20, 3, agg_lds<20>(3, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
-    else TL_CASE(ctrgc_agg_fwd_kernel, 20, 1, agg_lds<20>(1, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
+    TL_CASE(ctrgc_agg_fwd_kernel, 64, 3, stream_agg_lds(TlGeo<64>::VP, 3, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
+    else TL_CASE(ctrgc_agg_fwd_kernel, 64, 1, stream_agg_lds(TlGeo<64>::VP, 1, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
+    else TL_CASE(ctrgc_agg_fwd_kernel, 32, 3, stream_agg_lds(TlGeo<32>::VP, 3, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
+    else TL_CASE(ctrgc_agg_fwd_kernel, 32, 1, stream_agg_lds(TlGeo<32>::VP, 1, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
+    else TL_CASE(ctrgc_agg_fwd_kernel, 25, 3, stream_agg_lds(TlGeo<25>::VP, 3, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
+    else TL_CASE(ctrgc_agg_fwd_kernel, 25, 1, stream_agg_lds(TlGeo<25>::VP, 1, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
+    else TL_CASE(ctrgc_agg_fwd_kernel, 20, 3, stream_agg_lds(TlGeo<20>::VP, 3, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
+    else TL_CASE(ctrgc_agg_fwd_kernel, 20, 1, stream_agg_lds(TlGeo<20>::VP, 1, false), d->N, d->Cout, d->T, x3, E, y, stats_part)
     TG_CHECK(launched, "tamgcn_ctrgc_tiled_agg_fwd: no instantiation for S=%d V=%d", d->S, d->V);
     TG_LAUNCH_CHECK("tamgcn_ctrgc_tiled_agg_fwd");
     return 0;
@@ -718,14 +382,14 @@ extern "C" int tamgcn_ctrgc_tiled_agg_bwd(const tamgcn_ctrgc_desc* d, const tamg
     TG_CHECK(dy->ctot >= dy->coff + d->Cout, "tamgcn_ctrgc_tiled_agg_bwd: dy has %d channels from %d, need %d", dy->ctot, dy->coff, d->Cout);
     const SrcDev dys = make_src(*dy);
     bool launched = false;
-    TL_CASE(ctrgc_agg_bwd_kernel, 64, 3, agg_lds<64>(3, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
-    else TL_CASE(ctrgc_agg_bwd_kernel, 64, 1, agg_lds<64>(1, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
-    else TL_CASE(ctrgc_agg_bwd_kernel, 32, 3, agg_lds<32>(3, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
-    else TL_CASE(ctrgc_agg_bwd_kernel, 32, 1, agg_lds<32>(1, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
-    else TL_CASE(ctrgc_agg_bwd_kernel, 25, 3, agg_lds<25>(3, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
-    else TL_CASE(ctrgc_agg_bwd_kernel, 25, 1, agg_lds<25>(1, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
-    else TL_CASE(ctrgc_agg_bwd_kernel, 20, 3, agg_lds<20>(3, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
-    else TL_CASE(ctrgc_agg_bwd_kernel, 20, 1, agg_lds<20>(1, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
+    TL_CASE(ctrgc_agg_bwd_kernel, 64, 3, stream_agg_lds(TlGeo<64>::VP, 3, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
+    else TL_CASE(ctrgc_agg_bwd_kernel, 64, 1, stream_agg_lds(TlGeo<64>::VP, 1, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
+    else TL_CASE(ctrgc_agg_bwd_kernel, 32, 3, stream_agg_lds(TlGeo<32>::VP, 3, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
+    else TL_CASE(ctrgc_agg_bwd_kernel, 32, 1, stream_agg_lds(TlGeo<32>::VP, 1, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
+    else TL_CASE(ctrgc_agg_bwd_kernel, 25, 3, stream_agg_lds(TlGeo<25>::VP, 3, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
+    else TL_CASE(ctrgc_agg_bwd_kernel, 25, 1, stream_agg_lds(TlGeo<25>::VP, 1, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
+    else TL_CASE(ctrgc_agg_bwd_kernel, 20, 3, stream_agg_lds(TlGeo<20>::VP, 3, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
+    else TL_CASE(ctrgc_agg_bwd_kernel, 20, 1, stream_agg_lds(TlGeo<20>::VP, 1, true), d->N, d->Cout, d->T, dys, E, dx3, db3_part)
     TG_CHECK(launched, "tamgcn_ctrgc_tiled_agg_bwd: no instantiation for S=%d V=%d", d->S, d->V);
     TG_LAUNCH_CHECK("tamgcn_ctrgc_tiled_agg_bwd");
     return 0;
@@ -737,15 +401,14 @@ extern "C" int tamgcn_ctrgc_tiled_de_acc(const tamgcn_ctrgc_desc* d, const tamgc
     TG_CHECK(dy->ctot >= dy->coff + d->Cout, "tamgcn_ctrgc_tiled_de_acc: dy has %d channels from %d, need %d", dy->ctot, dy->coff, d->Cout);
     const SrcDev dys = make_src(*dy);
     bool launched = false;
-#define TL_DE_LDS(VV_, SS_) (sizeof(float) * (size_t)((SS_ + 1) * TL_BT * (TlGeo<VV_>::VP + 16)))
-    TL_CASE(ctrgc_de_acc_mfma_kernel, 64, 3, TL_DE_LDS(64, 3), d->N, d->Cout, d->T, x3, dys, dE)
-    else TL_CASE(ctrgc_de_acc_mfma_kernel, 64, 1, TL_DE_LDS(64, 1), d->N, d->Cout, d->T, x3, dys, dE)
-    else TL_CASE(ctrgc_de_acc_mfma_kernel, 32, 3, TL_DE_LDS(32, 3), d->N, d->Cout, d->T, x3, dys, dE)
-    else TL_CASE(ctrgc_de_acc_mfma_kernel, 32, 1, TL_DE_LDS(32, 1), d->N, d->Cout, d->T, x3, dys, dE)
-    else TL_CASE(ctrgc_de_acc_mfma_kernel, 25, 3, TL_DE_LDS(25, 3), d->N, d->Cout, d->T, x3, dys, dE)
-    else TL_CASE(ctrgc_de_acc_mfma_kernel, 25, 1, TL_DE_LDS(25, 1), d->N, d->Cout, d->T, x3, dys, dE)
-    else TL_CASE(ctrgc_de_acc_mfma_kernel, 20, 3, TL_DE_LDS(20, 3), d->N, d->Cout, d->T, x3, dys, dE)
-    else TL_CASE(ctrgc_de_acc_mfma_kernel, 20, 1, TL_DE_LDS(20, 1), d->N, d->Cout, d->T, x3, dys, dE)
+    TL_CASE(ctrgc_de_acc_mfma_kernel, 64, 3, stream_de_lds(TlGeo<64>::VP, 3), d->N, d->Cout, d->T, x3, dys, dE)
+    else TL_CASE(ctrgc_de_acc_mfma_kernel, 64, 1, stream_de_lds(TlGeo<64>::VP, 1), d->N, d->Cout, d->T, x3, dys, dE)
+    else TL_CASE(ctrgc_de_acc_mfma_kernel, 32, 3, stream_de_lds(TlGeo<32>::VP, 3), d->N, d->Cout, d->T, x3, dys, dE)
+    else TL_CASE(ctrgc_de_acc_mfma_kernel, 32, 1, stream_de_lds(TlGeo<32>::VP, 1), d->N, d->Cout, d->T, x3, dys, dE)
+    else TL_CASE(ctrgc_de_acc_mfma_kernel, 25, 3, stream_de_lds(TlGeo<25>::VP, 3), d->N, d->Cout, d->T, x3, dys, dE)
+    else TL_CASE(ctrgc_de_acc_mfma_kernel, 25, 1, stream_de_lds(TlGeo<25>::VP, 1), d->N, d->Cout, d->T, x3, dys, dE)
+    else TL_CASE(ctrgc_de_acc_mfma_kernel, 20, 3, stream_de_lds(TlGeo<20>::VP, 3), d->N, d->Cout, d->T, x3, dys, dE)
+    else TL_CASE(ctrgc_de_acc_mfma_kernel, 20, 1, stream_de_lds(TlGeo<20>::VP, 1), d->N, d->Cout, d->T, x3, dys, dE)
     TG_CHECK(launched, "tamgcn_ctrgc_tiled_de_acc: no instantiation for S=%d V=%d", d->S, d->V);
     TG_LAUNCH_CHECK("tamgcn_ctrgc_tiled_de_acc");
     return 0;

@@ -1,6 +1,8 @@
-// CTRGC for ANY skeleton of 2 <= V <= 32 joints: the kernels of the V = 25 route (ctrgc.hip's E builder, ctrgc_tiled.hip's three
-// streaming kernels, ctrgc_de.hip's register-staged tail) with V as a kernel ARGUMENT.  Same arithmetic, same output tensors,
-// same partial-sum layouts, so the ops layer's fixed-order reductions serve both.
+// CTRGC for ANY skeleton of 2 <= V <= 32 joints: the kernels of the V = 25 route (ctrgc.hip's E builder, the three streaming
+// kernels, ctrgc_de.hip's register-staged tail) with V as a kernel ARGUMENT.  Same arithmetic, same output tensors, same
+// partial-sum layouts, so the ops layer's fixed-order reductions serve both.  The streaming kernels are not a copy:
+// ctrgc_stream_body.h holds their bodies once, ctrgc_tiled.hip instantiates them with the compile-time policy TlGeo<V> and this
+// file with the run-time policy VgGeo<VP>, and at V = 20, 25, 32 the two give the same words (tests/test_gpu_vgen_routes.py).
 //
 //   vgen_E_kernel               E[n,s,c,u,v] = alpha (W4_s tanh(p_u - q_v) + b4_s)[c] + A_s[u,v]   workgroup = (n, s), D in LDS
 //   vgen_agg_fwd_kernel<VP,ST>  y[n,c,t,u]     = sum_s sum_v x3_s[n,c,t,v] E_s[n,c,u,v]  + moment partials   workgroup = (n, c)
@@ -22,11 +24,10 @@
 // The tail keeps D = tanh(p_u - q_v) of every (u, v) in LDS (R * V * V floats: 131 KB at V = 32, R = 32), which leaves no room
 // for a 16-channel dE chunk of all V * V columns at the large end.  So the chunk is staged in column windows of W columns (W a
 // multiple of 16 chosen by the host from what D leaves free; one window wherever it fits, which is every V <= 25).
-#include "common.h"
+#include "ctrgc_stream_body.h"
 
 namespace {
 
-constexpr int VG_BT = 32;            // frames per chunk of the streaming kernels
 constexpr int VG_LDS_MAX = 160 * 1024 - 256;   // dynamic LDS a workgroup may ask for (static arrays of the kernels on top)
 
 __host__ __device__ constexpr int vg_pitch16(int n) { return ((n + 13) & ~15) + 2; }   // smallest p >= n with p % 16 == 2
@@ -97,349 +98,30 @@ __global__ __launch_bounds__(512) void vgen_E_kernel(const VgEArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// streaming kernels: shared pieces
-// ---------------------------------------------------------------------------------------------------------------
-template <int VP> struct VgGeo {
-    static constexpr int PE = VP + 2;                  // A-type pitch (16 rows x 2 k hit 32 distinct banks)
-    static constexpr int NUT = VP / 16;                // 16-wide joint tiles
-    static constexpr int JW = NUT >= 2 ? NUT / 2 : 1;  // joint tiles per wave of the aggregation kernels
-    static_assert(VP == 16 || VP == 32, "VP is 16 or 32");
-};
-
-// four consecutive floats of a contiguous [rows][V] run starting at flat index f -> LDS image with row pitch P
-__device__ __forceinline__ void vg_scatter4(float* img, int P, int V, float rcpV, int f, const float (&vals)[4]) {
-    int r = tg_rcp_div(f, rcpV), c = f - r * V;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        img[r * P + c] = vals[k];
-        if (++c == V) { c = 0; ++r; }
-    }
-}
-
-// E_c of every subset -> LDS, rows u (TRANSPOSE = false: Es[s][u][v]) or rows v (true: Es[s][v][u]), pitch VP + 2, pads zero.
-// The caller has zeroed the image and passed a barrier.
-template <int VP, int ST, bool TRANSPOSE>
-__device__ __forceinline__ void vg_stage_E(const float* __restrict__ Eg, int Cout, int V, float rcpV, int n, int c, float* Es) {
-    constexpr int PE = VgGeo<VP>::PE, NL = VP * VP / 256;
-    const int VV = V * V;
-#pragma unroll
-    for (int s = 0; s < ST; ++s) {
-        const float* g = Eg + (((long long)n * ST + s) * Cout + c) * VV;
-        float t[NL];
-#pragma unroll
-        for (int i = 0; i < NL; ++i) { const int e = threadIdx.x + i * 256; t[i] = g[e < VV ? e : 0]; }
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int e = threadIdx.x + i * 256;
-            if (e < VV) {
-                const int u = tg_rcp_div(e, rcpV), v = e - u * V;
-                Es[TRANSPOSE ? (s * VP + v) * PE + u : (s * VP + u) * PE + v] = t[i];
-            }
-        }
-    }
-}
-
-// the fused operand prologue of dy on four floats of a chunk: act(c1 x1 + c2 x2 + c0), zero from flat index `valid` on (frames
-// past T: the prologue's constant must not leak into them, and what a piece read past its row must not either)
-__device__ __forceinline__ void vg_prologue4(const float4& p1, const float4& p2, float c1, float c2, float c0, int act, int f, int valid,
-                                             float (&o)[4]) {
-    o[0] = fmaf(c1, p1.x, fmaf(c2, p2.x, c0)); o[1] = fmaf(c1, p1.y, fmaf(c2, p2.y, c0));
-    o[2] = fmaf(c1, p1.z, fmaf(c2, p2.z, c0)); o[3] = fmaf(c1, p1.w, fmaf(c2, p2.w, c0));
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (act == 1) o[k] = fmaxf(o[k], 0.f);
-        if (f + k >= valid) o[k] = 0.f;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// aggregation, forward: workgroup = (n, c)
+// streaming kernels: the body fragments of ctrgc_stream_body.h under the run-time policy VgGeo<VP>, pasted into the kernels
 // ---------------------------------------------------------------------------------------------------------------
 template <int VP, int ST>
 __global__ __launch_bounds__(256, 2) void vgen_agg_fwd_kernel(int N, int Cout, int T, int V, const float* __restrict__ x3, const float* __restrict__ E,
                                                               float* __restrict__ y, float* __restrict__ stats_part) {
     using G = VgGeo<VP>;
-    constexpr int PE = G::PE, JW = G::JW, BT = VG_BT, NPF = (ST * BT * VP / 4 + 255) / 256;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ float red[2][4];
-    float* Es = smem;                         // [ST][VP][PE]
-    float* Xs = Es + ST * VP * PE;            // [ST][BT][PE]
-    const int n = blockIdx.x / Cout, c = blockIdx.x - n * Cout;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kq = lane >> 4;
-    const bool active = G::NUT >= 2 || wave < 2;                   // VP = 16: two output tiles per chunk
-    const int tt = G::NUT >= 2 ? wave >> 1 : wave & 1, ub = G::NUT >= 2 ? (wave & 1) * JW : 0;
-    const int CH4 = BT * V / 4, K4 = (V + 3) / 4;
-    const long long TV = (long long)T * V;
-    const float rcpV = 1.f / (float)V;
-    for (int e = tid; e < ST * (VP + BT) * PE; e += 256) smem[e] = 0.f;     // joint pads stay zero
-    __syncthreads();
-    vg_stage_E<VP, ST, false>(E, Cout, V, rcpV, n, c, Es);
-
-    float4 pre[NPF];
-    auto prefetch = [&](int t0) {
-        const int valid = min(BT, T - t0) * V;
-#pragma unroll
-        for (int i = 0; i < NPF; ++i) {
-            const int e = tid + i * 256, s = (e >= CH4) + (e >= 2 * CH4), r = e - s * CH4;
-            const bool ok = e < ST * CH4 && r * 4 < valid;
-            pre[i] = ok ? reinterpret_cast<const float4*>(x3 + (((long long)n * ST + s) * Cout + c) * TV + (long long)t0 * V)[r]
-                        : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    prefetch(0);
-    float s1 = 0.f, s2 = 0.f;
-    float* yrow = y + ((long long)n * Cout + c) * TV;
-    for (int t0 = 0; t0 < T; t0 += BT) {
-        __syncthreads();                      // previous chunk's MFMAs are done with Xs (first pass: E staged)
-        const int valid = min(BT, T - t0) * V;
-#pragma unroll
-        for (int i = 0; i < NPF; ++i) {
-            const int e = tid + i * 256, s = (e >= CH4) + (e >= 2 * CH4), r = e - s * CH4;
-            if (e < ST * CH4) {
-                float o[4] = {pre[i].x, pre[i].y, pre[i].z, pre[i].w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) if (r * 4 + k >= valid) o[k] = 0.f;
-                vg_scatter4(Xs + s * BT * PE, PE, V, rcpV, r * 4, o);
-            }
-        }
-        __syncthreads();
-        if (t0 + BT < T) prefetch(t0 + BT);   // in flight under the MFMAs
-        if (active) {
-            f32x4 acc[JW];
-#pragma unroll
-            for (int u = 0; u < JW; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < ST; ++s) {
-                const float* ar = Xs + (s * BT + tt * 16 + j) * PE + kq;
-                const float* br = Es + (s * VP + ub * 16 + j) * PE + kq;
-                for (int k4 = 0; k4 < K4; ++k4) {
-                    const float av = ar[k4 * 4];
-#pragma unroll
-                    for (int u = 0; u < JW; ++u) acc[u] = mfma16(av, br[u * 16 * PE + k4 * 4], acc[u]);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int t = t0 + tt * 16 + kq * 4 + r;
-                if (t < T) {
-#pragma unroll
-                    for (int u = 0; u < JW; ++u) {
-                        const int uu = (ub + u) * 16 + j;
-                        if (uu < V) {
-                            const float v = acc[u][r];
-                            yrow[(long long)t * V + uu] = v;
-                            s1 += v;
-                            s2 = fmaf(v, v, s2);
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (stats_part) {
-        s1 = wave_sum64(s1); s2 = wave_sum64(s2);
-        if (lane == 0) { red[0][wave] = s1; red[1][wave] = s2; }
-        __syncthreads();
-        if (tid < 2) stats_part[((long long)tid * Cout + c) * N + n] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
-    }
+    const G g(V);
+#include "ctrgc_stream_agg_fwd.h"
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// aggregation, backward w.r.t. x3: dx3_s[t][v] = sum_u dy[t][u] E_s[u][v]
-// ---------------------------------------------------------------------------------------------------------------
 template <int VP, int ST>
 __global__ __launch_bounds__(256, 2) void vgen_agg_bwd_kernel(int N, int Cout, int T, int V, const SrcDev dy, const float* __restrict__ E,
                                                               float* __restrict__ dx3, float* __restrict__ db3_part) {
     using G = VgGeo<VP>;
-    constexpr int PE = G::PE, JW = G::JW, BT = VG_BT, NPF = (BT * VP / 4 + 255) / 256;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    __shared__ float red[ST][4];
-    float* Es = smem;                         // [ST][v][PE] (transposed)
-    float* Zs = Es + ST * VP * PE;            // [BT][PE]
-    const int n = blockIdx.x / Cout, c = blockIdx.x - n * Cout;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kq = lane >> 4;
-    const bool active = G::NUT >= 2 || wave < 2;
-    const int tt = G::NUT >= 2 ? wave >> 1 : wave & 1, vb = G::NUT >= 2 ? (wave & 1) * JW : 0;
-    const int CH4 = BT * V / 4, K4 = (V + 3) / 4;
-    const long long TV = (long long)T * V;
-    const float rcpV = 1.f / (float)V;
-    for (int e = tid; e < (ST * VP + BT) * PE; e += 256) smem[e] = 0.f;
-    __syncthreads();
-    vg_stage_E<VP, ST, true>(E, Cout, V, rcpV, n, c, Es);
-    const int ch = dy.coff + c;
-    const float c1 = dy.coef ? dy.coef[ch] : 1.f;
-    const float c2 = (dy.coef && dy.x2) ? dy.coef[dy.ctot + ch] : 0.f;
-    const float c0 = dy.coef ? dy.coef[2 * dy.ctot + ch] : 0.f;
-    const long long dyb = ((long long)n * dy.ctot + ch) * TV;
-
-    float4 p1[NPF], p2[NPF];
-    auto prefetch = [&](int t0) {
-        const int valid = min(BT, T - t0) * V;
-#pragma unroll
-        for (int i = 0; i < NPF; ++i) {
-            const int r = tid + i * 256;
-            const bool ok = r < CH4 && r * 4 < valid;
-            p1[i] = ok ? reinterpret_cast<const float4*>(dy.x1 + dyb + (long long)t0 * V)[r] : make_float4(0.f, 0.f, 0.f, 0.f);
-            p2[i] = (ok && dy.x2) ? reinterpret_cast<const float4*>(dy.x2 + dyb + (long long)t0 * V)[r] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    prefetch(0);
-    float sb[ST];
-#pragma unroll
-    for (int s = 0; s < ST; ++s) sb[s] = 0.f;
-    for (int t0 = 0; t0 < T; t0 += BT) {
-        __syncthreads();
-        const int valid = min(BT, T - t0) * V;
-#pragma unroll
-        for (int i = 0; i < NPF; ++i) {
-            const int r = tid + i * 256;
-            if (r < CH4) {
-                float o[4];
-                vg_prologue4(p1[i], p2[i], c1, c2, c0, dy.act, r * 4, valid, o);
-                vg_scatter4(Zs, PE, V, rcpV, r * 4, o);
-            }
-        }
-        __syncthreads();
-        if (t0 + BT < T) prefetch(t0 + BT);
-        if (active) {
-            f32x4 acc[ST][JW];
-#pragma unroll
-            for (int s = 0; s < ST; ++s)
-#pragma unroll
-                for (int v = 0; v < JW; ++v) acc[s][v] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            const float* ar = Zs + (tt * 16 + j) * PE + kq;
-            for (int k4 = 0; k4 < K4; ++k4) {
-                const float av = ar[k4 * 4];
-#pragma unroll
-                for (int s = 0; s < ST; ++s)
-#pragma unroll
-                    for (int v = 0; v < JW; ++v) acc[s][v] = mfma16(av, Es[(s * VP + (vb + v) * 16 + j) * PE + k4 * 4 + kq], acc[s][v]);
-            }
-#pragma unroll
-            for (int s = 0; s < ST; ++s) {
-                float* orow = dx3 + (((long long)n * ST + s) * Cout + c) * TV;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int t = t0 + tt * 16 + kq * 4 + r;
-                    if (t < T) {
-#pragma unroll
-                        for (int v = 0; v < JW; ++v) {
-                            const int vv = (vb + v) * 16 + j;
-                            if (vv < V) {
-                                orow[(long long)t * V + vv] = acc[s][v][r];
-                                sb[s] += acc[s][v][r];
-                            }
-                        }
-                    }
-                }
-            }
-        }
-    }
-    if (db3_part) {
-#pragma unroll
-        for (int s = 0; s < ST; ++s) {
-            const float t = wave_sum64(sb[s]);
-            if (lane == 0) red[s][wave] = t;
-        }
-        __syncthreads();
-        if (tid < ST) db3_part[(long long)n * ST * Cout + tid * Cout + c] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
-    }
+    const G g(V);
+#include "ctrgc_stream_agg_bwd.h"
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// dE_s[u][v] = sum_t dy[t][u] x3_s[t][v]: workgroup = (n, c)
-// VP = 32: wave -> (u tile = wave & 1, v tile = wave >> 1), every subset; VP = 16: wave s -> subset s
-// ---------------------------------------------------------------------------------------------------------------
 template <int VP, int ST>
 __global__ __launch_bounds__(256) void vgen_de_acc_kernel(int N, int Cout, int T, int V, const float* __restrict__ x3, const SrcDev dy,
                                                           float* __restrict__ dE) {
-    constexpr int P = VP + 16, BT = VG_BT, NPX = (ST * BT * VP / 4 + 255) / 256, NPY = (BT * VP / 4 + 255) / 256;
-    constexpr bool WIDE = VP == 32;
-    constexpr int NS = WIDE ? ST : 1;         // subsets a wave accumulates
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Zs = smem;                         // [BT][P]      dy chunk (prologue applied)
-    float* Xs = Zs + BT * P;                  // [ST][BT][P]
-    const int n = blockIdx.x / Cout, c = blockIdx.x - n * Cout;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kq = lane >> 4;
-    const bool active = WIDE || wave < ST;
-    const int ut = WIDE ? wave & 1 : 0, vt = WIDE ? wave >> 1 : 0, sb = WIDE ? 0 : (wave < ST ? wave : 0);
-    const int CH4 = BT * V / 4, VV = V * V;
-    const long long TV = (long long)T * V;
-    const float rcpV = 1.f / (float)V;
-    const int ch = dy.coff + c;
-    const float c1 = dy.coef ? dy.coef[ch] : 1.f;
-    const float c2 = (dy.coef && dy.x2) ? dy.coef[dy.ctot + ch] : 0.f;
-    const float c0 = dy.coef ? dy.coef[2 * dy.ctot + ch] : 0.f;
-    const long long dyb = ((long long)n * dy.ctot + ch) * TV;
-    for (int e = tid; e < (ST + 1) * BT * P; e += 256) smem[e] = 0.f;     // joint pads stay zero
-
-    float4 px[NPX], p1[NPY], p2[NPY];
-    auto prefetch = [&](int t0) {
-        const int valid = min(BT, T - t0) * V;
-#pragma unroll
-        for (int i = 0; i < NPX; ++i) {
-            const int e = tid + i * 256, s = (e >= CH4) + (e >= 2 * CH4), r = e - s * CH4;
-            const bool ok = e < ST * CH4 && r * 4 < valid;
-            px[i] = ok ? reinterpret_cast<const float4*>(x3 + (((long long)n * ST + s) * Cout + c) * TV + (long long)t0 * V)[r]
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int i = 0; i < NPY; ++i) {
-            const int r = tid + i * 256;
-            const bool ok = r < CH4 && r * 4 < valid;
-            p1[i] = ok ? reinterpret_cast<const float4*>(dy.x1 + dyb + (long long)t0 * V)[r] : make_float4(0.f, 0.f, 0.f, 0.f);
-            p2[i] = (ok && dy.x2) ? reinterpret_cast<const float4*>(dy.x2 + dyb + (long long)t0 * V)[r] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    prefetch(0);
-    f32x4 acc[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) acc[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int t0 = 0; t0 < T; t0 += BT) {
-        __syncthreads();
-        const int valid = min(BT, T - t0) * V;
-#pragma unroll
-        for (int i = 0; i < NPX; ++i) {
-            const int e = tid + i * 256, s = (e >= CH4) + (e >= 2 * CH4), r = e - s * CH4;
-            if (e < ST * CH4) {
-                float o[4] = {px[i].x, px[i].y, px[i].z, px[i].w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) if (r * 4 + k >= valid) o[k] = 0.f;
-                vg_scatter4(Xs + s * BT * P, P, V, rcpV, r * 4, o);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NPY; ++i) {
-            const int r = tid + i * 256;
-            if (r < CH4) {
-                float o[4];
-                vg_prologue4(p1[i], p2[i], c1, c2, c0, dy.act, r * 4, valid, o);
-                vg_scatter4(Zs, P, V, rcpV, r * 4, o);
-            }
-        }
-        __syncthreads();
-        if (t0 + BT < T) prefetch(t0 + BT);
-        if (active) {
-#pragma unroll
-            for (int k4 = 0; k4 < BT / 4; ++k4) {
-                const float av = Zs[(k4 * 4 + kq) * P + ut * 16 + j];          // A[i = u][k = t]
-#pragma unroll
-                for (int s = 0; s < NS; ++s)
-                    acc[s] = mfma16(av, Xs[((sb + s) * BT + k4 * 4 + kq) * P + vt * 16 + j], acc[s]);   // B[k = t][j = v]
-            }
-        }
-    }
-    if (active) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            float* o = dE + (((long long)n * ST + sb + s) * Cout + c) * VV;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int uu = ut * 16 + kq * 4 + r, vv = vt * 16 + j;
-                if (uu < V && vv < V) o[uu * V + vv] = acc[s][r];
-            }
-        }
-    }
+    using G = VgGeo<VP>;
+    const G g(V);
+#include "ctrgc_stream_de_acc.h"
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -623,8 +305,6 @@ __global__ __launch_bounds__(512) void vgen_de_tail_kernel(const VgTailArgs a) {
 // ---------------------------------------------------------------------------------------------------------------
 int vg_vp(int V) { return V <= 16 ? 16 : 32; }
 size_t vg_e_lds(int V, int R) { return sizeof(float) * ((size_t)R * V * V + 2 * (size_t)R * V); }
-size_t vg_agg_lds(int V, int S, bool bwd) { const int VP = vg_vp(V); return sizeof(float) * (size_t)((S * VP + (bwd ? 1 : S) * VG_BT) * (VP + 2)); }
-size_t vg_de_lds(int V, int S) { return sizeof(float) * (size_t)((S + 1) * VG_BT * (vg_vp(V) + 16)); }
 // the tail's window: as many columns as D and the partial tiles leave room for, at most all of them; 0: does not fit
 int vg_tail_window(int V, int R) {
     const int VV = V * V, RT = R <= 16 ? 1 : 2;
@@ -653,7 +333,7 @@ extern "C" int tamgcn_vgen_supported(int V) { return vg_v_ok(V) ? 1 : 0; }
 extern "C" int tamgcn_vgen_lds_bytes(int S, int V, int R) {
     if (!vg_v_ok(V) || !(S == 1 || S == 3) || !vg_r_ok(R) || !vg_tail_window(V, R)) return -1;
     size_t m = vg_e_lds(V, R);
-    const size_t o[4] = {vg_agg_lds(V, S, false), vg_agg_lds(V, S, true), vg_de_lds(V, S), vg_tail_lds(V, R)};
+    const size_t o[4] = {stream_agg_lds(vg_vp(V), S, false), stream_agg_lds(vg_vp(V), S, true), stream_de_lds(vg_vp(V), S), vg_tail_lds(V, R)};
     for (size_t x : o) m = x > m ? x : m;
     return (int)m;
 }
@@ -680,7 +360,7 @@ static int vgen_stream_check(const tamgcn_ctrgc_desc* d, const char* who) {
         tamgcn_set_error("%s: bad dims N=%d Cout=%d T=%d (Cout a multiple of 16)", who, d->N, d->Cout, d->T); return -1;
     }
     if ((long long)d->N * d->Cout >= (1LL << 31)) { tamgcn_set_error("%s: N*Cout too large for the grid", who); return -1; }
-    if ((long long)d->T * d->V >= (1LL << 31) - 4 * VG_BT * 32) { tamgcn_set_error("%s: T*V=%lld >= 2^31", who, (long long)d->T * d->V); return -1; }
+    if ((long long)d->T * d->V >= (1LL << 31) - 4 * STREAM_BT * 32) { tamgcn_set_error("%s: T*V=%lld >= 2^31", who, (long long)d->T * d->V); return -1; }
     return 0;
 }
 
@@ -710,10 +390,10 @@ extern "C" int tamgcn_vgen_agg_fwd(const tamgcn_ctrgc_desc* d, const float* x3, 
     TG_CHECK(d && x3 && E && y, "tamgcn_vgen_agg_fwd: null pointer");
     if (vgen_stream_check(d, "tamgcn_vgen_agg_fwd")) return -1;
     bool launched = false;
-    VG_CASE(vgen_agg_fwd_kernel, 32, 3, vg_agg_lds(32, 3, false), d->N, d->Cout, d->T, d->V, x3, E, y, stats_part)
-    else VG_CASE(vgen_agg_fwd_kernel, 32, 1, vg_agg_lds(32, 1, false), d->N, d->Cout, d->T, d->V, x3, E, y, stats_part)
-    else VG_CASE(vgen_agg_fwd_kernel, 16, 3, vg_agg_lds(16, 3, false), d->N, d->Cout, d->T, d->V, x3, E, y, stats_part)
-    else VG_CASE(vgen_agg_fwd_kernel, 16, 1, vg_agg_lds(16, 1, false), d->N, d->Cout, d->T, d->V, x3, E, y, stats_part)
+    VG_CASE(vgen_agg_fwd_kernel, 32, 3, stream_agg_lds(32, 3, false), d->N, d->Cout, d->T, d->V, x3, E, y, stats_part)
+    else VG_CASE(vgen_agg_fwd_kernel, 32, 1, stream_agg_lds(32, 1, false), d->N, d->Cout, d->T, d->V, x3, E, y, stats_part)
+    else VG_CASE(vgen_agg_fwd_kernel, 16, 3, stream_agg_lds(16, 3, false), d->N, d->Cout, d->T, d->V, x3, E, y, stats_part)
+    else VG_CASE(vgen_agg_fwd_kernel, 16, 1, stream_agg_lds(16, 1, false), d->N, d->Cout, d->T, d->V, x3, E, y, stats_part)
     TG_CHECK(launched, "tamgcn_vgen_agg_fwd: no instantiation for S=%d V=%d", d->S, d->V);
     TG_LAUNCH_CHECK("tamgcn_vgen_agg_fwd");
     return 0;
@@ -725,10 +405,10 @@ extern "C" int tamgcn_vgen_agg_bwd(const tamgcn_ctrgc_desc* d, const tamgcn_src*
     TG_CHECK(dy->coff >= 0 && dy->ctot >= dy->coff + d->Cout, "tamgcn_vgen_agg_bwd: dy has %d channels from %d, need %d", dy->ctot, dy->coff, d->Cout);
     const SrcDev dys = make_src(*dy);
     bool launched = false;
-    VG_CASE(vgen_agg_bwd_kernel, 32, 3, vg_agg_lds(32, 3, true), d->N, d->Cout, d->T, d->V, dys, E, dx3, db3_part)
-    else VG_CASE(vgen_agg_bwd_kernel, 32, 1, vg_agg_lds(32, 1, true), d->N, d->Cout, d->T, d->V, dys, E, dx3, db3_part)
-    else VG_CASE(vgen_agg_bwd_kernel, 16, 3, vg_agg_lds(16, 3, true), d->N, d->Cout, d->T, d->V, dys, E, dx3, db3_part)
-    else VG_CASE(vgen_agg_bwd_kernel, 16, 1, vg_agg_lds(16, 1, true), d->N, d->Cout, d->T, d->V, dys, E, dx3, db3_part)
+    VG_CASE(vgen_agg_bwd_kernel, 32, 3, stream_agg_lds(32, 3, true), d->N, d->Cout, d->T, d->V, dys, E, dx3, db3_part)
+    else VG_CASE(vgen_agg_bwd_kernel, 32, 1, stream_agg_lds(32, 1, true), d->N, d->Cout, d->T, d->V, dys, E, dx3, db3_part)
+    else VG_CASE(vgen_agg_bwd_kernel, 16, 3, stream_agg_lds(16, 3, true), d->N, d->Cout, d->T, d->V, dys, E, dx3, db3_part)
+    else VG_CASE(vgen_agg_bwd_kernel, 16, 1, stream_agg_lds(16, 1, true), d->N, d->Cout, d->T, d->V, dys, E, dx3, db3_part)
     TG_CHECK(launched, "tamgcn_vgen_agg_bwd: no instantiation for S=%d V=%d", d->S, d->V);
     TG_LAUNCH_CHECK("tamgcn_vgen_agg_bwd");
     return 0;
@@ -740,10 +420,10 @@ extern "C" int tamgcn_vgen_de_acc(const tamgcn_ctrgc_desc* d, const tamgcn_src* 
     TG_CHECK(dy->coff >= 0 && dy->ctot >= dy->coff + d->Cout, "tamgcn_vgen_de_acc: dy has %d channels from %d, need %d", dy->ctot, dy->coff, d->Cout);
     const SrcDev dys = make_src(*dy);
     bool launched = false;
-    VG_CASE(vgen_de_acc_kernel, 32, 3, vg_de_lds(32, 3), d->N, d->Cout, d->T, d->V, x3, dys, dE)
-    else VG_CASE(vgen_de_acc_kernel, 32, 1, vg_de_lds(32, 1), d->N, d->Cout, d->T, d->V, x3, dys, dE)
-    else VG_CASE(vgen_de_acc_kernel, 16, 3, vg_de_lds(16, 3), d->N, d->Cout, d->T, d->V, x3, dys, dE)
-    else VG_CASE(vgen_de_acc_kernel, 16, 1, vg_de_lds(16, 1), d->N, d->Cout, d->T, d->V, x3, dys, dE)
+    VG_CASE(vgen_de_acc_kernel, 32, 3, stream_de_lds(32, 3), d->N, d->Cout, d->T, d->V, x3, dys, dE)
+    else VG_CASE(vgen_de_acc_kernel, 32, 1, stream_de_lds(32, 1), d->N, d->Cout, d->T, d->V, x3, dys, dE)
+    else VG_CASE(vgen_de_acc_kernel, 16, 3, stream_de_lds(16, 3), d->N, d->Cout, d->T, d->V, x3, dys, dE)
+    else VG_CASE(vgen_de_acc_kernel, 16, 1, stream_de_lds(16, 1), d->N, d->Cout, d->T, d->V, x3, dys, dE)
     TG_CHECK(launched, "tamgcn_vgen_de_acc: no instantiation for S=%d V=%d", d->S, d->V);
     TG_LAUNCH_CHECK("tamgcn_vgen_de_acc");
     return 0;

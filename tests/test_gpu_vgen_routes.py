@@ -7,7 +7,9 @@ channels are NaN; NaN in the slack floats behind every streamed operand.
 Joint counts: 3 (VP = 16, almost all pad), 16 (an exact tile, no pads), 17 (one joint past a tile), 18, 23, 31: both padded
 widths and every residue mod 4.  The streaming shapes are the V = 25 list of the templated ledger (a full 32-frame chunk plus a
 ragged frame, a short chunk, T = 1, two chunks, T*V % 4 != 0 for odd V), thinned so that every V and every shape appears at
-least twice.  At V = 25 and V = 32 the new entry points run beside the templated kernels on one shape each.
+least twice.  At V = 25 and V = 32 the new entry points run beside the templated kernels on one shape each, and at V = 20, 25 and
+32 the three streaming kernels of both families (one body, csrc/ctrgc_stream_body.h, under two geometry policies) must give
+the same bits on every streaming shape of that list (BITEQ).
 
 tests/test_vgen_cpu.py (CPU) checks that every instantiation vgen.hip dispatches to is launched here, that an fp32 torch
 evaluation of every case passes its bars and that subtly wrong results do not.  Run with -s for the err / bound ratios."""
@@ -57,6 +59,19 @@ PINNED = {c['sym'] for c in CASES.values()}
 CROSS = ['aggfwd_V25_N2_C16_T33_S3', 'aggbwd_V25_N2_C16_T33_S3', 'deacc_V25_N2_C16_T33_S3', 'E_V25_R8_S3_C48_N2', 'tail_V25_R8_S3_N3_C16',
          'aggfwd_V32_N2_C16_T33_S3', 'aggbwd_V32_N2_C16_T33_S3', 'deacc_V32_N2_C16_T33_S3', 'E_V32_R32_S3_C16_N2', 'tail_V32_R32_S1_N3_C16']
 
+# the streaming kernels exist in both families for V = 20, 25 and 32: every shape of the V = 25 list, every dy form; the case
+# carries both symbols (sym: the templated kernel, vsym: the run-time-V one)
+STREAM_KINDS = ('aggfwd', 'aggbwd', 'deacc')
+TEMPLATED = dict(aggfwd='ctrgc_agg_fwd_kernel', aggbwd='ctrgc_agg_bwd_kernel', deacc='ctrgc_de_acc_mfma_kernel')
+VGEN = dict(aggfwd='vgen_agg_fwd_kernel', aggbwd='vgen_agg_bwd_kernel', deacc='vgen_de_acc_kernel')
+BITEQ = {}
+for _V in (20, 25, 32):
+    for _N, _C, _T, _S in SHAPES:
+        for _k in STREAM_KINDS:
+            BITEQ[f'both_{_k}_V{_V}_N{_N}_C{_C}_T{_T}_S{_S}'] = dict(
+                kind=_k, sym=f'{TEMPLATED[_k]}<{_V}, {_S}>', vsym=f'{VGEN[_k]}<{vp(_V)}, {_S}>', V=_V, N=_N, C=_C, T=_T, S=_S,
+                forms=('plain', 'two', 'relu'), abi='tiled')
+
 
 # ---------------------------------------------------------------------------------------------------------------------
 # problems, references and bars: the templated ledger's functions on this table
@@ -65,7 +80,7 @@ class _table:
     """Run a function of tests/test_gpu_ctrgc_routes.py on this module's case table (its functions look cases up by id)."""
     def __enter__(self):
         self.saved = L.CASES
-        L.CASES = {**L.CASES, **CASES}
+        L.CASES = {**L.CASES, **CASES, **BITEQ}
 
     def __exit__(self, *exc):
         L.CASES = self.saved
@@ -89,9 +104,11 @@ def verify(cid, p, got):
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU runner: every kind through the raw vgen ABI
 # ---------------------------------------------------------------------------------------------------------------------
-def run_once(c, p):
-    """Launch case c (a dict of this table's form) once through tamgcn_vgen_*: the dict evaluate() returns, on the device."""
+def run_once(c, p, abi='tamgcn_vgen'):
+    """Launch case c (a dict of this table's form) once through tamgcn_vgen_*: the dict evaluate() returns, on the device.
+    The three streaming entry points of the templated family take the same arguments: abi='tamgcn_ctrgc_tiled' runs those."""
     k, N, Cout, S, V, sym = c['kind'], c['N'], c['C'], c['S'], c['V'], c['sym']
+    assert abi == 'tamgcn_vgen' or k in STREAM_KINDS
     d = L._desc(c)
     out = {}
     if k == 'E':
@@ -116,7 +133,7 @@ def run_once(c, p):
     elif k == 'aggfwd':
         x3, E = L._dev(p['x3']), L._dev(p['E'])
         y, part = L._out(N, Cout, c['T'], V), L._out(2, Cout, N)
-        L._launch('tamgcn_vgen_agg_fwd', sym, C.byref(d), x3.data_ptr(), E.data_ptr(), y.data_ptr(), part.data_ptr())
+        L._launch(f'{abi}_agg_fwd', sym, C.byref(d), x3.data_ptr(), E.data_ptr(), y.data_ptr(), part.data_ptr())
         out.update(y=y, s1=part[0].double().sum(-1), s2=part[1].double().sum(-1))
         out['raw'] = part
     else:
@@ -126,11 +143,11 @@ def run_once(c, p):
             sc = s.c()
             if k == 'deacc':
                 dE = L._out(N, S, Cout, V, V)
-                L._launch('tamgcn_vgen_de_acc', sym, C.byref(d), C.byref(sc), x3.data_ptr(), dE.data_ptr())
+                L._launch(f'{abi}_de_acc', sym, C.byref(d), C.byref(sc), x3.data_ptr(), dE.data_ptr())
                 out[f'{f}.dE'] = dE
                 continue
             dx3, part = L._out(N, S * Cout, c['T'], V), L._out(N, S * Cout)
-            L._launch('tamgcn_vgen_agg_bwd', sym, C.byref(d), C.byref(sc), E.data_ptr(), dx3.data_ptr(), part.data_ptr())
+            L._launch(f'{abi}_agg_bwd', sym, C.byref(d), C.byref(sc), E.data_ptr(), dx3.data_ptr(), part.data_ptr())
             out[f'{f}.dx3'], out[f'{f}.db3'], out[f'{f}.raw'] = dx3, part.double().sum(0), part
     torch.cuda.synchronize()
     return out
@@ -173,4 +190,23 @@ def test_vgen_beside_the_templated_kernel(cid):
     new = _results(run_once(vgen_twin(c), p))
     assert set(new) == set(old)
     ro, rn = L.verify(cid, p, old), L.verify(cid, p, new)
+    if c['kind'] in STREAM_KINDS:
+        for n in new:
+            assert torch.equal(new[n], old[n]), f'{cid}: {n}: the two families differ'
     print(f'VGEN-CROSS {cid} | templated ' + ' '.join(f'{n}={v:.3f}' for n, v in ro.items()) + ' | vgen ' + ' '.join(f'{n}={v:.3f}' for n, v in rn.items()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('cid', list(BITEQ))
+def test_vgen_same_bits_as_the_templated_kernel(cid):
+    """The streaming kernels are one body under a compile-time-V and a run-time-V policy: the same sums in the same order.  y,
+    dx3, dE and the moment / db3 partial slabs of the two entry points must be the same words, on every streaming shape of the
+    V = 25 list at V = 20, 25 and 32 and for every dy form (plain, two-operand slice between NaN channels, relu)."""
+    c = BITEQ[cid]
+    p = problem(cid)
+    tpl = run_once(c, p, abi='tamgcn_ctrgc_tiled')
+    vgn = run_once(dict(c, sym=c['vsym']), p)
+    assert set(tpl) == set(vgn) and tpl
+    for n in tpl:
+        assert not torch.isnan(tpl[n]).any(), f'{cid}: {n}: NaN in the templated kernel\'s output'
+        assert torch.equal(tpl[n], vgn[n]), f'{cid}: {n}: {int((tpl[n] != vgn[n]).sum())} words differ between the two policies'
