@@ -447,6 +447,31 @@ int tamgcn_add_act_bwd_bits(const float* dout, const unsigned char* bits, const 
                             const float* r_pre, const float* r_save,
                             int N, int C, int T, int V, float* dz, float* part, void* stream);
 
+/* Dropout inside the residual tail (st_gcn with an active Dropout, models/stgcn.py:77-99): out = act(keep * a * scale + res) in
+ * _add_act_fwd's single pass.  Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed.
+ * The draw.  state int64 [2] = (seed, call) on the device; both words are READ ON THE DEVICE, so a HIP graph holding the call
+ *   sees their current values.  For the site tensor (N, C, T, V): row r = n * C + c, L = T * V, group g = i >> 2 of position
+ *   i in the row.  Philox4x32-10 with key = (seed low, seed high) and counter = (call low, call high, r, (site << 20) | g);
+ *   word e of the result decides element 4g + e, which is KEPT iff word >= thr.  thr = floor(p 2^32), computed by the caller
+ *   in fp64; scale = float32(1 / (1 - p)), computed in fp64 and rounded once.  A kept element is fl32(a * scale), a = the
+ *   value of the source descriptor `a` (fma(c1, z, c0) for a BatchNorm-applied tensor); a dropped element is +0.  One forward
+ *   pass uses one value of `call` for all its sites, which differ in `site`.  Refused before any launch: L > 2^22 (g < 2^20
+ *   shares its counter word with the site), site outside 0 .. 4095, a scale that is not a finite value >= 1.
+ * _drop_add_act_fwd  res: NULL (a block without residual) | src.  bits: NULL | the array of tamgcn_conv_signmask's layout, one
+ *   byte per four floats of a row: LOW nibble = the sign bits of `out` as _add_act_fwd_bits writes them (zero when relu = 0),
+ *   HIGH nibble = the keep bits of the same four elements.
+ * _drop_add_act_bwd  d = dout under the sign nibble (relu = 1; dout itself otherwise); dza = fl32(d * scale) where the element
+ *   was kept, 0 elsewhere; dzr = d (NULL: not written; required with r_pre).  part (NULL iff a_pre and r_pre are NULL) has
+ *   _add_act_bwd's layout: part[0..1] = (sum dza, sum dza (a_pre - a_save[c])), and with r_pre part[2..3] = (sum d,
+ *   sum d (r_pre - r_save[c])).  Draws nothing: it reads the bits.  Sums in a fixed order, no atomics.
+ * _dropout_advance   call += 1 in a one-thread launch on the stream (plain store), to follow the last site of a forward pass. */
+int tamgcn_drop_add_act_fwd(const tamgcn_src* a, const tamgcn_src* res, int relu, int N, int C, int T, int V,
+                            const long long* state, int site, unsigned thr, float scale, float* out, unsigned char* bits, void* stream);
+int tamgcn_drop_add_act_bwd(const float* dout, const unsigned char* bits, int relu, float scale, const float* a_pre, const float* a_save,
+                            const float* r_pre, const float* r_save, int N, int C, int T, int V, float* dza, float* dzr, float* part,
+                            void* stream);
+int tamgcn_dropout_advance(long long* state, void* stream);
+
 /* y = prologue value (materialise a src; used by stand-alone modules and tests) */
 int tamgcn_apply(const tamgcn_src* src, int N, int C, int T, int V, float* y, int yctot, int ycoff, void* stream);
 

@@ -221,6 +221,9 @@ SIGNATURES = {
     'tamgcn_add_act_bwd': (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     'tamgcn_add_act_fwd_bits': (_i, [_SP, _SP, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     'tamgcn_add_act_bwd_bits': (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    'tamgcn_drop_add_act_fwd': (_i, [_SP, _SP, _i, _i, _i, _i, _i, _p, _i, C.c_uint, _f, _p, _p, _p]),
+    'tamgcn_drop_add_act_bwd': (_i, [_p, _p, _i, _f, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    'tamgcn_dropout_advance': (_i, [_p, _p]),
     'tamgcn_apply': (_i, [_SP, _i, _i, _i, _i, _p, _i, _i, _p]),
     'tamgcn_score_fuse': (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     'tamgcn_ce_fwd': (_i, [_p, _p, _i, _i, _p, _p, _p]),

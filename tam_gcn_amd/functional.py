@@ -9,6 +9,7 @@ Reference arithmetic being reproduced: models/ctrgcn.py:52-69 (TemporalConv),
 :72-147 (MultiScale_TemporalConv), :150-177 (CTRGC), :179-193 (unit_tcn),
 :196-263 (unit_gcn), :266-284 (TCN_GCN_unit).
 """
+import collections
 import contextlib
 import os
 import threading
@@ -1054,12 +1055,21 @@ def _stgcn_ctrgc_args(x, Ae, W3, B3, Cout):
                 A=Ae.transpose(1, 2).contiguous(), alpha=z(1, device=dev), R=R, K=K)
 
 
+class DropTail(collections.namedtuple('DropTail', 'state site p')):
+    """StGcnFn's `tail` argument for a block whose Dropout runs on the device: the int64 [2] (seed, call) tensor of a
+    dropout.DropoutStream, the block's site id and its drop probability (0 < p < 1)."""
+    __slots__ = ()
+
+
 class StGcnFn(_Fn):
     """relu(tcn(gcn(x, A)) + residual(x)) of one st_gcn block as one autograd node."""
 
     @staticmethod
     def forward(ctx, mod, tail, x, Ae, w3, b3, g1, be1, wt, bt, g2, be2, *res_params):
-        """tail False: stop at the second BatchNorm's output (no residual, no ReLU) -- st_gcn with an active Dropout."""
+        """tail False: stop at the second BatchNorm's output (no residual, no ReLU) -- st_gcn with an active Dropout on torch's
+        generator.  tail a DropTail: relu(dropout(bn2(..)) + residual(x)) with the device mask inside the tail's single pass
+        (ops.drop_add_act_fwd); the backward reads the keep bits the forward left, it draws nothing."""
+        drop = tail if isinstance(tail, DropTail) else None
         N, Cin, T, V = x.shape
         Cout, s, kt = mod.out_channels, mod.stride, mod.t_kernel
         training = mod.training
@@ -1093,9 +1103,13 @@ class StGcnFn(_Fn):
             res = S(r_pre, coef=coef_r)
         else:
             res = None
-        out = ops.add_act_fwd(S(z_pre, coef=coef2), res, bool(tail), Cout)
+        dbits = None
+        if drop is not None:
+            out, dbits = ops.drop_add_act_fwd(S(z_pre, coef=coef2), res, True, Cout, drop.state, drop.site, drop.p, keep_bits=save)
+        else:
+            out = ops.add_act_fwd(S(z_pre, coef=coef2), res, bool(tail), Cout)
         if save:
-            ctx.sv = dict(x=x, Ae=Ae, W3=W3, b3=b3, a=a, x3=x3, E=E, y_pre=y_pre, z_pre=z_pre, r_pre=r_pre, out=out, coef1=coef1, save1=save1,
+            ctx.sv = dict(x=x, dbits=dbits, drop_p=drop.p if drop is not None else None, Ae=Ae, W3=W3, b3=b3, a=a, x3=x3, E=E, y_pre=y_pre, z_pre=z_pre, r_pre=r_pre, out=None if drop is not None else out, coef1=coef1, save1=save1,
                           coef2=coef2, save2=save2, coef_r=coef_r, save_r=save_r, wt=wt, res_params=res_params, training=training,
                           rmode=rmode, tail=bool(tail))
         ctx.mod = mod
@@ -1119,9 +1133,14 @@ class StGcnFn(_Fn):
         xs = S(x)
         with ops.ReduceBatch():
             dout = dout.contiguous()
-            dz, part = ops.add_act_bwd(dout, out, int(sv['tail']), z_pre, sv['save2'], r_pre, sv['save_r'], want_dz=sv['tail'])
-            if dz is None:
-                dz = dout
+            if sv['dbits'] is not None:              # dz feeds bn2 (kept elements, scaled), dres the residual branch (the ReLU mask only)
+                dz, dres, part = ops.drop_add_act_bwd(dout, sv['dbits'], 1, sv['drop_p'], z_pre, sv['save2'], r_pre, sv['save_r'],
+                                                      want_dzr=rmode == 'identity')
+            else:
+                dz, part = ops.add_act_bwd(dout, out, int(sv['tail']), z_pre, sv['save2'], r_pre, sv['save_r'], want_dz=sv['tail'])
+                if dz is None:
+                    dz = dout
+                dres = dz
             coefb2 = torch.empty(3, Cout, device=x.device)
             dg2, dbe2, dbt = bn2.bwd(part, 0, cnt2, sv['save2'], 0, training, coefb2, 0, want_dbias=True)
             gz = S(dz, z_pre, coefb2)
@@ -1139,13 +1158,13 @@ class StGcnFn(_Fn):
             gres = []
             add1 = None
             if rmode == 'identity':
-                add1 = dz
+                add1 = dres
             elif rmode == 'conv':
                 wr = sv['res_params'][0]
                 bnr = BN(mod.residual[1])
                 coefb_r = torch.empty(3, Cout, device=x.device)
                 dgr, dber, dbr = bnr.bwd(part[2:4], 0, cnt2, sv['save_r'], 0, training, coefb_r, 0, True)
-                gyr = S(dz, r_pre, coefb_r)
+                gyr = S(dres, r_pre, coefb_r)
                 dwr = ops.wgrad(gyr, xs, M=Cout, K=Cin, KT=1, stride=s, pad=0)
                 gres = [dwr, dbr, dgr, dber]
                 if need_dx:
@@ -1212,6 +1231,13 @@ class PointwiseConvFn(_Fn):
         if ctx.needs_input_grad[0]:
             dx, _ = ops.conv(S(dy), K=M, w=w.reshape(M, K), bias=None, M=K, wmode=1)
         return dx, dw, db
+
+
+def dropout(x, p, stream, site):
+    """x with the device mask of (stream, site) applied: kept elements times float32(1 / (1 - p)), dropped ones +0
+    (include/tamgcn.h, tamgcn_drop_add_act_fwd).  A 4-D x is walked as (N, C, T, V) rows, anything else as rows x.shape[0]
+    of the remaining elements -- the model heads pass their pooled (N, C).  The caller advances the stream."""
+    return torch.ops.tamgcn.dropout(x, stream.tensor, int(site), float(p))[0]
 
 
 from . import torch_ops  # noqa: E402,F401  (registers torch.ops.tamgcn.*; imports only .ops)

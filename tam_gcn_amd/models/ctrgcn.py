@@ -562,6 +562,11 @@ class Model(nn.Module):
         if isinstance(self.drop_out, nn.Dropout):          # drop_out > 0: pool here, torch's dropout + linear (reference :343-348)
             x, N, M = self._blocks(x)
             x = x.view(N, M, x.size(1), -1).mean(3).mean(1)
+            stream = self.__dict__.get('_tamgcn_drop_stream') if self.training else None
+            if stream is not None and 0 < self.drop_out.p < 1:      # dropout.enable(): the device mask, one call per training forward
+                x = Fn.dropout(x, self.drop_out.p, stream, self.__dict__['_tamgcn_drop_site'])
+                stream.advance()
+                return self.fc(x)
             return self.fc(self.drop_out(x))
         x, N, M, rm = self._blocks(x, emit_pool=True)
         if rm.shape[0]:                                    # l10's last pass already reduced its rows: no second pass over x

@@ -86,6 +86,14 @@ class st_gcn(nn.Module):
             raise AssertionError('A.size(0) must equal the spatial kernel size')
         p = [self.gcn.conv.weight, self.gcn.conv.bias, self.tcn[0].weight, self.tcn[0].bias, self.tcn[2].weight, self.tcn[2].bias,
              self.tcn[3].weight, self.tcn[3].bias]
+        stream = self.__dict__.get('_tamgcn_drop_stream')
+        if stream is not None and self.training and 0 < self._dropout < 1:
+            # dropout.enable(): the mask is drawn inside the fused tail (one autograd node, the conv residual's parameters in it);
+            # the caller -- Model.forward, or the user of a bare block -- advances the stream after the pass's last site
+            if self._rmode == 'conv':
+                p += [self.residual[0].weight, self.residual[0].bias, self.residual[1].weight, self.residual[1].bias]
+            tail = Fn.DropTail(stream.tensor, self.__dict__['_tamgcn_drop_site'], self._dropout)
+            return Fn.StGcnFn.run(self, tail, x, A, *p), A
         if self._dropout and self.training:
             # reference :82-88, :96-99 with an active Dropout between the second BatchNorm and the residual add: the fused node
             # stops at bn2(conv(relu(bn1(gcn(x))))); dropout, the residual branch and the final ReLU follow as separate ops
@@ -159,10 +167,17 @@ class Model(nn.Module):
         if eng is not None:
             return eng(x)
         x, N, M = self._blocks(x)
+        stream = self.__dict__.get('_tamgcn_drop_stream') if self.training else None
         if isinstance(self.drop_out, nn.Dropout):
             x = x.view(N, M, x.size(1), -1).mean(3).mean(1)
-            x = self.drop_out(x)
+            if stream is not None and 0 < self.drop_out.p < 1:
+                x = Fn.dropout(x, self.drop_out.p, stream, self.__dict__['_tamgcn_drop_site'])
+                stream.advance()
+            else:
+                x = self.drop_out(x)
             return torch.nn.functional.linear(x, self.fcn.weight.view(self.fcn.weight.size(0), -1), self.fcn.bias)
+        if stream is not None:
+            stream.advance()
         return torch.ops.tamgcn.head(x, self.fcn.weight.view(self.fcn.weight.size(0), -1), self.fcn.bias, M)   # :193-198
 
     def extract_feature(self, x):

@@ -910,6 +910,65 @@ def add_act_bwd_bits(dout, bits, a_pre, a_save, r_pre, r_save, want_dz):
     return dz, part
 
 
+# ---------------------------------------------------------------------------
+# dropout inside the residual tail (include/tamgcn.h: tamgcn_drop_add_act_fwd has the draw)
+DROP_MAX_ROW = 2 ** 22        # elements per (n, c) row: the group index shares a counter word with the site id
+DROP_MAX_SITES = 4096
+
+
+def dropout_consts(p):
+    """(thr, scale) of a drop probability p in (0, 1): thr = floor(p 2^32) and scale = float32(1 / (1 - p)), both from fp64.
+    The scale is returned as the Python float that holds the rounded fp32 value."""
+    p = float(p)
+    if not 0.0 < p < 1.0:
+        raise ValueError(f'tam_gcn_amd: the device dropout takes 0 < p < 1, not p = {p!r}')
+    import numpy as np
+    return int(p * 4294967296.0), float(np.float32(1.0 / (1.0 - p)))
+
+
+def _drop_check(T, V, site):
+    if T * V > DROP_MAX_ROW:
+        raise ValueError(f'tam_gcn_amd: the device dropout takes rows of at most 2^22 elements, not T * V = {T * V}')
+    if not 0 <= int(site) < DROP_MAX_SITES:
+        raise ValueError(f'tam_gcn_amd: dropout site {site} outside 0 .. {DROP_MAX_SITES - 1}')
+
+
+def drop_add_act_fwd(a, res, relu, C_, state, site, p, keep_bits=True):
+    """out = act(keep * a * scale + res) over (N, C_, T, V); returns (out, bits or None).  state: the int64 [2] = (seed, call)
+    tensor of a DropoutStream, read on the device.  bits (ops.sign_empty's shape): sign nibble low, keep nibble high."""
+    N, _, T, V = a.x1.shape
+    thr, scale = dropout_consts(p)
+    _drop_check(T, V, site)
+    if state.dtype != torch.int64 or state.numel() != 2:
+        raise RuntimeError('tam_gcn_amd: the dropout state is an int64 [2] tensor')
+    out = empty(N, C_, T, V, like=a.x1)
+    bits = sign_empty(N, C_, T, V, out) if keep_bits else None
+    ac = a.c()
+    rc = res.c() if res is not None else None
+    _lib.check(_lib_().tamgcn_drop_add_act_fwd(C.byref(ac), C.byref(rc) if rc is not None else None, int(bool(relu)), N, C_, T, V,
+                                               _ptr(state), int(site), thr, scale, _ptr(out), _ptr(bits), _stream()),
+               'tamgcn_drop_add_act_fwd')
+    return out, bits
+
+
+def drop_add_act_bwd(dout, bits, relu, p, a_pre, a_save, r_pre, r_save, want_dzr):
+    """(dza, dzr or None, part or None) of drop_add_act_fwd's backward; part [4 | 2][C][N] exists iff a_pre is given."""
+    N, Cc, T, V = dout.shape
+    _, scale = dropout_consts(p)
+    dza = empty_like(dout)
+    dzr = empty_like(dout) if (want_dzr or r_pre is not None) else None
+    part = empty(4 if r_pre is not None else 2, Cc, N, like=dout) if a_pre is not None else None
+    _lib.check(_lib_().tamgcn_drop_add_act_bwd(_ptr(dout), _ptr(bits), int(bool(relu)), scale, _ptr(a_pre), _ptr(a_save), _ptr(r_pre),
+                                               _ptr(r_save), N, Cc, T, V, _ptr(dza), _ptr(dzr), _ptr(part), _stream()),
+               'tamgcn_drop_add_act_bwd')
+    return dza, dzr, part
+
+
+def dropout_advance(state):
+    """call += 1 on the device, in stream order."""
+    _lib.check(_lib_().tamgcn_dropout_advance(_ptr(state), _stream()), 'tamgcn_dropout_advance')
+
+
 def apply(src, C_, y=None, ycoff=0):
     N, _, T, V = src.x1.shape
     if y is None:

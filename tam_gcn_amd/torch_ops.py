@@ -12,6 +12,7 @@ backward is itself a registered op:
     tamgcn::pointwise_conv(x, w, b) -> y;  tamgcn::pointwise_conv_backward(dy, x, w) -> (dx, dw, db)
     tamgcn::head(x, W, b, M) -> logits;  tamgcn::head_backward(dlogits, x, W, M) -> (dx, dW, db)        models/ctrgcn.py:343-348
     tamgcn::head_pooled(x, rowmean, W, b, M): the same with the row means of x already taken by the producer of x
+    tamgcn::dropout(x, state, site, p) -> (out, bits);  tamgcn::dropout_backward(dout, bits, p) -> dx      the device mask of dropout.py
     tamgcn::stream_derive(x, parent, mode) -> stream            feeder/feeder_nucla_gcn.py:119-127
     tamgcn::feeder_transform(raw, offsets, rot, idx, parent, V, time_steps, center_joint, mode) -> clips   :85-130
     tamgcn::guidance_reduce(h, M) -> (intensity, pooled, minmax);  tamgcn::guidance_weights(intensity, minmax, joints, k) -> weights;
@@ -310,6 +311,52 @@ def _headp_bwd(ctx, dl):
 
 
 head_pooled.register_autograd(_headp_bwd, setup_context=_headp_setup)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# device dropout (the model heads; the st_gcn blocks carry theirs inside functional.StGcnFn)
+# ---------------------------------------------------------------------------------------------------------------
+def _rows4(x):
+    """x as the (N, C, T, V) the row kernels walk: a 4-D tensor as it is, anything else as (shape[0], 1, 1, rest)."""
+    x = _c(x)
+    return x if x.dim() == 4 else x.view(x.shape[0], 1, 1, -1)
+
+
+@torch.library.custom_op('tamgcn::dropout', mutates_args=())
+def dropout(x: Tensor, state: Tensor, site: int, p: float) -> tuple[Tensor, Tensor]:
+    x4 = _rows4(x)
+    out, bits = ops.drop_add_act_fwd(S(x4), None, False, x4.shape[1], state, site, p)
+    return out.view(x.shape), bits
+
+
+@dropout.register_fake
+def _(x, state, site, p):
+    x4 = x if x.dim() == 4 else x.view(x.shape[0], 1, 1, -1)
+    return torch.empty_like(x), x.new_empty(x4.shape[0], x4.shape[1], (x4.shape[2] * x4.shape[3] + 3) // 4, dtype=torch.uint8)
+
+
+@torch.library.custom_op('tamgcn::dropout_backward', mutates_args=())
+def dropout_backward(dout: Tensor, bits: Tensor, p: float) -> Tensor:
+    d4 = _rows4(dout)
+    dx, _, _ = ops.drop_add_act_bwd(d4, bits, False, p, None, None, None, None, want_dzr=False)
+    return dx.view(dout.shape)
+
+
+@dropout_backward.register_fake
+def _(dout, bits, p):
+    return torch.empty_like(dout)
+
+
+def _dropout_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+    ctx.p = inputs[3]
+
+
+def _dropout_bwd(ctx, dout, _dbits):
+    return torch.ops.tamgcn.dropout_backward(dout, ctx.saved_tensors[0], ctx.p), None, None, None
+
+
+dropout.register_autograd(_dropout_bwd, setup_context=_dropout_setup)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -35,6 +35,7 @@ A replay executes no Python, so the host-side counters that invalidate the folde
 """
 import torch
 
+from . import dropout as _dropout
 from . import functional as Fn
 
 
@@ -42,7 +43,8 @@ class CapturedStep:
     """One model, one loss, one FusedSGD / FusedAdam over ``arena`` / ``bucket``.  ``example_x`` / ``example_y`` fix the
     shapes and dtypes every later batch must have.  Construction runs WARMUP eager steps on a side stream (graph
     capture needs the allocator and the kernels warmed up) and then restores the parameters, the model's buffers and the
-    optimiser's state: building the step does not train the model.  ``eager=True`` runs the same sequence without
+    optimiser's state -- and the (seed, call) of a DropoutStream attached by ``dropout.enable`` -- : building the step does not
+    train the model or consume draws; the capture records the stream's advance launch, so every replay draws a new mask.  ``eager=True`` runs the same sequence without
     graphs (debugging; equality tests).  ``accum_steps=k > 1``: ``step`` accumulates k micro-batch gradients, each scaled
     by 1/k, and updates on every k-th call; ``pending`` is the number accumulated since the last update."""
     WARMUP = 2                                                  # eager steps before capture, as bench.py
@@ -69,6 +71,7 @@ class CapturedStep:
         if eager:
             return
         saved = (arena.flat.clone(), [b.detach().clone() for b in model.buffers()], optimizer.state_dict())
+        drops = [(s, s.tensor.clone()) for s in _dropout.streams_under(model)]      # the warm-up forwards advance `call`
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(dev)
         side.wait_stream(cur)
@@ -84,6 +87,8 @@ class CapturedStep:
             arena.flat.copy_(saved[0])
             for b, v in zip(model.buffers(), saved[1]):
                 b.copy_(v)
+            for s, v in drops:                                  # building the step consumes no draws
+                s.tensor.copy_(v)
         optimizer.load_state_dict(saved[2])
         arena.touch()
         torch.cuda.synchronize(dev)
