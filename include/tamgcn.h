@@ -1020,6 +1020,51 @@ typedef struct tamgcn_grad_guard {
 } tamgcn_grad_guard;
 int tamgcn_optim_step_guarded(const tamgcn_optim_desc* d, const tamgcn_grad_guard* g, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Live and sliding-window inference from a device-resident frame ring (csrc/streaming.hip, tam_gcn_amd/streaming.py).
+ * Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed.
+ *
+ * Frames are numbered absolutely in int64 from 0, the first frame ever pushed; frame f lives in slot f % cap.  A ring is
+ * logically (P, cap, R) with elements of `elem` bytes: P = 1, R = V 3, elem = 8 is fp64 (cap, V, 3), the raw form
+ * tamgcn_feeder_transform reads; P = C, R = V M, elem = 4 is fp32 (C, cap, V, M), the clip feeder's layout with T = cap.
+ * A sequence that is resident as a whole is a ring of cap = its length that never wraps.  A plan is int64 (B, 2) =
+ * (start, L) per window; L = 0 marks an invalid window, and so does any row with start < 0 or L > cap.  No entry point
+ * synchronises, none uses floating-point atomics: two calls give the same bits, a graph replay the eager call's.
+ *
+ *   _ring_push     frames (P, n, R) -> slots (count + i) % cap of every plane, 1 <= n <= cap.  state int64 [2] =
+ *                  (count, pushes) on the device, read by this launch and advanced by a one-thread launch behind it.
+ *                  16-byte accesses where R elem is a multiple of 16 and both arrays are 16-byte aligned.
+ *   _ring_plan     window j of B has length L and ends (B - 1 - j) hop frames before the newest frame: j = B - 1 is the
+ *                  newest.  A window that would start before frame 0 or before count - cap (overwritten) gets (0, 0).
+ *                  1 <= L <= cap, hop >= 1.
+ *   _window_nucla  out (B, 3, time_steps, V, 1) fp32: the arithmetic of tamgcn_feeder_transform on the window's L frames
+ *                  with the identity view and idx = np.linspace(0, L - 1, time_steps).astype(int) -- centre on
+ *                  center_joint of the window's first frame, per-coordinate min / max over the window,
+ *                  (p - lo) / (hi - lo + 1e-6) * 2 - 1 in fp64, the stream `mode` 0..3 -- one body with that kernel, so
+ *                  bit-equal to it on a copy of the window's frames.  time_steps <= 64.  Invalid windows: zeros.
+ *   _window_clip   out (B, C, W, V, M) fp32: the linear time-resize of tamgcn_clip_resize on the crop (start, L) without
+ *                  rotation -- the same taps, src = ((2 t + 1) L - W) / (2 W) clamped at 0 as that kernel computes it in
+ *                  fp32, the same blend l0 x[i0] + l1 x[i1] without contraction -- sources fetched at (start + i) % cap.
+ *                  L = W copies the frames (l1 = 0; a -0.0 comes out +0.0, as from tamgcn_clip_resize).  Invalid: zeros.
+ *   _window_vote   probs[j] = softmax(logits[j]) over K <= 4096 classes: fp64 from the fp32 logits, max shift, the sum class
+ *                  ascending, rounded once to fp32.  frame_scores[f], f < n_frames: the mean over j ascending of probs[j]
+ *                  (the fp32 values, summed in fp64, rounded once) of the valid windows with start_j <= f < start_j + L_j;
+ *                  frame_label[f] int64 its first arg max; no such window: zeros and -1.  frame_scores and frame_label
+ *                  may both be NULL: only probs is written.  One launch, two with the frame outputs.
+ *   _score_ema     plan_row: one plan row.  Valid: ema = probs when *seen == 0, else beta ema + (1 - beta) probs in fp64,
+ *                  then *seen += 1; invalid: nothing moves.  out = (float)ema, *label = the first arg max of ema or -1
+ *                  while *seen == 0, *conf = out[*label] (0 with -1).  ema fp64 [K], seen int64 [1], K <= 4096,
+ *                  0 <= beta < 1. */
+int tamgcn_ring_push(const void* frames, int n, int P, int R, int elem, void* ring, int cap, long long* state, void* stream);
+int tamgcn_ring_plan(const long long* state, int cap, int B, int L, int hop, long long* plan, void* stream);
+int tamgcn_window_nucla(const double* ring, int cap, const long long* plan, int B, const int* parent, int V, int time_steps,
+                        int center_joint, int mode, float* out, void* stream);
+int tamgcn_window_clip(const float* ring, int cap, const long long* plan, int B, int C, int V, int M, int W, float* out, void* stream);
+int tamgcn_window_vote(const float* logits, const long long* plan, int B, int K, int n_frames, float* probs, float* frame_scores,
+                       long long* frame_label, void* stream);
+int tamgcn_score_ema(const float* probs, const long long* plan_row, int K, double beta, double* ema, long long* seen, float* out,
+                     long long* label, float* conf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -242,6 +242,12 @@ SIGNATURES = {
     'tamgcn_clip_transform': (_i, [_p, _ll, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     'tamgcn_clip_crop_draw': (_i, [_p, _ll, _p, _i, _p, _p, _i, _d, _d, _i, _d, _p, _p, _p, _p, _p]),
     'tamgcn_clip_resize': (_i, [_p, _ll, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    'tamgcn_ring_push': (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p]),
+    'tamgcn_ring_plan': (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    'tamgcn_window_nucla': (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _p, _p]),
+    'tamgcn_window_clip': (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
+    'tamgcn_window_vote': (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    'tamgcn_score_ema': (_i, [_p, _p, _i, _d, _p, _p, _p, _p, _p, _p]),
     'tamgcn_f2_e': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2_gcn': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2_gemm': (_i, [C.POINTER(F2GemmDesc), _p]),

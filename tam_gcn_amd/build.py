@@ -10,7 +10,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = ['lib.hip', 'conv.hip', 'wgrad.hip', 'reduce.hip', 'bn.hip', 'elementwise.hip', 'dropout.hip', 'ctrgc.hip', 'ctrgc_de.hip', 'ctrgc_tiled.hip', 'vgen.hip', 'stemhead.hip', 'celoss.hip', 'feeder.hip', 'clipfeeder.hip', 'f2.hip', 'f2v.hip', 'f2g.hip', 'f2s.hip', 'f2s_bwd.hip', 'saliency.hip', 'guidance.hip', 'tconv.hip', 'optim.hip', 'evalmeter.hip']
+SRC = ['lib.hip', 'conv.hip', 'wgrad.hip', 'reduce.hip', 'bn.hip', 'elementwise.hip', 'dropout.hip', 'ctrgc.hip', 'ctrgc_de.hip', 'ctrgc_tiled.hip', 'vgen.hip', 'stemhead.hip', 'celoss.hip', 'feeder.hip', 'clipfeeder.hip', 'streaming.hip', 'f2.hip', 'f2v.hip', 'f2g.hip', 'f2s.hip', 'f2s_bwd.hip', 'saliency.hip', 'guidance.hip', 'tconv.hip', 'optim.hip', 'evalmeter.hip']
 LIB = os.path.join(HERE, 'libtamgcn.so')
 ARCH = 'gfx950'
 

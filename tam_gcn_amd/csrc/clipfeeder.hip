@@ -330,12 +330,9 @@ struct ClipRsArgs {
 struct Tap { int o0, o1; float l0, l1; };
 
 __device__ __forceinline__ Tap resize_tap(int t, int start, int L, float scale, int VM) {
-#pragma clang fp contract(off)
-    const float src = fmaxf(scale * ((float)t + 0.5f) - 0.5f, 0.f);
-    const int i0 = min((int)src, L - 1), i1 = min(i0 + 1, L - 1);
-    const float l1 = src - (float)i0;
+    const ResizeTaps r = resize_taps(t, L, scale);       // feeder_common.h: shared with the ring's window builder
     Tap tp;
-    tp.o0 = (start + i0) * VM; tp.o1 = (start + i1) * VM; tp.l0 = 1.f - l1; tp.l1 = l1;
+    tp.o0 = (start + r.i0) * VM; tp.o1 = (start + r.i1) * VM; tp.l0 = r.l0; tp.l1 = r.l1;
     return tp;
 }
 

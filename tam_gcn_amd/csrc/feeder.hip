@@ -40,83 +40,22 @@ struct FeederArgs {
     long long n_clips;
 };
 
-__device__ __forceinline__ void rot_point(const double* p, const double* c, const double* R, double* o) {
-    const double x = p[0] - c[0], y = p[1] - c[1], z = p[2] - c[2];
-    // numpy's row-vector-times-matrix order: o_j = x R[0][j] + y R[1][j] + z R[2][j], left to right
-    o[0] = x * R[0] + y * R[3] + z * R[6];
-    o[1] = x * R[1] + y * R[4] + z * R[7];
-    o[2] = x * R[2] + y * R[5] + z * R[8];
-}
-
-// One workgroup per clip.  Pass 1: per-coordinate min / max over every (frame, joint) of the transformed clip;
-// pass 2: the TS x V output positions (gathered frames), normalised to [-1, 1] and written as the requested stream.
+// One workgroup per clip, the body of feeder_common.h (shared with the ring's window builder, streaming.hip).
 // INDEXED: slot n reads clip clip_ids[n] % n_clips of the resident split instead of clip n of a gathered copy; the
 // arithmetic is this one body either way.
 template <bool INDEXED>
 __global__ __launch_bounds__(256) void feeder_transform_kernel(const FeederArgs a) {
-    __shared__ double smin[3][256 / 64], smax[3][256 / 64];
-    __shared__ double lo[3], hi[3];
-    const int n = blockIdx.x, tid = threadIdx.x, V = a.V;
+    const int n = blockIdx.x, V = a.V, TS = a.TS;
     const long long c = INDEXED ? clip_of(a.clip_ids[n], a.n_clips) : n;
     const long long f0 = a.offs[c], L = a.offs[c + 1] - f0;
     const double* clip = a.raw + f0 * V * 3;
-    const double* R = a.rot + (long long)n * 9;
-    const double cen[3] = {clip[a.center_joint * 3 + 0], clip[a.center_joint * 3 + 1], clip[a.center_joint * 3 + 2]};   // frame 0
-    double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
-    for (long long e = tid; e < L * V; e += 256) {
-        double o[3];
-        rot_point(clip + e * 3, cen, R, o);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { mn[k] = fmin(mn[k], o[k]); mx[k] = fmax(mx[k], o[k]); }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        for (int off = 1; off < 64; off <<= 1) {
-            mn[k] = fmin(mn[k], __shfl_xor(mn[k], off));
-            mx[k] = fmax(mx[k], __shfl_xor(mx[k], off));
-        }
-        if ((tid & 63) == 0) { smin[k][tid >> 6] = mn[k]; smax[k][tid >> 6] = mx[k]; }
-    }
-    __syncthreads();
-    if (tid < 3) {
-        double l = smin[tid][0], h = smax[tid][0];
-        for (int w = 1; w < 4; ++w) { l = fmin(l, smin[tid][w]); h = fmax(h, smax[tid][w]); }
-        lo[tid] = l; hi[tid] = h;
-    }
-    __syncthreads();
-    const int TS = a.TS;
-    auto joint = [&](int t, int v, double* o) {        // normalised joint coordinates of output frame t
-        const long long fr = a.idx[(long long)n * TS + t];
-        double p[3];
-        rot_point(clip + (fr * V + v) * 3, cen, R, p);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o[k] = (p[k] - lo[k]) / (hi[k] - lo[k] + 1e-6) * 2 - 1;
-    };
-    auto bone = [&](int t, int v, double* o) {
-        double c[3], p[3];
-        joint(t, v, c); joint(t, a.parent[v], p);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o[k] = c[k] - p[k];
-    };
-    for (int e = tid; e < TS * V; e += 256) {
-        const int t = e / V, v = e - t * V;
-        double o[3] = {0., 0., 0.};
-        if (a.mode == 0) joint(t, v, o);
-        else if (a.mode == 1) bone(t, v, o);
-        else if (t < TS - 1) {
-            double c[3], nx[3];
-            if (a.mode == 2) { joint(t, v, c); joint(t + 1, v, nx); }
-            else { bone(t, v, c); bone(t + 1, v, nx); }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) o[k] = nx[k] - c[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) a.out[(((long long)n * 3 + k) * TS + t) * V + v] = (float)o[k];
-    }
+    const int* idx = a.idx + (long long)n * TS;
+    feeder_transform_body([&](long long e) { return clip + e * 3; }, [&](int t) { return idx[t]; }, L, V, TS, a.mode, a.center_joint,
+                          a.rot + (long long)n * 9, a.parent, a.out + (long long)n * 3 * TS * V);
 }
 
 // ---- the train path's draws on the device (Feeder.batch_device) ----------------------------------------------------
-// (clip_of and Philox4x32-10: feeder_common.h)
+// (clip_of, val_frame and Philox4x32-10: feeder_common.h)
 // o = a . b, 3 x 3 row-major, each entry summed left to right
 __device__ __forceinline__ void mat3(const double* a, const double* b, double* o) {
 #pragma unroll
@@ -157,10 +96,7 @@ __global__ __launch_bounds__(64) void feeder_draw_kernel(const DrawArgs a) {
     double* view = a.view + (long long)b * 3;
     double* rot = a.rot + (long long)b * 9;
     if (!a.train) {                                      // np.linspace(0, L - 1, TS).astype(int), reference :116
-        if (lane < TS) {
-            const double step = (double)(L - 1) / (double)(TS > 1 ? TS - 1 : 1);
-            idx[lane] = (lane == TS - 1 && TS > 1) ? (int)(L - 1) : (int)((double)lane * step);
-        }
+        if (lane < TS) idx[lane] = val_frame(lane, L, TS);
         if (lane < 9) rot[lane] = (lane % 4 == 0) ? 1.0 : 0.0;
         if (lane < 3) view[lane] = lane == 2 ? 1.0 : 0.0;
         return;

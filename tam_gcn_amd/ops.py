@@ -1249,6 +1249,116 @@ def clip_resize(raw, clip_ids, crop, W, rot=None):
     return out
 
 
+# live and sliding-window inference (csrc/streaming.hip; include/tamgcn.h has the ring, the plan and every rule)
+STREAM_MAX_TS = 64            # time_steps of window_nucla
+STREAM_MAX_K = 4096           # classes of window_vote / score_ema
+
+
+def _ring_geometry(ring, what):
+    """(P, cap, R, elem) of a ring tensor: fp64 (cap, V, 3) or fp32 (C, cap, V, M)."""
+    if isinstance(ring, torch.Tensor) and ring.dtype == torch.float64 and ring.dim() == 3 and ring.shape[2] == 3 and ring.numel():
+        return 1, ring.shape[0], ring.shape[1] * 3, 8
+    if isinstance(ring, torch.Tensor) and ring.dtype == torch.float32 and ring.dim() == 4 and ring.numel():
+        return ring.shape[0], ring.shape[1], ring.shape[2] * ring.shape[3], 4
+    raise RuntimeError(f'tam_gcn_amd: {what} takes a non-empty fp64 (cap, V, 3) or fp32 (C, cap, V, M) ring, got '
+                       f'{getattr(ring, "dtype", type(ring))} {tuple(getattr(ring, "shape", ()))}')
+
+
+def ring_push(frames, ring, state):
+    """frames fp64 (n, V, 3) into ring fp64 (cap, V, 3), or fp32 (C, n, V, M) into fp32 (C, cap, V, M): slots (count + i) % cap;
+    state int64 [2] = (count, pushes), read and advanced on the device.  1 <= n <= cap.  No host sync, capturable."""
+    P, cap, R, elem = _ring_geometry(ring, 'ring_push')
+    _want(ring, 'ring', ring.dtype)
+    _want(state, 'state', torch.int64, (2,))
+    t = 0 if elem == 8 else 1                       # the time axis
+    if not isinstance(frames, torch.Tensor) or frames.dim() != ring.dim() or frames.shape[:t] + frames.shape[t + 1:] != ring.shape[:t] + ring.shape[t + 1:]:
+        raise RuntimeError(f'tam_gcn_amd: ring_push: frames {tuple(getattr(frames, "shape", ()))} do not fit the ring {tuple(ring.shape)}')
+    _want(frames, 'frames', ring.dtype)
+    _lib.check(_lib_().tamgcn_ring_push(_ptr(frames), frames.shape[t], P, R, elem, _ptr(ring), cap, _ptr(state), _stream()), 'tamgcn_ring_push')
+
+
+def ring_plan(state, cap, B, L, hop):
+    """-> plan int64 (B, 2) = (start, L): window j ends (B - 1 - j) hop frames before the newest frame of the ring whose state
+    is `state`; (0, 0) where the window starts before frame 0 or is overwritten.  No host sync, capturable."""
+    _want(state, 'state', torch.int64, (2,))
+    plan = torch.empty(B, 2, device=state.device, dtype=torch.int64)
+    _lib.check(_lib_().tamgcn_ring_plan(_ptr(state), cap, B, L, hop, _ptr(plan), _stream()), 'tamgcn_ring_plan')
+    return plan
+
+
+def _want_plan(plan):
+    _want(plan, 'plan', torch.int64)
+    if plan.dim() != 2 or plan.shape[1] != 2 or plan.shape[0] < 1:
+        raise RuntimeError(f'tam_gcn_amd: plan is {tuple(plan.shape)}, expected (B, 2)')
+    return plan.shape[0]
+
+
+def window_nucla(ring, plan, parent, time_steps, center_joint, mode):
+    """ring fp64 (cap, V, 3), plan int64 (B, 2), parent int32 [V] -> (B, 3, time_steps, V, 1) fp32: feeder_transform's val path
+    on every window (identity view, np.linspace indices), zeros for an invalid one."""
+    _want(ring, 'ring', torch.float64)
+    if ring.dim() != 3 or ring.shape[2] != 3 or ring.numel() == 0:
+        raise RuntimeError(f'tam_gcn_amd: window_nucla takes a non-empty (cap, V, 3) ring, got {tuple(ring.shape)}')
+    cap, V = ring.shape[0], ring.shape[1]
+    B = _want_plan(plan)
+    _want(parent, 'parent', torch.int32, (V,))
+    m = STREAM_MODES[mode] if isinstance(mode, str) else int(mode)
+    out = torch.empty(B, 3, time_steps, V, 1, device=ring.device, dtype=torch.float32)
+    _lib.check(_lib_().tamgcn_window_nucla(_ptr(ring), cap, _ptr(plan), B, _ptr(parent), V, time_steps, center_joint, m, _ptr(out), _stream()),
+               'tamgcn_window_nucla')
+    return out
+
+
+def window_clip(ring, plan, W):
+    """ring fp32 (C, cap, V, M), plan int64 (B, 2) -> (B, C, W, V, M) fp32: clip_resize's linear time-resize of every window
+    (no rotation), zeros for an invalid one."""
+    _want(ring, 'ring', torch.float32)
+    if ring.dim() != 4 or ring.numel() == 0:
+        raise RuntimeError(f'tam_gcn_amd: window_clip takes a non-empty (C, cap, V, M) ring, got {tuple(ring.shape)}')
+    C_, cap, V, M = ring.shape
+    B = _want_plan(plan)
+    out = torch.empty(B, C_, W, V, M, device=ring.device, dtype=torch.float32)
+    _lib.check(_lib_().tamgcn_window_clip(_ptr(ring), cap, _ptr(plan), B, C_, V, M, W, _ptr(out), _stream()), 'tamgcn_window_clip')
+    return out
+
+
+def window_vote(logits, plan, n_frames=None):
+    """logits fp32 (B, K), plan int64 (B, 2) -> probs fp32 (B, K) = softmax rows, and with n_frames: frame_scores fp32
+    (n_frames, K) = per frame the mean of the valid windows that cover it, frame_label int64 (n_frames,) (-1: uncovered);
+    both None without n_frames."""
+    _want(logits, 'logits', torch.float32)
+    if logits.dim() != 2 or logits.numel() == 0:
+        raise RuntimeError(f'tam_gcn_amd: window_vote takes non-empty (B, K) logits, got {tuple(logits.shape)}')
+    B, K = logits.shape
+    _want(plan, 'plan', torch.int64, (B, 2))
+    probs = torch.empty_like(logits)
+    fs = fl = None
+    if n_frames is not None:
+        fs = torch.empty(n_frames, K, device=logits.device, dtype=torch.float32)
+        fl = torch.empty(n_frames, device=logits.device, dtype=torch.int64)
+    _lib.check(_lib_().tamgcn_window_vote(_ptr(logits), _ptr(plan), B, K, n_frames or 0, _ptr(probs), _ptr(fs), _ptr(fl), _stream()),
+               'tamgcn_window_vote')
+    return probs, fs, fl
+
+
+def score_ema(probs, plan_row, beta, ema, seen):
+    """probs fp32 [K], plan_row int64 [2], ema fp64 [K] and seen int64 [1] updated in place on the device (an invalid window moves
+    nothing) -> out fp32 [K] = the average, label int64 [1] (-1 before the first valid window), conf fp32 [1]."""
+    _want(probs, 'probs', torch.float32)
+    K = probs.numel()
+    _want(plan_row, 'plan_row', torch.int64, (2,))
+    _want(ema, 'ema', torch.float64, (K,))
+    _want(seen, 'seen', torch.int64, (1,))
+    if probs.dim() != 1:
+        raise RuntimeError(f'tam_gcn_amd: score_ema takes one row of probabilities, got {tuple(probs.shape)}')
+    out = torch.empty(K, device=probs.device, dtype=torch.float32)
+    label = torch.empty(1, device=probs.device, dtype=torch.int64)
+    conf = torch.empty(1, device=probs.device, dtype=torch.float32)
+    _lib.check(_lib_().tamgcn_score_ema(_ptr(probs), _ptr(plan_row), K, float(beta), _ptr(ema), _ptr(seen), _ptr(out), _ptr(label), _ptr(conf),
+                                        _stream()), 'tamgcn_score_ema')
+    return out, label, conf
+
+
 # ---------------------------------------------------------------------------
 # loss of the harness step (SURVEY.md §8 f1)
 def ce_fwd(logits, labels):

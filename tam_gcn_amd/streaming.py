@@ -1,0 +1,453 @@
+"""Live and untrimmed inference: a stream of skeleton frames from a pose estimator, or one long recording, instead of clips a
+feeder cut from a dataset split (the reference ships the pose extraction for this use, tools/gen_ucla_yolo_ske.py; graph.coco
+and graph.openpose are its skeletons).
+
+``FrameRing`` holds the last ``capacity`` frames in HBM and is pushed to without the host.  The model's input windows are built
+straight from it by the val path of either feeder -- ``prep='nucla'``: feeder_nucla_gcn's centring, min-max normalisation and
+resampling to ``time_steps`` frames on raw (V, 3) fp64 joints; ``prep='clip'``: clip_feeder's linear time-resize to
+``window_size`` frames on (C, V, M) fp32 frames -- by the kernels those feeders run (csrc/streaming.hip shares their bodies), so
+a window is bit-equal to what the feeder makes of a clip with the same frames.
+
+``LiveClassifier`` is the frame-by-frame use: push -> plan -> window -> stream derivation -> forward -> softmax -> moving
+average as one HIP graph that never synchronises:
+
+    ring = FrameRing(128, prep='nucla', V=20)
+    live = LiveClassifier(model.eval(), ring, window=40, beta=0.8)
+    for frame in camera:                                   # (1, 20, 3) on the device
+        label, conf, smoothed, logits = live.step(frame)   # device tensors, overwritten by the next step
+        ...                                                # read them when a decision is due: that read is the only sync
+
+``SlidingWindow`` is the offline use, one dense pass over a long sequence with per-frame votes:
+
+    sw = SlidingWindow(model.eval(), window=40, hop=8, prep='nucla')
+    res = sw.run(recording)                                # (len, 20, 3)
+    res.frame_label                                        # (len,) int64 on the device
+
+The plan rule of ``SlidingWindow``: windows start at j * hop while j * hop + window <= len; one more window at len - window
+when that leaves frames uncovered; a sequence shorter than the window is one window (0, len).  A frame's scores are the mean
+of the softmax rows of the windows that cover it.  ``LiveClassifier``: per step `hop_windows` windows, window j ending
+(hop_windows - 1 - j) * hop frames before the newest frame; a window that reaches before frame 0, or into frames the ring has
+overwritten, is invalid: its input is zeros, it does not move the average, and until the first valid window the label is -1."""
+import collections
+
+import torch
+
+from . import ops
+from .evaluation import _state_key
+from .inference import ENGINE_SLOTS, GraphedForward, default_parent
+
+__all__ = ['FrameRing', 'SlidingWindow', 'LiveClassifier', 'plan_offline']
+
+PREPS = ('nucla', 'clip')
+NUCLA_CENTER_JOINT = 1         # feeder_nucla_gcn centres on joint 1 of the first frame
+
+
+def _int(name, v, lo, who):
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+        raise ValueError(f'{who}: {name} = {v!r} must be an integer >= {lo}')
+    return v
+
+
+def _device(device, who):
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise ValueError(f'{who}: the frames live on the GPU; there is no CPU path')
+    return dev
+
+
+class FrameRing:
+    """capacity frames in HBM; frame f (counted from 0, the first frame ever pushed) lives in slot f % capacity.
+
+    prep='nucla': buf fp64 (capacity, V, 3), push((n, V, 3)) in any float dtype (cast to fp64 on the device).
+    prep='clip':  buf fp32 (C, capacity, V, M), push((C, n, V, M)) fp32.
+    push() makes no host synchronisation and is capturable; 1 <= n <= capacity.  state int64 [2] = (frames, pushes) lives on
+    the device; `count` reads it (a synchronisation).  reset() forgets every frame."""
+
+    def __init__(self, capacity, prep='nucla', V=None, C=3, M=1, device='cuda'):
+        who = 'FrameRing'
+        self.capacity = _int('capacity', capacity, 1, who)
+        if prep not in PREPS:
+            raise ValueError(f'{who}: prep {prep!r} (one of {PREPS})')
+        self.V, self.C, self.M = _int('V', V, 1, who), _int('C', C, 1, who), _int('M', M, 1, who)
+        if prep == 'nucla' and (C != 3 or M != 1):
+            raise ValueError(f"{who}: prep='nucla' holds one person's (V, 3) joints; C = {C}, M = {M}")
+        self.prep = prep
+        dev = _device(device, who)
+        if prep == 'nucla':
+            self.buf = torch.zeros(capacity, V, 3, dtype=torch.float64, device=dev)
+        else:
+            self.buf = torch.zeros(C, capacity, V, M, dtype=torch.float32, device=dev)
+        self.state = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def frames_shape(self, n):
+        return (n, self.V, 3) if self.prep == 'nucla' else (self.C, n, self.V, self.M)
+
+    def push(self, frames):
+        if not torch.is_tensor(frames) or not frames.is_cuda:
+            raise RuntimeError('FrameRing.push: expected a HIP (cuda) tensor; there is no CPU path')
+        t = 0 if self.prep == 'nucla' else 1
+        if frames.dim() != self.buf.dim() or tuple(frames.shape) != self.frames_shape(frames.shape[t]) or not frames.is_floating_point():
+            raise ValueError(f'FrameRing.push: frames must be {self.frames_shape("n")} floats, got {tuple(frames.shape)} {frames.dtype}')
+        if not 1 <= frames.shape[t] <= self.capacity:
+            raise ValueError(f'FrameRing.push: {frames.shape[t]} frames outside 1..capacity = {self.capacity}')
+        if self.prep == 'clip' and frames.dtype != torch.float32:
+            raise ValueError(f"FrameRing.push: prep='clip' takes fp32 frames, got {frames.dtype}")
+        ops.ring_push(frames.to(self.buf.dtype).contiguous(), self.buf, self.state)
+
+    def reset(self):
+        self.buf.zero_()
+        self.state.zero_()
+
+    @property
+    def count(self):
+        return int(self.state[0])
+
+
+def plan_offline(length, window, hop):
+    """[(start, L)] of SlidingWindow's pass over `length` frames (the rule in the module docstring)."""
+    if length < 1:
+        return []
+    if length < window:
+        return [(0, length)]
+    plan = [(s, window) for s in range(0, length - window + 1, hop)]
+    if plan[-1][0] + window < length:
+        plan.append((length - window, window))
+    return plan
+
+
+def _family_batch(model, frames_per_window, V, M):
+    """Windows per call that keep `model` on its small-batch eval family (Model.forward's routing bounds)."""
+    from . import f2, f2g, f2s, f2v
+    G = len(model.models) if hasattr(model, 'models') else 1        # a StreamEnsemble's grouped pass counts G N M
+    if type(model).__module__.endswith('stgcn'):
+        return max(1, f2s.F2S_MAX_FRAMES // (frames_per_window * M))
+    if V == 20:
+        return max(1, f2.F2_MAX_CLIPS // (G * M))
+    bound = f2v.F2V_MAX_FRAMES if V == 25 else f2v.F2J_MAX_FRAMES if V in f2v.JOINTS else f2g.F2G_MAX_FRAMES
+    return max(1, bound // (G * M * frames_per_window))
+
+
+class _StateWatch:
+    """evaluation._state_key(model) at the price a per-frame caller can pay.  The whole key walks the module tree (about a
+    millisecond of host time for a ten-block model: twice the forward it guards); most of that is the walk, not the reading.  So
+    the walk's result -- the tensors, the BatchNorm counters, the arenas -- is kept, and a call reads only what can move under
+    an unchanged tree: every tensor's address and version, the counters, the arenas' state versions.  That sees what
+    CapturedEval's key sees of an optimiser step, a CapturedStep replay, load_state_dict, an in-place edit, a train-mode
+    forward or model.to().  Replacing a parameter or sub-module OBJECT changes the tree itself: the whole key is compared
+    every `recheck` calls to catch that late, and invalidate() makes the next call catch it at once."""
+
+    def __init__(self, model, recheck=256):
+        self.model, self.recheck = model, recheck
+        self.walk()
+
+    def walk(self):
+        from . import functional as Fn
+        m = self.model
+        self.full = _state_key(m)
+        self.watch = list(m.parameters()) + list(m.buffers())
+        self.epochs = [Fn._bn_epoch(b) for b in m.modules() if isinstance(b, torch.nn.modules.batchnorm._BatchNorm)]
+        arenas = {}
+        for t in self.watch:
+            a = getattr(t, '_tamgcn_arena', None)
+            if a is not None:
+                arenas[id(a)] = a
+        self.arenas = list(arenas.values())
+        self.fast = self.read()
+        self.calls = 0
+
+    def read(self):
+        return (tuple((t.data_ptr(), t._version) for t in self.watch), tuple(e[0] for e in self.epochs),
+                tuple(v for a in self.arenas for v in a.state_version()))
+
+    def invalidate(self):
+        self.calls = self.recheck
+
+    def moved(self):
+        """True once per change: the watch then stands on the current state."""
+        self.calls += 1
+        if self.calls >= self.recheck:
+            before = self.full
+            self.walk()
+            return self.full != before
+        fast = self.read()
+        if fast == self.fast:
+            return False
+        self.walk()
+        return True
+
+
+class _Windows:
+    """What SlidingWindow and LiveClassifier share: the checked arguments and plan -> model input."""
+
+    def __init__(self, who, model, prep, time_steps, window_size, stream, parent, V, C, M):
+        if prep not in PREPS:
+            raise ValueError(f'{who}: prep {prep!r} (one of {PREPS})')
+        if stream not in ops.STREAM_MODES:
+            raise ValueError(f'{who}: unknown stream {stream!r} (one of {sorted(ops.STREAM_MODES)})')
+        if getattr(model, 'training', False):
+            raise ValueError(f'{who}: put the model in eval() mode first')
+        if getattr(model, 'arrangement', None) == 'streams':
+            raise ValueError(f"{who}: a StreamEnsemble with arrangement='streams' forks HIP streams inside the captured graph; "
+                             "the chain stays on one stream (arrangement None, 'grouped' or 'serial')")
+        if hasattr(model, 'streams') and stream != 'joint':
+            raise ValueError(f"{who}: a StreamEnsemble derives its own streams from the joint windows; stream = {stream!r}")
+        if prep == 'nucla':
+            if window_size is not None:
+                raise ValueError(f"{who}: prep='nucla' resamples to time_steps frames; window_size belongs to prep='clip'")
+            self.T = _int('time_steps', 52 if time_steps is None else time_steps, 1, who)
+            if self.T > ops.STREAM_MAX_TS:
+                raise ValueError(f'{who}: time_steps = {self.T} above {ops.STREAM_MAX_TS}')
+        else:
+            if time_steps is not None:
+                raise ValueError(f"{who}: prep='clip' resizes to window_size frames; time_steps belongs to prep='nucla'")
+            self.T = _int('window_size', window_size, 1, who)
+        self.model, self.prep, self.stream = model, prep, stream
+        self.V, self.C, self.M = V, C, M
+        self._parent_arg, self.parent = parent, None
+
+    def bind(self, dev):
+        """The bone-parent table on the device (once)."""
+        if self.parent is not None and self.parent.device == dev:
+            return
+        parent = self._parent_arg
+        if parent is None:
+            if self.prep == 'nucla' and self.V == 20:
+                from .feeder.feeder_nucla_gcn import BONE_PARENT
+                parent = BONE_PARENT
+            else:
+                first = self.model.models[0] if hasattr(self.model, 'models') else self.model
+                parent = default_parent(first.graph)
+        parent = [int(p) for p in (parent.tolist() if torch.is_tensor(parent) else parent)]
+        if len(parent) != self.V or any(p < 0 or p >= self.V for p in parent):
+            raise ValueError(f'parent must hold {self.V} joint indices in [0, {self.V})')
+        self.parent = torch.tensor(parent, dtype=torch.int32, device=dev)
+
+    def build(self, ring, plan):
+        """ring tensor, plan int64 (B, 2) -> the model's input (B, C, T, V, M) of the configured stream."""
+        if self.prep == 'nucla':
+            return ops.window_nucla(ring, plan, self.parent, self.T, NUCLA_CENTER_JOINT, self.stream)
+        return ops.stream_derive(ops.window_clip(ring, plan, self.T), self.parent, self.stream)
+
+    def forward_one_stream(self, fn, x):
+        """fn(x) with a StreamEnsemble that was left to choose kept on the grouped, one-stream arrangement (CapturedEval's rule)."""
+        m = self.model
+        if getattr(m, 'arrangement', 0) is not None:
+            return fn(x)
+        m.arrangement = 'grouped'
+        try:
+            return fn(x)
+        finally:
+            m.arrangement = None
+
+
+SlidingResult = collections.namedtuple('SlidingResult', 'window_logits window_probs frame_scores frame_label plan')
+
+
+class SlidingWindow:
+    """model in eval() mode (a Model or a one-stream-arrangement StreamEnsemble); window, hop in frames; prep and its
+    time_steps (default 52) or window_size; stream of ops.STREAM_MODES; parent: bone parents (default: the N-UCLA feeder's
+    table for prep='nucla' at V = 20, else the model graph's); batch_windows: windows per forward call (default: what keeps the
+    model on its small-batch eval family).
+
+    run(seq) -> SlidingResult(window_logits (n, K), window_probs (n, K), frame_scores (len, K), frame_label (len,), plan (n, 2)),
+    all on the device.  seq is the whole sequence, (len, V, 3) for 'nucla', (C, len, V, M) fp32 for 'clip', on the device or the
+    host.  The plan is made on the host from len alone; the windows run in fixed-shape chunks of batch_windows, the last padded
+    with invalid (all-zero) windows, through GraphedForward under torch.no_grad()."""
+
+    def __init__(self, model, window, hop, prep='nucla', time_steps=None, window_size=None, stream='joint', parent=None,
+                 batch_windows=None):
+        who = 'SlidingWindow'
+        self.window, self.hop = _int('window', window, 1, who), _int('hop', hop, 1, who)
+        if batch_windows is not None:
+            _int('batch_windows', batch_windows, 1, who)
+        first = model.models[0] if hasattr(model, 'models') else model
+        V = getattr(first, 'num_point', None)
+        if not isinstance(V, int):
+            raise ValueError(f'{who}: the model has no num_point (a models.ctrgcn.Model, models.stgcn.Model or StreamEnsemble is expected)')
+        self._w = _Windows(who, model, prep, time_steps, window_size, stream, parent, V, None, None)
+        self.batch_windows = batch_windows
+        self._fwd = GraphedForward(model)
+        self._watch = _StateWatch(model)
+
+    def _seq(self, seq):
+        w = self._w
+        if not torch.is_tensor(seq):
+            seq = torch.as_tensor(seq)
+        if w.prep == 'nucla':
+            ok = seq.dim() == 3 and seq.shape[1:] == (w.V, 3) and seq.is_floating_point()
+        else:
+            ok = seq.dim() == 4 and seq.shape[2] == w.V and seq.dtype == torch.float32
+        if not ok or seq.numel() == 0:
+            form = f'(len, {w.V}, 3) floats' if w.prep == 'nucla' else f'(C, len, {w.V}, M) fp32'
+            raise ValueError(f'SlidingWindow.run: the sequence must be a non-empty {form} tensor, got {tuple(seq.shape)} {seq.dtype}')
+        if not seq.is_cuda:
+            seq = seq.to(next(self._w.model.parameters()).device)
+            if not seq.is_cuda:
+                raise RuntimeError('SlidingWindow.run: the model is not on the GPU; there is no CPU path')
+        return seq.to(torch.float64 if w.prep == 'nucla' else torch.float32).contiguous()
+
+    def run(self, seq):
+        w = self._w
+        seq = self._seq(seq)
+        dev = seq.device
+        w.bind(dev)
+        length = seq.shape[0] if w.prep == 'nucla' else seq.shape[1]
+        M = 1 if w.prep == 'nucla' else seq.shape[3]
+        rows = plan_offline(length, self.window, self.hop)
+        n = len(rows)
+        bw = self.batch_windows or _family_batch(w.model, w.T, w.V, M)
+        chunks = -(-n // bw)
+        plan = torch.zeros(chunks * bw, 2, dtype=torch.int64)
+        plan[:n] = torch.tensor(rows, dtype=torch.int64)
+        plan = plan.to(dev)
+        if w.model.training:
+            raise RuntimeError('SlidingWindow.run: the model is in train() mode; call model.eval() first')
+        if self._watch.moved():                                     # the forward graph holds the folded coefficients of one state
+            self._fwd.reset()
+        logits = None
+        with torch.no_grad():
+            for c in range(chunks):
+                rows_c = plan[c * bw:(c + 1) * bw]
+                out = w.forward_one_stream(self._fwd, w.build(seq, rows_c))
+                if logits is None:
+                    if out.dim() != 2 or out.shape[0] != bw:
+                        raise ValueError(f'SlidingWindow: the model returned {tuple(out.shape)}, expected ({bw}, num_class)')
+                    logits = torch.empty(chunks * bw, out.shape[1], dtype=torch.float32, device=dev)
+                logits[c * bw:(c + 1) * bw].copy_(out)              # out is the graph's own tensor
+        logits, plan = logits[:n], plan[:n]
+        probs, scores, label = ops.window_vote(logits, plan, n_frames=length)
+        return SlidingResult(logits, probs, scores, label, plan)
+
+
+class LiveClassifier:
+    """model in eval() mode; ring: the FrameRing the frames go to (its prep decides the window form); window frames per window;
+    per step hop_windows windows `hop` frames apart (default hop = window), the newest last; beta in [0, 1): the moving average
+    ema = beta ema + (1 - beta) probs over the valid windows in the order they are seen (0: the newest window's softmax);
+    time_steps / window_size, stream, parent as SlidingWindow's; eager=True runs the chain launch by launch instead of
+    replaying a graph (the same bits).
+
+    step(frames) takes the same n frames per call -- frames_per_step, default 1 -- in the ring's push form, copies them into
+    the chain's input and runs push -> plan -> window -> derive -> forward -> softmax -> average.  -> (label int64 [1], conf
+    fp32 [1], smoothed fp32 [K], logits fp32 (hop_windows, K)): device tensors, no synchronisation; they are the graph's own
+    outputs, overwritten by the next step (clone to keep them).  label is -1 until the first valid window.
+
+    CapturedEval's rules: step() raises while the model is in train() mode; the model's state key (evaluation._state_key, read
+    per step through _StateWatch: see there for what a step sees at once) is compared per step and the chain is captured again
+    when it moved (`captures` counts; such a step synchronises); a StreamEnsemble stays on one stream.  reset() clears the ring,
+    the average and its count; invalidate() makes the next step compare the whole key (after replacing a parameter object)."""
+
+    def __init__(self, model, ring, window, hop_windows=1, hop=None, beta=0.0, time_steps=None, window_size=None, stream='joint',
+                 parent=None, frames_per_step=1, eager=False):
+        who = 'LiveClassifier'
+        if not isinstance(ring, FrameRing):
+            raise ValueError(f'{who}: ring must be a FrameRing')
+        self.window, self.B = _int('window', window, 1, who), _int('hop_windows', hop_windows, 1, who)
+        self.hop = _int('hop', window if hop is None else hop, 1, who)
+        self.n = _int('frames_per_step', frames_per_step, 1, who)
+        if not (isinstance(beta, (int, float)) and 0.0 <= beta < 1.0):
+            raise ValueError(f'{who}: beta = {beta!r} outside [0, 1)')
+        need = self.window + (self.B - 1) * self.hop
+        if ring.capacity < need:
+            raise ValueError(f'{who}: the ring holds {ring.capacity} frames, window + (hop_windows - 1) hop = {need} are needed')
+        if self.n > ring.capacity:
+            raise ValueError(f'{who}: frames_per_step = {self.n} above the ring\'s capacity {ring.capacity}')
+        first = model.models[0] if hasattr(model, 'models') else model
+        if getattr(first, 'num_point', None) != ring.V:
+            raise ValueError(f'{who}: the model has {getattr(first, "num_point", None)} joints, the ring {ring.V}')
+        self._w = _Windows(who, model, ring.prep, time_steps, window_size, stream, parent, ring.V, ring.C, ring.M)
+        self.model, self.ring, self.beta, self.eager = model, ring, float(beta), bool(eager)
+        dev = ring.buf.device
+        self._w.bind(dev)
+        self._frames = torch.zeros(ring.frames_shape(self.n), dtype=ring.buf.dtype, device=dev)
+        with torch.no_grad():
+            K = self._warm().shape[1]
+        if K > ops.STREAM_MAX_K:
+            raise ValueError(f'{who}: {K} classes above {ops.STREAM_MAX_K}')
+        self.num_class = K
+        self.ema = torch.zeros(K, dtype=torch.float64, device=dev)
+        self.seen = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._graph = self._out = self._keep = None
+        self._watch = _StateWatch(model)
+        self.captures = 0
+        if not self.eager:
+            self._capture()
+
+    def _logits(self):
+        """plan -> window -> derive -> forward on the ring as it stands: (plan, logits)."""
+        w = self._w
+        plan = ops.ring_plan(self.ring.state, self.ring.capacity, self.B, self.window, self.hop)
+        logits = w.forward_one_stream(self.model, w.build(self.ring.buf, plan))
+        if logits.dim() != 2 or logits.shape[0] != self.B:
+            raise ValueError(f'LiveClassifier: the model returned {tuple(logits.shape)}, expected ({self.B}, num_class)')
+        return plan, logits
+
+    def _warm(self):
+        """The read-only part of the chain (nothing of the ring or the average moves): allocator, engines, folded coefficients."""
+        return self._logits()[1]
+
+    def _chain(self):
+        ops.ring_push(self._frames, self.ring.buf, self.ring.state)
+        plan, logits = self._logits()
+        probs, _, _ = ops.window_vote(logits, plan)
+        for j in range(self.B):                                       # oldest first
+            smoothed, label, conf = ops.score_ema(probs[j], plan[j], self.beta, self.ema, self.seen)
+        return label, conf, smoothed, logits
+
+    def _capture(self):
+        dev = self.ring.buf.device
+        told = hasattr(self.model, '_tamgcn_graphed')                 # GraphedForward's note to a StreamEnsemble
+        if told:
+            before, self.model._tamgcn_graphed = self.model._tamgcn_graphed, True
+        try:
+            with torch.no_grad():
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(side):
+                    for _ in range(2):
+                        self._warm()
+                torch.cuda.current_stream(dev).wait_stream(side)
+                g = torch.cuda.CUDAGraph()
+                try:
+                    with torch.cuda.graph(g):
+                        out = self._chain()
+                except Exception as e:                                # noqa: BLE001  -- no silent eager fall-back
+                    raise RuntimeError(f'LiveClassifier: HIP graph capture failed ({type(e).__name__}: {e})') from e
+        finally:
+            if told:
+                self.model._tamgcn_graphed = before
+        # what the graph reads through pointers and the eval caches own (GraphedForward._capture_told has the reasons)
+        keep = [dict(m.__dict__['_tamgcn_eval_cache']) for m in self.model.modules() if '_tamgcn_eval_cache' in m.__dict__]
+        for slot in ENGINE_SLOTS:
+            eng = self.model.__dict__.get(slot)
+            if eng:
+                keep.append(eng._blocks)
+        hook = getattr(self.model, '_tamgcn_keep_alive', None)
+        if hook is not None:
+            keep.append(hook())
+        self._graph, self._out, self._keep = g, out, keep
+        self.captures += 1
+
+    def step(self, frames):
+        if self.model.training:
+            raise RuntimeError('LiveClassifier: the model is in train() mode; call model.eval() before a step')
+        if not torch.is_tensor(frames) or not frames.is_cuda:
+            raise RuntimeError('LiveClassifier.step: expected a HIP (cuda) tensor; there is no CPU path')
+        if tuple(frames.shape) != tuple(self._frames.shape) or not frames.is_floating_point():
+            raise ValueError(f'LiveClassifier.step: frames must be {tuple(self._frames.shape)} floats, got {tuple(frames.shape)} {frames.dtype}')
+        moved = self._watch.moved()
+        self._frames.copy_(frames)
+        with torch.no_grad():
+            if self.eager:                                            # an eager chain folds a new state by itself
+                return self._chain()
+            if moved or self._graph is None:
+                self._capture()
+        self._graph.replay()
+        return self._out
+
+    def invalidate(self):
+        self._watch.invalidate()
+
+    def reset(self):
+        self.ring.reset()
+        self.ema.zero_()
+        self.seen.zero_()
