@@ -883,6 +883,26 @@ int tamgcn_f2s_supported(int V, int K, int Cin, int Cout, int KT, int stride);
 int tamgcn_f2s_gcn(const tamgcn_f2s_gcn_desc* d, void* stream);
 int tamgcn_f2s_tcn(const tamgcn_f2s_tcn_desc* d, void* stream);
 
+/* ---- f2s grouped: both stages for `groups` ST-GCN models of ONE geometry in one launch (a multi-stream ensemble of ST-GCN
+ * models: tam_gcn_amd.f2s.GroupedEvalST under tam_gcn_amd.inference.StreamEnsemble).  The contract of the "grouped" block above,
+ * on the f2s descriptors, unchanged, plus `int groups`:
+ *   samples      d->N is the TOTAL number of clip-persons, N % groups == 0; samples [g N/groups, (g+1) N/groups) belong to group g
+ *   activations  x, h, out: the layouts above, indexed by the total sample
+ *   parameters   every parameter pointer of the descriptor is group 0's; group g's array follows densely at g times the array's
+ *                own size:  Ae K*V*V,  wg K*Cout*Cin,  bg Cout*V;  wt Cout*Cout*9,  bt Cout,  wr Cout*Cin,  br Cout.  An absent
+ *                wr / br is absent for every group.
+ *   alignment    whether wg, wt and wr are read in 16-byte pieces is decided from group 0's pointer, so where one is, its group
+ *                stride must be a multiple of four floats; with Cin % 4 == 0 (wg, wr) and Cout % 16 == 0 (wt) it always is, and
+ *                it is checked.
+ * All groups share one geometry (V, K, Cin, Cout, stride, res_mode); g = sample / (N / groups) is uniform per workgroup and the
+ * parameter pointers are offset once, at the top of the SAME kernel text (a template flag).  Arithmetic, tiling, wave split and
+ * summation order are those of the plain entry points: group g's outputs are bit-equal to a plain call on group g's slice and
+ * parameters.  Refused on the host before any launch: groups < 1, N % groups != 0, N > 65535 and 2^31 elements or more (both on
+ * the TOTAL: the grid's z is the total sample), and whatever the plain entry points refuse.
+ * Added in ABI 401 without a version bump: new entry points only. */
+int tamgcn_f2s_gcn_grouped(const tamgcn_f2s_gcn_desc* d, int groups, void* stream);
+int tamgcn_f2s_tcn_grouped(const tamgcn_f2s_tcn_desc* d, int groups, void* stream);
+
 /* ---- f2s backward: the DATA gradient of that block (tam_gcn_amd/csrc/f2s_bwd.hip), again two launches, for gradient saliency
  * (tam_gcn_amd/saliency.py; reference tools/train_stgcn_group.py:264-356).  In eval mode the block is piecewise linear in x; the
  * two ReLU masks are read from the forward's own h and out, strictly (> 0, as torch).  No weight gradient; x, the biases and bg

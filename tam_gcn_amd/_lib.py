@@ -273,6 +273,8 @@ SIGNATURES = {
     'tamgcn_f2s_supported': (_i, [_i, _i, _i, _i, _i, _i]),
     'tamgcn_f2s_gcn': (_i, [C.POINTER(F2sGcnDesc), _p]),
     'tamgcn_f2s_tcn': (_i, [C.POINTER(F2sTcnDesc), _p]),
+    'tamgcn_f2s_gcn_grouped': (_i, [C.POINTER(F2sGcnDesc), _i, _p]),
+    'tamgcn_f2s_tcn_grouped': (_i, [C.POINTER(F2sTcnDesc), _i, _p]),
     'tamgcn_f2s_tcn_bwd': (_i, [C.POINTER(F2sTcnBwdDesc), _p]),
     'tamgcn_f2s_gcn_bwd': (_i, [C.POINTER(F2sGcnBwdDesc), _p]),
     'tamgcn_saliency_joints': (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),

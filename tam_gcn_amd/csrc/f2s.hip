@@ -2,6 +2,8 @@
 //
 //   tamgcn_f2s_gcn   h = relu( sum_k (Wg_k x) Ae_k + bg )          graph convolution, tcn.0 (BatchNorm) and the ReLU folded
 //   tamgcn_f2s_tcn   out = relu( Wt * h + bt + res )               9 x 1 temporal conv, tcn.3 folded, residual, ReLU
+//   tamgcn_f2s_gcn_grouped, tamgcn_f2s_tcn_grouped                 the same for `groups` models of one geometry in one launch
+//                                                                  (include/tamgcn.h "f2s grouped"): the same kernel text, GROUPED
 //
 // Both are GEMMs on v_mfma_f32_16x16x4_f32 (exact fp32) whose columns are the FLAT (frame, joint) index of a frame tile:
 // x, h and out are contiguous (N, C, T, V), so the 16 columns of a B fragment are 16 consecutive floats of a channel row
@@ -25,14 +27,17 @@
 
 namespace {
 
+// npg: samples per group of a grouped launch (include/tamgcn.h "f2s grouped"); the plain kernels do not read it
 struct FsGcnArgs {
-    int N, Cin, Cout, T, V, tf;
+    int N, Cin, Cout, T, V, tf, npg;
     bool vec;
     const float* x; const float* Ae; const float* wg; const float* bg;
     float* h;
 };
 
-template <int K>
+// GROUPED: samples [g npg, (g + 1) npg) read the g-th of the parameter arrays that follow one another densely behind group 0's.
+// g comes from blockIdx.z alone, so the offset bases stay scalar; everything below is the plain kernel's.
+template <int K, bool GROUPED>
 __global__ __launch_bounds__(FS_NT) void f2s_gcn_kernel(FsGcnArgs a) {
     __shared__ float ys[K * FS_CT * FS_YP];
     __shared__ float as[K * 32 * FS_AP];
@@ -42,6 +47,12 @@ __global__ __launch_bounds__(FS_NT) void f2s_gcn_kernel(FsGcnArgs a) {
     const int t0 = blockIdx.x * a.tf, c0 = blockIdx.y * FS_CT, n = blockIdx.z;
     const int tf = min(a.tf, T - t0);
     const int ncols = tf * V;
+    if (GROUPED) {
+        const int g = n / a.npg;
+        a.Ae += g * K * V * V;
+        a.wg += (long long)g * K * a.Cout * Cin;
+        a.bg += g * a.Cout * V;
+    }
 
     // Ae -> LDS, zero outside V x V; y's rows zeroed (the pad joints stay zero, the partial sums start from zero)
     for (int i = tid; i < K * 32 * FS_AP; i += FS_NT) {
@@ -140,12 +151,13 @@ __global__ __launch_bounds__(FS_NT) void f2s_gcn_kernel(FsGcnArgs a) {
 }
 
 struct FsTcnArgs {
-    int N, Cin, Cout, T, T2, V, stride, res_mode, tf;
+    int N, Cin, Cout, T, T2, V, stride, res_mode, tf, npg;
     bool vect, vecr;
     const float* h; const float* wt; const float* bt; const float* x; const float* wr; const float* br;
     float* out;
 };
 
+template <bool GROUPED>
 __global__ __launch_bounds__(FS_NT) void f2s_tcn_kernel(FsTcnArgs a) {
     __shared__ float red[FS_CT * FS_RP];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -154,6 +166,15 @@ __global__ __launch_bounds__(FS_NT) void f2s_tcn_kernel(FsTcnArgs a) {
     const int t0 = blockIdx.x * a.tf, c0 = blockIdx.y * FS_CT, n = blockIdx.z;
     const int tf = min(a.tf, a.T2 - t0);
     const int ncols = tf * V;
+    if (GROUPED) {                                                           // as in f2s_gcn_kernel
+        const int g = n / a.npg;
+        a.wt += (long long)g * C * C * FS_KT;
+        a.bt += g * C;
+        if (a.res_mode == 2) {
+            a.wr += (long long)g * C * a.Cin;
+            a.br += g * C;
+        }
+    }
 
     int col[FS_NP], fr0[FS_NP], off0[FS_NP]; bool cok[FS_NP];
 #pragma unroll
@@ -257,8 +278,25 @@ __global__ __launch_bounds__(FS_NT) void f2s_tcn_kernel(FsTcnArgs a) {
 
 extern "C" int tamgcn_f2s_supported(int V, int K, int Cin, int Cout, int KT, int stride) { return fs_geometry_ok(V, K, Cin, Cout, KT, stride); }
 
-extern "C" int tamgcn_f2s_gcn(const tamgcn_f2s_gcn_desc* d, void* stream) {
-    const char* who = "tamgcn_f2s_gcn";
+namespace {
+
+// groups == 0: the plain entry point; otherwise the grouped one (d->N the total, every check on the total).
+int fs_groups_ok(int N, int groups, const char* who) {
+    TG_CHECK(groups >= 1 && N % groups == 0, "%s: N=%d is not a multiple of groups=%d", who, N, groups);
+    return 0;
+}
+int fs_group_stride_ok(bool vec, long long stride, const char* who, const char* what) {
+    TG_CHECK(!vec || stride % 4 == 0, "%s: group stride of %s (%lld floats) breaks the 16-byte alignment of its vector path", who, what, stride);
+    return 0;
+}
+
+template <int K>
+void fs_gcn_run(const FsGcnArgs& a, bool grouped, const dim3& grid, hipStream_t st) {
+    if (grouped) hipLaunchKernelGGL((f2s_gcn_kernel<K, true>), grid, dim3(FS_NT), 0, st, a);
+    else hipLaunchKernelGGL((f2s_gcn_kernel<K, false>), grid, dim3(FS_NT), 0, st, a);
+}
+
+int fs_gcn_launch(const tamgcn_f2s_gcn_desc* d, int groups, void* stream, const char* who) {
     TG_CHECK(d, "%s: null descriptor", who);
     TG_CHECK(d->x && d->Ae && d->wg && d->bg && d->h, "%s: null pointer", who);
     TG_CHECK(d->N >= 1 && d->T >= 1 && d->N <= 65535, "%s: bad dims N=%d T=%d", who, d->N, d->T);
@@ -269,18 +307,19 @@ extern "C" int tamgcn_f2s_gcn(const tamgcn_f2s_gcn_desc* d, void* stream) {
     FsGcnArgs a;
     a.N = d->N; a.Cin = d->Cin; a.Cout = d->Cout; a.T = d->T; a.V = d->V; a.tf = fs_tf(d->V);
     a.vec = d->Cin % 4 == 0 && fs_al16(d->wg);
+    if (groups && (fs_groups_ok(d->N, groups, who) || fs_group_stride_ok(a.vec, (long long)d->K * d->Cout * d->Cin, who, "wg"))) return -1;
+    a.npg = groups ? d->N / groups : d->N;
     a.x = d->x; a.Ae = d->Ae; a.wg = d->wg; a.bg = d->bg; a.h = d->h;
     const dim3 grid(ceil_div(d->T, a.tf), d->Cout / FS_CT, d->N);
-    if (d->K == 1) hipLaunchKernelGGL(f2s_gcn_kernel<1>, grid, dim3(FS_NT), 0, (hipStream_t)stream, a);
-    else if (d->K == 2) hipLaunchKernelGGL(f2s_gcn_kernel<2>, grid, dim3(FS_NT), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(f2s_gcn_kernel<3>, grid, dim3(FS_NT), 0, (hipStream_t)stream, a);
-    tamgcn_note_kernel("f2s_gcn_kernel<%d>", d->K);
+    if (d->K == 1) fs_gcn_run<1>(a, groups != 0, grid, (hipStream_t)stream);
+    else if (d->K == 2) fs_gcn_run<2>(a, groups != 0, grid, (hipStream_t)stream);
+    else fs_gcn_run<3>(a, groups != 0, grid, (hipStream_t)stream);
+    tamgcn_note_kernel(groups ? "f2s_gcn_grouped_kernel<%d>" : "f2s_gcn_kernel<%d>", d->K);
     TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-extern "C" int tamgcn_f2s_tcn(const tamgcn_f2s_tcn_desc* d, void* stream) {
-    const char* who = "tamgcn_f2s_tcn";
+int fs_tcn_launch(const tamgcn_f2s_tcn_desc* d, int groups, void* stream, const char* who) {
     TG_CHECK(d, "%s: null descriptor", who);
     TG_CHECK(d->h && d->wt && d->bt && d->out, "%s: null pointer", who);
     TG_CHECK(d->N >= 1 && d->T >= 1 && d->N <= 65535, "%s: bad dims N=%d T=%d", who, d->N, d->T);
@@ -298,10 +337,32 @@ extern "C" int tamgcn_f2s_tcn(const tamgcn_f2s_tcn_desc* d, void* stream) {
     a.res_mode = d->res_mode; a.tf = fs_tf(d->V);
     a.vect = fs_al16(d->wt);                                                 // rows of 9 * Cout floats: a multiple of 16
     a.vecr = d->res_mode == 2 && Cin % 4 == 0 && fs_al16(d->wr);
+    if (groups && (fs_groups_ok(d->N, groups, who) || fs_group_stride_ok(a.vect, (long long)d->Cout * d->Cout * FS_KT, who, "wt") ||
+                   fs_group_stride_ok(a.vecr, (long long)d->Cout * Cin, who, "wr")))
+        return -1;
+    a.npg = groups ? d->N / groups : d->N;
     a.h = d->h; a.wt = d->wt; a.bt = d->bt; a.x = d->x; a.wr = d->wr; a.br = d->br; a.out = d->out;
     const dim3 grid(ceil_div(a.T2, a.tf), d->Cout / FS_CT, d->N);
-    hipLaunchKernelGGL(f2s_tcn_kernel, grid, dim3(FS_NT), 0, (hipStream_t)stream, a);
-    tamgcn_note_kernel("f2s_tcn_kernel");
+    if (groups) hipLaunchKernelGGL(f2s_tcn_kernel<true>, grid, dim3(FS_NT), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(f2s_tcn_kernel<false>, grid, dim3(FS_NT), 0, (hipStream_t)stream, a);
+    tamgcn_note_kernel(groups ? "f2s_tcn_grouped_kernel" : "f2s_tcn_kernel");
     TG_LAUNCH_CHECK(who);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int tamgcn_f2s_gcn(const tamgcn_f2s_gcn_desc* d, void* stream) { return fs_gcn_launch(d, 0, stream, "tamgcn_f2s_gcn"); }
+extern "C" int tamgcn_f2s_tcn(const tamgcn_f2s_tcn_desc* d, void* stream) { return fs_tcn_launch(d, 0, stream, "tamgcn_f2s_tcn"); }
+
+// include/tamgcn.h "f2s grouped": `groups` models of one geometry in the same launch
+extern "C" int tamgcn_f2s_gcn_grouped(const tamgcn_f2s_gcn_desc* d, int groups, void* stream) {
+    const char* who = "tamgcn_f2s_gcn_grouped";
+    TG_CHECK(groups >= 1, "%s: groups=%d", who, groups);
+    return fs_gcn_launch(d, groups, stream, who);
+}
+extern "C" int tamgcn_f2s_tcn_grouped(const tamgcn_f2s_tcn_desc* d, int groups, void* stream) {
+    const char* who = "tamgcn_f2s_tcn_grouped";
+    TG_CHECK(groups >= 1, "%s: groups=%d", who, groups);
+    return fs_tcn_launch(d, groups, stream, who);
 }

@@ -319,19 +319,20 @@ def _(x, xpart, params, geom, groups):
 # ----------------------------------------------------------------------------------------------------------------------
 # G models as one launch sequence
 # ----------------------------------------------------------------------------------------------------------------------
-def stack_blocks(per_model):
-    """per_model: G lists of _Block (one per TCN_GCN_unit) of ONE geometry -> per block (stacked params, geom).
-    ValueError naming the first field in which a model differs from model 0."""
+def stack_blocks(per_model, label='l{}'):
+    """per_model: G lists of _Block (one per TCN_GCN_unit; f2s._BlockST: one per st_gcn) of ONE geometry -> per block (stacked
+    params, geom).  ValueError naming the first field in which a model differs from model 0; label: how block i (from 1) is named."""
     out = []
     for i, blks in enumerate(zip(*per_model), 1):
+        i = label.format(i)
         b0 = blks[0]
         for g, b in enumerate(blks[1:], 1):
             for field in ('Cin', 'Cout', 'geom'):
                 if getattr(b, field) != getattr(b0, field):
-                    raise ValueError(f'grouped eval: model {g} differs from model 0 in l{i}.{field}: '
+                    raise ValueError(f'grouped eval: model {g} differs from model 0 in {i}.{field}: '
                                      f'{getattr(b, field)} != {getattr(b0, field)}')
             if [tuple(t.shape) for t in b.params] != [tuple(t.shape) for t in b0.params]:
-                raise ValueError(f'grouped eval: model {g} differs from model 0 in the parameter shapes of l{i}')
+                raise ValueError(f'grouped eval: model {g} differs from model 0 in the parameter shapes of {i}')
         out.append(([torch.stack([b.params[j] for b in blks]) for j in range(len(b0.params))], list(b0.geom)))
     return out
 
@@ -353,25 +354,40 @@ class GroupedEval:
                                                         # -> (G, N, K): model g on stream modes[g] of x
 
     Every model keeps its own FusedEval(V) for the folding and the state key: a model whose state changed is folded again and
-    only its slice of the stacked tensors is rewritten."""
+    only its slice of the stacked tensors is rewritten.
+
+    f2s.GroupedEvalST derives the ST-GCN engine from this one: NAME, LABEL, _fields, _family, _fc and run are what it sets."""
+    NAME = 'GroupedEval'
+    LABEL = 'l{}'                                                  # how block i (from 1) is named in a message
+    _fields = staticmethod(_model_fields)
 
     def __init__(self, models):
         models = list(models)
+        who = self.NAME
         if not models:
-            raise ValueError('GroupedEval: no models')
+            raise ValueError(f'{who}: no models')
         for g, m in enumerate(models):
             if m.training:
-                raise ValueError(f'GroupedEval: model {g} is in train mode; put every model in eval() mode first')
+                raise ValueError(f'{who}: model {g} is in train mode; put every model in eval() mode first')
         devs = [next(m.parameters()).device for m in models]
         for g, d in enumerate(devs):
             if d != devs[0]:
-                raise ValueError(f'GroupedEval: model {g} is on {d}, model 0 on {devs[0]}')
-        f0 = _model_fields(models[0])
+                raise ValueError(f'{who}: model {g} is on {d}, model 0 on {devs[0]}')
+        f0 = self._fields(models[0])
         for g, m in enumerate(models[1:], 1):
-            for (name, a), (_, b) in zip(f0, _model_fields(m)):
+            for (name, a), (_, b) in zip(f0, self._fields(m)):
                 if a != b:
-                    raise ValueError(f'GroupedEval: model {g} differs from model 0 in {name}: {b} != {a}')
+                    raise ValueError(f'{who}: model {g} differs from model 0 in {name}: {b} != {a}')
         V = f0[0][1]
+        cls = self._family(V)
+        self.V, self.M, self.K = V, f0[3][1], f0[1][1]
+        self.models = models
+        self.engines = [cls(m) for m in models]
+        self._seen = [None] * len(models)                          # the _blocks list of each engine the stacks were built from
+        self._stacked = self._coef = self._fcw = self._fcb = None
+
+    def _family(self, V):
+        """The per-model engine class for V joints; sets FAMILY and the grouped block operator."""
         from . import f2v
         if V == 20:
             cls, self.FAMILY = FusedEval, 'f2'
@@ -384,11 +400,12 @@ class GroupedEval:
             self._blk = torch.ops.tamgcn.tcn_gcn_unit_eval_vj_grouped
         else:
             raise Unsupported(f'{V} joints (the small-batch kernels are built for V = 20 and V in {f2v.JOINTS})')
-        self.V, self.M, self.K = V, f0[3][1], f0[1][1]
-        self.models = models
-        self.engines = [cls(m) for m in models]
-        self._seen = [None] * len(models)                          # the _blocks list of each engine the stacks were built from
-        self._stacked = self._coef = self._fcw = self._fcb = None
+        return cls
+
+    @staticmethod
+    def _fc(m):
+        """The classifier of model m as (weight (K, C), bias (K))."""
+        return m.fc.weight.detach(), m.fc.bias.detach()
 
     def keep_alive(self):
         """What a captured graph reads through raw pointers (inference.GraphedForward keeps it)."""
@@ -398,29 +415,38 @@ class GroupedEval:
         bn = Fn.BN(m.data_bn)
         return Fn._eval_cached(m.data_bn, 'stem', [bn], lambda: Fn._eval_coefs([(bn, 0)], bn.C, like))[0]
 
+    def _restack(self, per_model):
+        """The blocks alone (no device needed): the first call stacks them (geometry checks), a later one rewrites in place the
+        slice of every model whose folded blocks are not the ones seen last.  -> the indices of the models written."""
+        if self._stacked is None:
+            self._stacked = stack_blocks(per_model, self.LABEL)
+            return list(range(len(per_model)))
+        moved = [g for g, blks in enumerate(per_model) if blks is not self._seen[g]]
+        for g in moved:
+            for i, (b, (stk, geom)) in enumerate(zip(per_model[g], self._stacked), 1):
+                if list(b.geom) != geom or [tuple(t.shape) for t in b.params] != [tuple(t.shape[1:]) for t in stk]:
+                    raise ValueError(f'grouped eval: model {g} no longer has the geometry of its group in {self.LABEL.format(i)}')
+                for dst, src in zip(stk, b.params):
+                    if src.numel():
+                        dst[g].copy_(src)
+        return moved
+
     def _packed(self, device):
         per_model = [e._packed(device) for e in self.engines]      # folds again whichever model's state key changed
         with torch.no_grad():
-            if self._stacked is None:
-                self._stacked = stack_blocks(per_model)            # geometry checks: before anything is launched
-                like = per_model[0][0].sy
+            first = self._stacked is None
+            moved = self._restack(per_model)                       # geometry checks: before anything is launched
+            if first:
+                like = per_model[0][0].params[0]
                 self._coef = torch.stack([self._stem_coef(m, like) for m in self.models]).contiguous()
-                self._fcw = torch.stack([m.fc.weight.detach() for m in self.models]).contiguous()
-                self._fcb = torch.stack([m.fc.bias.detach() for m in self.models]).contiguous()
+                self._fcw = torch.stack([self._fc(m)[0] for m in self.models]).contiguous()
+                self._fcb = torch.stack([self._fc(m)[1] for m in self.models]).contiguous()
             else:
-                for g, blks in enumerate(per_model):
-                    if blks is self._seen[g]:
-                        continue
-                    for i, (b, (stk, geom)) in enumerate(zip(blks, self._stacked), 1):
-                        if list(b.geom) != geom or [tuple(t.shape) for t in b.params] != [tuple(t.shape[1:]) for t in stk]:
-                            raise ValueError(f'grouped eval: model {g} no longer has the geometry of its group in l{i}')
-                        for dst, src in zip(stk, b.params):
-                            if src.numel():
-                                dst[g].copy_(src)
+                for g in moved:
                     m = self.models[g]
                     self._coef[g].copy_(self._stem_coef(m, self._coef))
-                    self._fcw[g].copy_(m.fc.weight.detach())
-                    self._fcb[g].copy_(m.fc.bias.detach())
+                    self._fcw[g].copy_(self._fc(m)[0])
+                    self._fcb[g].copy_(self._fc(m)[1])
             self._seen = per_model
         return self._stacked
 
@@ -428,11 +454,11 @@ class GroupedEval:
         """-> x as (N, C, T, V, M); the guards of FusedEval.blocks, before anything is launched."""
         for g, m in enumerate(self.models):
             if m.training:
-                raise RuntimeError(f'GroupedEval: model {g} went back to train() mode')
+                raise RuntimeError(f'{self.NAME}: model {g} went back to train() mode')
         if torch.is_grad_enabled() and any(p.requires_grad for m in self.models for p in m.parameters()):
-            raise RuntimeError('GroupedEval is an inference path: call it under torch.no_grad()')
+            raise RuntimeError(f'{self.NAME} is an inference path: call it under torch.no_grad()')
         if not x.is_cuda or x.dtype != torch.float32:
-            raise RuntimeError('GroupedEval: expected a float32 HIP (cuda) tensor; there is no CPU path')
+            raise RuntimeError(f'{self.NAME}: expected a float32 HIP (cuda) tensor; there is no CPU path')
         if x.dim() == 3:
             N, T, VC = x.shape
             x = x.view(N, T, self.V, -1).permute(0, 3, 1, 2).contiguous().unsqueeze(-1)

@@ -18,8 +18,14 @@ edge_importance update or a train-mode forward):
 
 `stgcn.Model.forward` / `extract_feature` route here by themselves in eval mode without autograd for batches of at most
 F2S_MAX_FRAMES clip-persons x frames (N * M * T; TAMGCN_F2S_MAX_FRAMES overrides it, TAMGCN_F2=0 switches the routing off;
-measured: profiles/f2s_infer_bench.txt).  Limits: temporal kernel 9 only, V <= 32, K <= 3, Cout % 16 == 0; there is no
-grouped (multi-stream) pass.  No CPU path, no fallback inside: `Unsupported` is raised before anything is launched.
+measured: profiles/f2s_infer_bench.txt).  Limits: temporal kernel 9 only, V <= 32, K <= 3, Cout % 16 == 0.  No CPU path, no
+fallback inside: `Unsupported` is raised before anything is launched.
+
+A multi-stream ensemble of G ST-GCN models of one geometry (inference.StreamEnsemble) runs as ONE launch sequence:
+`GroupedEvalST` stacks the folded tensors of the G models on a leading group axis and runs the fused stem, ten
+tamgcn::st_gcn_eval_grouped (the same two kernels with a group offset on their parameter pointers: tamgcn_f2s_gcn_grouped,
+tamgcn_f2s_tcn_grouped; include/tamgcn.h "f2s grouped"), one pool and one grouped fc -- 23 launches whatever G is, bit-equal
+per group to that model's own FusedEvalST (measured: profiles/stgcn_ensemble_bench.txt).
 
 The same engine serves gradient saliency (tam_gcn_amd.saliency; reference tools/train_stgcn_group.py:264-356).  In eval mode a
 block is piecewise linear in its input with these static folded weights, so its DATA gradient is again two launches
@@ -44,9 +50,9 @@ from torch import Tensor
 
 from . import _lib
 from . import functional as Fn
-from .f2 import FusedEval, Unsupported, enabled, _affine, _fold, _opt
+from .f2 import FusedEval, GroupedEval, Unsupported, enabled, _affine, _fold, _opt
 
-__all__ = ['FusedEvalST', 'Unsupported', 'F2S_MAX_FRAMES', 'F2S_BWD_MAX_FRAMES', 'enabled']
+__all__ = ['FusedEvalST', 'GroupedEvalST', 'Unsupported', 'F2S_MAX_FRAMES', 'F2S_BWD_MAX_FRAMES', 'enabled']
 
 # N*M*T up to which stgcn.Model.forward routes here: the largest measured clip-persons x frames at which the family beats the
 # general eval path both eager and under graph replay at every measured joint count (17, 18, 20, 25); it loses at 1200 (25
@@ -222,15 +228,25 @@ class FusedEvalST(FusedEval):
 #   geom:   K, KT, stride, block residual (0 none | 1 identity | 2 conv)
 # x (N, Cin, T, V) -> out (N, Cout, (T - 1) // stride + 1, V).  Two launches.
 # ----------------------------------------------------------------------------------------------------------------------
-def _st_gcn_fwd(name, x, params, geom):
+def _st_gcn_fwd(name, x, params, geom, groups=None):
+    """groups None: the plain entry points on one model's params; else the grouped ones on params stacked on a leading group axis."""
     if not x.is_cuda or x.dtype != torch.float32:
         raise RuntimeError(f'{name}: expected a float32 HIP (cuda) tensor; there is no CPU path')
     if x.dim() != 4 or len(params) != 7 or len(geom) != 4:
         raise RuntimeError(f'{name}: expected x (N, C, T, V), 7 tensors and 4 integers, got {tuple(x.shape)}, {len(params)}, {len(geom)}')
     lib = _lib.load()
     K, kt, stride, rmode = geom
-    Ae, Wg, bg, Wt, bt, Wr, br = (t.contiguous() for t in params)
     N, Cin, T, V = x.shape
+    ga, sfx = (), ''                                         # the grouped entry points take `groups` after the descriptor
+    if groups is not None:
+        if groups < 1 or N % groups:
+            raise RuntimeError(f'{name}: {N} samples are not a multiple of groups = {groups}')
+        if any(t.dim() < 1 or t.shape[0] != groups for t in params):
+            raise RuntimeError(f'{name}: every tensor of params needs a leading axis of groups = {groups}')
+        ga, sfx = (groups,), '_grouped'
+        full = params
+        params = [t[0] for t in params]                      # group 0's: the shapes below are per group
+    Ae, Wg, bg, Wt, bt, Wr, br = (t.contiguous() for t in params)
     Cout = bt.shape[0]
     if not (2 <= V <= 32 and 1 <= K <= 3 and 1 <= Cin <= 256 and 16 <= Cout <= 256 and Cout % 16 == 0 and kt == KT and stride in (1, 2)):
         raise RuntimeError(f'{name}: V={V} K={K} Cin={Cin} Cout={Cout} KT={kt} stride={stride} is outside the f2s kernels '
@@ -239,18 +255,20 @@ def _st_gcn_fwd(name, x, params, geom):
         raise RuntimeError(f'{name}: parameter shapes {[tuple(t.shape) for t in params]} do not fit x {tuple(x.shape)}, geom {list(geom)}')
     if rmode == 2 and (tuple(Wr.shape) != (Cout, Cin) or br.numel() != Cout) or rmode == 1 and (Cin != Cout or stride != 1):
         raise RuntimeError(f'{name}: residual mode {rmode} does not fit Cin={Cin} Cout={Cout} stride={stride}')
+    if groups is not None:                                   # the whole stacked arrays: group g's follows group 0's densely
+        Ae, Wg, bg, Wt, bt, Wr, br = (t.contiguous() for t in full)
     x = x.contiguous()
     dev = x.device
     st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     h = torch.empty(N, Cout, T, V, device=dev)
     g = _lib.F2sGcnDesc(N=N, Cin=Cin, Cout=Cout, T=T, V=V, K=K, x=x.data_ptr(), Ae=Ae.data_ptr(), wg=Wg.data_ptr(), bg=bg.data_ptr(),
                         h=h.data_ptr())
-    _lib.check(lib.tamgcn_f2s_gcn(C.byref(g), st), 'tamgcn_f2s_gcn')
+    _lib.check(getattr(lib, 'tamgcn_f2s_gcn' + sfx)(C.byref(g), *ga, st), 'tamgcn_f2s_gcn' + sfx)
     out = torch.empty(N, Cout, (T - 1) // stride + 1, V, device=dev)
     t = _lib.F2sTcnDesc(N=N, Cin=Cin, Cout=Cout, T=T, V=V, KT=kt, stride=stride, res_mode=rmode, h=h.data_ptr(), wt=Wt.data_ptr(),
                         bt=bt.data_ptr(), x=x.data_ptr() if rmode else None, wr=_opt(Wr) if rmode == 2 else None,
                         br=_opt(br) if rmode == 2 else None, out=out.data_ptr())
-    _lib.check(lib.tamgcn_f2s_tcn(C.byref(t), st), 'tamgcn_f2s_tcn')
+    _lib.check(getattr(lib, 'tamgcn_f2s_tcn' + sfx)(C.byref(t), *ga, st), 'tamgcn_f2s_tcn' + sfx)
     return out, h
 
 
@@ -276,6 +294,24 @@ def _(x, params, geom):
     N, _, T, V = x.shape
     Cout = params[4].shape[0]
     return x.new_empty(N, Cout, (T - 1) // geom[2] + 1, V), x.new_empty(N, Cout, T, V)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The grouped block: `groups` models of one geometry in the same two launches (include/tamgcn.h "f2s grouped").
+#   x      (groups*n, Cin, T, V): rows [g n, (g+1) n) are group g's samples
+#   params the seven tensors above, EVERY one stacked on a new leading group axis (an absent one: no elements)
+#   geom   as above, shared by all groups
+# Group g's slice of the result is bit-equal to st_gcn_eval on group g's slice and parameters.
+# ----------------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op('tamgcn::st_gcn_eval_grouped', mutates_args=())
+def st_gcn_eval_grouped(x: Tensor, params: List[Tensor], geom: List[int], groups: int) -> Tensor:
+    return _st_gcn_fwd('tamgcn::st_gcn_eval_grouped', x, params, geom, groups)[0]
+
+
+@st_gcn_eval_grouped.register_fake
+def _(x, params, geom, groups):
+    N, _, T, V = x.shape
+    return x.new_empty(N, params[4].shape[1], (T - 1) // geom[2] + 1, V)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -326,3 +362,56 @@ def st_gcn_eval_bwd(gout: Tensor, out: Tensor, h: Tensor, params: List[Tensor], 
 def _(gout, out, h, params, geom):
     N, _, T, V = h.shape
     return h.new_empty(N, params[1].shape[1], T, V)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# G models as one launch sequence
+# ----------------------------------------------------------------------------------------------------------------------
+def _model_fields(m):
+    """The geometry all ST-GCN models of a group must share, as (name, value) pairs (f2.GroupedEval reads the first, second and
+    fourth by position); each block's geometry is compared after folding (f2.stack_blocks)."""
+    if not hasattr(m, 'st_gcn_networks') or not hasattr(m, 'edge_importance'):
+        raise Unsupported('GroupedEvalST serves models.stgcn.Model')
+    V = getattr(m, 'num_point', None)
+    cin = m.st_gcn_networks[0].in_channels
+    return [('num_point', V), ('num_class', m.fcn.out_channels), ('in_channels', cin),
+            ('num_person', m.data_bn.num_features // (cin * V) if V else None), ('subsets', int(m.A.shape[0])),
+            ('block plan', [(b.in_channels, b.out_channels, int(b.tcn[2].stride[0]), b._rmode) for b in m.st_gcn_networks])]
+
+
+class GroupedEvalST(GroupedEval):
+    """f2.GroupedEval on G models.stgcn.Model of one geometry: a fused stem (tamgcn_stem_streams_eval), TWO grouped launches per
+    block (tamgcn::st_gcn_eval_grouped), one pool and one grouped fc -- 23 launches whatever G is.
+
+        eng = GroupedEvalST(models)                     # all in eval() mode, on one device
+        scores = eng(x, parent, modes)                  # x (N, C, T, V, M) JOINT clips; modes int32 [G] on the device
+                                                        # -> (G, N, K): model g on stream modes[g] of x
+
+    The models share num_point, num_class, in_channels, num_person, the number of subsets and the block plan; every model has its
+    own edge_importance, so Ae = A * edge_importance differs per group like every other folded tensor.  Each model keeps its own
+    FusedEvalST for the folding and the state key; stacking, the in-place re-fold of one model's slice, keep_alive and
+    check_input are GroupedEval's."""
+    NAME = 'GroupedEvalST'
+    LABEL = 'st_gcn block {}'
+    FAMILY = 'f2s'
+    _fields = staticmethod(_model_fields)
+
+    def _family(self, V):
+        if not 2 <= V <= 32:
+            raise Unsupported(f'{V} joints (the f2s kernels serve 2 <= V <= 32)')
+        self._blk = torch.ops.tamgcn.st_gcn_eval_grouped
+        return FusedEvalST
+
+    @staticmethod
+    def _fc(m):
+        return m.fcn.weight.detach().view(m.fcn.weight.size(0), -1), m.fcn.bias.detach()
+
+    def run(self, x, parent, modes, stacked):
+        """x already checked (check_input), stacked = self._packed(x.device): the launches alone."""
+        from . import ops
+        G = len(self.models)
+        h = ops.stem_streams_eval(x, parent, modes, self._coef)
+        for params, geom in stacked:
+            h = self._blk(h, params, geom, G)
+        pooled = ops.head_pool_fwd(h, self.M)                      # (G*N, C): the single model's per-row arithmetic
+        return ops.head_fc_grouped(pooled, self._fcw, self._fcb, G)

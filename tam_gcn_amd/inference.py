@@ -15,7 +15,8 @@ BatchNorm coefficients are keyed on parameter versions, so re-capture with .rese
 A multi-stream ensemble (the published four-stream accuracies: joint, bone, joint-motion and bone-motion models whose scores
 are summed) as ONE call on the joint clips:
 
-    ens = StreamEnsemble([joint, bone, motion, bone_motion])       # eval() models of one architecture
+    ens = StreamEnsemble([joint, bone, motion, bone_motion])       # eval() models of one architecture: all models.ctrgcn.Model
+                                                                   # or all models.stgcn.Model
     with torch.no_grad():
         fused = ens(x)                                             # (N, K); GraphedForward(ens) captures it
         fused, pred, scores = ens.predict(x)                       # + arg max (N) and the per-stream scores (G, N, K)"""
@@ -138,11 +139,11 @@ class StreamEnsemble(nn.Module):
     x is (N, C, T, V, M) or (N, T, V*C), float32 on the GPU, under torch.no_grad().  forward(x) -> fused (N, K);
     predict(x) -> (fused, pred int64 (N), scores (G, N, K)).
 
-    Small inputs (G*N*M <= f2.F2_MAX_CLIPS at V = 20, G*N*M*T <= f2v.F2V_MAX_FRAMES at V = 25 and <= f2v.F2J_MAX_FRAMES at
-    V = 17, 18; TAMGCN_F2 != 0; no forward
-    hooks on any sub-module) run as ONE grouped launch sequence (f2.GroupedEval: 54 launches whatever G is).  Anything else
-    runs each model's own forward on its derived stream (ops.stream_derive) and fuses the scores: the same result to
-    rounding, at any size.
+    Small inputs (CTR-GCN: G*N*M <= f2.F2_MAX_CLIPS at V = 20, G*N*M*T <= f2v.F2V_MAX_FRAMES at V = 25 and <=
+    f2v.F2J_MAX_FRAMES at V = 17, 18; ST-GCN: G*N*M*T <= f2s.F2S_MAX_FRAMES at any V <= 32; TAMGCN_F2 != 0; no forward
+    hooks on any sub-module) run as ONE grouped launch sequence (f2.GroupedEval: 54 launches whatever G is; f2s.GroupedEvalST:
+    24 with the score fusion).  Anything else runs each model's own forward on its derived stream (ops.stream_derive) and fuses the scores: the
+    same result to rounding, at any size.  The models are all CTR-GCN or all ST-GCN: a mix is refused.
 
     arrangement (None: by measurement, profiles/stream_ensemble_bench.txt) | 'grouped' | 'streams' | 'serial'.  Launched from
     Python the grouped sequence is the fastest (54 launches against 216).  Inside a HIP-graph capture (GraphedForward(ens)) the
@@ -152,12 +153,20 @@ class StreamEnsemble(nn.Module):
     faster: kernels of different models fill each other's tails, which one grouped launch per stage cannot.  So None takes
     'streams' for a call made by GraphedForward (its warm-up calls and its capture alike) with N*M > 1, and 'grouped'
     otherwise.  A capture made by hand (torch.cuda.graph around ens(x)) gets no such switch: pass arrangement= there.  The
-    routes agree bit for bit where the grouped one applies."""
+    routes agree bit for bit where the grouped one applies.
+
+    ST-GCN ensembles were measured on their own (profiles/stgcn_ensemble_bench.txt, four models, HIP-graph replay, medians of 7
+    alternating rounds whose [min .. max] spread is at most 0.009 ms) and the measurement gives the SAME rule.  One clip-person per
+    model (N-UCLA batch 1): grouped 0.625 ms, G streams 0.701 ms, serial 1.821 ms -- the grouped pass wins by 11 %, outside the
+    spread.  Beyond: N-UCLA batch 4 grouped 1.376 ms against 1.180 ms on G streams, NTU batch 1 (two persons) 1.233 ms against
+    1.109 ms -- the streams are 14 % and 10 % faster.  So None takes 'streams' under GraphedForward with N*M > 1 and 'grouped'
+    otherwise, as above.  Launched from Python the grouped sequence takes 0.79 / 1.39 / 1.24 ms against 1.83 / 2.44 / 2.04 ms for
+    the models one after another."""
 
     def __init__(self, models, streams=('joint', 'bone', 'motion', 'bone_motion'), weights=None, softmax=False, parent=None,
                  arrangement=None):
         super().__init__()
-        from . import f2
+        from . import f2, f2s
         models, streams = list(models), list(streams)
         if len(streams) != len(models):
             raise ValueError(f'StreamEnsemble: {len(models)} models but {len(streams)} streams')
@@ -172,8 +181,13 @@ class StreamEnsemble(nn.Module):
         weights = [1.0] * len(models) if weights is None else [float(w) for w in weights]
         if len(weights) != len(models):
             raise ValueError(f'StreamEnsemble: {len(models)} models but {len(weights)} weights')
-        try:
-            self._eng = f2.GroupedEval(models)                 # ValueError: train mode, devices, differing geometry
+        st = [hasattr(m, 'st_gcn_networks') for m in models]   # models.stgcn.Model: the f2s family and its own bound
+        if any(st) and not all(st):
+            raise ValueError('StreamEnsemble: a mix of ST-GCN and CTR-GCN models (model '
+                             f'{st.index(not st[0])} is not of model 0\'s architecture); every model must be of one architecture')
+        self._st = bool(st) and st[0]
+        try:                                                   # ValueError: train mode, devices, differing geometry
+            self._eng = (f2s.GroupedEvalST if self._st else f2.GroupedEval)(models)
         except f2.Unsupported:
             self._eng = None                                   # outside both families: every call takes the per-model route
             if any(m.training for m in models):
@@ -203,7 +217,7 @@ class StreamEnsemble(nn.Module):
 
     def _grouped(self, x5):
         """(the grouped engine, its stacked folded tensors) if this call is one for it, else (None, None)."""
-        from . import f2, f2v
+        from . import f2, f2s, f2v
         eng = self._eng
         none = (None, None)
         if eng is None or not f2.enabled():
@@ -211,7 +225,10 @@ class StreamEnsemble(nn.Module):
         G, (N, _, T, V, M) = len(self.models), x5.shape
         if V != eng.V or M != eng.M:
             return none
-        if (G * N * M > f2.F2_MAX_CLIPS) if V == 20 else (G * N * M * T > (f2v.F2V_MAX_FRAMES if V == 25 else f2v.F2J_MAX_FRAMES)):
+        if self._st:
+            if G * N * M * T > f2s.F2S_MAX_FRAMES:
+                return none
+        elif (G * N * M > f2.F2_MAX_CLIPS) if V == 20 else (G * N * M * T > (f2v.F2V_MAX_FRAMES if V == 25 else f2v.F2J_MAX_FRAMES)):
             return none
         for mod in self.modules():
             if mod._forward_hooks or mod._forward_pre_hooks:

@@ -119,8 +119,9 @@ def _family_batch(model, frames_per_window, V, M):
     """Windows per call that keep `model` on its small-batch eval family (Model.forward's routing bounds)."""
     from . import f2, f2g, f2s, f2v
     G = len(model.models) if hasattr(model, 'models') else 1        # a StreamEnsemble's grouped pass counts G N M
-    if type(model).__module__.endswith('stgcn'):
-        return max(1, f2s.F2S_MAX_FRAMES // (frames_per_window * M))
+    one = model.models[0] if hasattr(model, 'models') else model     # a StreamEnsemble's models are of one architecture
+    if type(one).__module__.endswith('stgcn'):
+        return max(1, f2s.F2S_MAX_FRAMES // (G * M * frames_per_window))
     if V == 20:
         return max(1, f2.F2_MAX_CLIPS // (G * M))
     bound = f2v.F2V_MAX_FRAMES if V == 25 else f2v.F2J_MAX_FRAMES if V in f2v.JOINTS else f2g.F2G_MAX_FRAMES

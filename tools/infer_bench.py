@@ -20,7 +20,7 @@ one joint batch, every arrangement under HIP-graph replay, alternating within th
     (b) streams   the same with the G models on G streams inside the graph (functional.model_stream)
     (c) grouped   inference.StreamEnsemble(arrangement='grouped'): one grouped launch sequence
 then GraphedForward(StreamEnsemble(...)) with its default arrangement, and (a) and (c) launched from Python (eager): both
-carry the host cost of G parameter-state keys per call.
+carry the host cost of G parameter-state keys per call.  --model stgcn --ensemble G: the same for ST-GCN models (f2s.GroupedEvalST).
 --model stgcn --saliency [--ab R]: gradient saliency (tam_gcn_amd/saliency.py) of the true class, (N, V) per batch, alternating in
 this process, R timings each (default 5):
     A  general   eval-mode Model.forward in grad mode and torch.autograd.grad of the gathered score with respect to x (the only
@@ -70,8 +70,6 @@ while args and args[0].startswith('--'):
         sys.exit(__doc__)
     args = args[2:]
 if model == 'stgcn':
-    if ens_g:
-        sys.exit('--ensemble: there is no grouped pass for ST-GCN')
     from tam_gcn_amd.models.stgcn import Model
 if graph == 'ntu':
     V, P = 25, 2
