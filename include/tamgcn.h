@@ -1085,6 +1085,50 @@ int tamgcn_window_vote(const float* logits, const long long* plan, int B, int K,
 int tamgcn_score_ema(const float* probs, const long long* plan_row, int K, double beta, double* ema, long long* seen, float* out,
                      long long* label, float* conf, void* stream);
 
+/* ------------------------------------------------------------------------
+ * A bank of S frame rings for S live feeds in one graph (csrc/streaming.hip, tam_gcn_amd/streaming.py RingBank / LiveBank).
+ * Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed.
+ *
+ * The bank is S rings in one allocation, feed s at s (P cap R) elements: fp64 (S, cap, V, 3) or fp32 (S, C, cap, V, M); feed
+ * s alone is the ring described above.  state int64 (S, 2) = (count, pushes) per feed.  1 <= S <= 1024.  counts and restart
+ * are int32 [S] on the device and may be NULL (every feed takes all n frames; no feed restarts).  take_s =
+ * min(max(counts[s], 0), n); fresh_s = restart[s] != 0.  The arithmetic is the single-ring kernels' own (one body each).
+ * No entry point synchronises, none uses atomics: two runs give the same bits.
+ *
+ *   _bank_push          frames (S, P, n, R): feed s stores the first take_s frames of its slice at slots (c_s + i) % cap, c_s =
+ *                       fresh_s ? 0 : count_s; a unit of a frame i >= take_s is neither read nor stored (it may hold NaN).
+ *                       A second launch behind it: fresh_s -> (count, pushes) = (0, 0) first; then count += take_s and
+ *                       pushes += 1 where take_s > 0.  take_s = 0 without restart: nothing of feed s moves.  16-byte
+ *                       accesses where R elem and both feed strides are multiples of 16 and both arrays are aligned.
+ *   _bank_plan          plan (S B, 2): row s B + j = _ring_plan's row j on feed s's count; (0, 0) rows for a feed with
+ *                       counts[s] <= 0.  Run it behind _bank_push: it reads the advanced state.
+ *   _bank_window_nucla  out (S B, 3, time_steps, V, 1): _window_nucla's window, plan row w on the ring of feed w / B.
+ *   _bank_window_clip   out (S B, C, W, V, M): _window_clip's window, plan row w on the ring of feed w / B.
+ *   (softmax)           tamgcn_window_vote without frame outputs serves the S B rows.
+ *   _bank_ema           one workgroup per feed: _score_ema's update for the feed's B windows (probs and plan rows s B + j),
+ *                       j ascending, on ema (S, K) fp64 and seen int64 [S].  fresh_s: the average reads as zeros and seen as 0
+ *                       (both are stored, a valid window or not).  out (S, K), label [S], conf [S] as _score_ema's after
+ *                       the last window; advanced int32 [S] = 1 where seen moved.
+ *   _bank_decide        one workgroup; the debounce of every feed, then the events in ascending feed order through a scan.
+ *                       deb int64 (S, 3) = (stable, cand, run), (-1, -1, 0) at the start and where fresh_s.  Where advanced[s]:
+ *                       conf[s] >= threshold and label[s] == cand: run += 1; else conf[s] >= threshold: cand = label[s],
+ *                       run = 1; else cand = -1, run = 0; then, if run >= hold and cand != stable: stable = cand and one event
+ *                       (s, count_s - 1, label[s]) with conf[s].  log_rows int64 (log_capacity, 3), log_conf fp32
+ *                       [log_capacity], log_count int64 [2] = (written, dropped): an event goes to row `written`; a full log
+ *                       drops it and counts it, it never overwrites.  hold >= 1, log_capacity >= 1. */
+int tamgcn_bank_push(const void* frames, int S, int n, int P, int R, int elem, void* ring, int cap, long long* state, const int* counts,
+                     const int* restart, void* stream);
+int tamgcn_bank_plan(const long long* state, const int* counts, int S, int cap, int B, int L, int hop, long long* plan, void* stream);
+int tamgcn_bank_window_nucla(const double* ring, int S, int cap, const long long* plan, int B, const int* parent, int V, int time_steps,
+                             int center_joint, int mode, float* out, void* stream);
+int tamgcn_bank_window_clip(const float* ring, int S, int cap, const long long* plan, int B, int C, int V, int M, int W, float* out,
+                            void* stream);
+int tamgcn_bank_ema(const float* probs, const long long* plan, const int* restart, int S, int B, int K, double beta, double* ema,
+                    long long* seen, float* out, long long* label, float* conf, int* advanced, void* stream);
+int tamgcn_bank_decide(const long long* label, const float* conf, const int* advanced, const int* restart, const long long* state, int S,
+                       float threshold, int hold, long long* deb, long long* log_rows, float* log_conf, long long* log_count,
+                       int log_capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -248,6 +248,12 @@ SIGNATURES = {
     'tamgcn_window_clip': (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
     'tamgcn_window_vote': (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
     'tamgcn_score_ema': (_i, [_p, _p, _i, _d, _p, _p, _p, _p, _p, _p]),
+    'tamgcn_bank_push': (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p]),
+    'tamgcn_bank_plan': (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    'tamgcn_bank_window_nucla': (_i, [_p, _i, _i, _p, _i, _p, _i, _i, _i, _i, _p, _p]),
+    'tamgcn_bank_window_clip': (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
+    'tamgcn_bank_ema': (_i, [_p, _p, _p, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p, _p]),
+    'tamgcn_bank_decide': (_i, [_p, _p, _p, _p, _p, _i, _f, _i, _p, _p, _p, _p, _i, _p]),
     'tamgcn_f2_e': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2_gcn': (_i, [C.POINTER(F2GcnDesc), _p]),
     'tamgcn_f2_gemm': (_i, [C.POINTER(F2GemmDesc), _p]),

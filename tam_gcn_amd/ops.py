@@ -681,9 +681,22 @@ def ctrgc_fwd(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, stats, keep_x3=F
     return y, part, x3
 
 
+def _dy_with_slack(dy):
+    """The streaming kernels fetch dy in 16-byte pieces; where V % 4 != 0 the last piece of the last row reaches up to 12 bytes past
+    the tensor (csrc/ctrgc_stream_body.h).  A gradient the ops allocated has that slack; a caller's cotangent that ends with its
+    storage (the stand-alone CTRGC's, autograd's) is copied once."""
+    if dy.x1.shape[-1] % 4 == 0:
+        return dy
+    x1, x2 = with_slack(dy.x1), with_slack(dy.x2)
+    if x1 is dy.x1 and x2 is dy.x2:
+        return dy
+    return type(dy)(x1, x2, dy.coef, dy.coff, dy.act)
+
+
 def ctrgc_bwd_dx3(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, E=None, per_subset=False):
     """dx3 (N,S*Cout,T,V) = E^T . dy, and db3 [S*Cout]."""
     N, _, T, V = x.x1.shape
+    dy = _dy_with_slack(dy)
     d = _ctrgc_desc(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, E)
     dyc = dy.c()
     dx3 = empty(N, S * Cout, T, V, like=x.x1)
@@ -709,6 +722,7 @@ def ctrgc_bwd_de_acc(dy, x3, Cout, S):
     """dE (N, S, Cout, V, V) = sum_t dy[n,c,t,u] x3[n,s*Cout+c,t,v]: the streaming accumulation of the dE chain.
     dy: an operand S(...) whose channels coff..coff+Cout are the gradient; x3 (N, S*Cout, T, V)."""
     N, _, T, V = x3.shape
+    dy, x3 = _dy_with_slack(dy), with_slack(x3)
     d = CtrgcDesc()
     d.N, d.Cout, d.S, d.T, d.V = N, Cout, S, T, V
     dE = empty(N, S, Cout, V, V, like=x3)
@@ -777,6 +791,7 @@ def ctrgc_bwd_de(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, x3=None, 
 
 def ctrgc_bwd(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, x3=None, E=None):
     """Returns dx3 (N,S*Cout,T,V), db3 [S*Cout], dA [S,V,V], dw4 [S,Cout,R], db4 [S,Cout], dalpha [1], dpq [S*2*R,N,V]."""
+    dy = _dy_with_slack(dy)                               # once for both chains
     dx3, db3 = ctrgc_bwd_dx3(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, E=E)
     dA, dw4, db4, dal, dpq = ctrgc_bwd_de(x, pq, w3, b3, w4, b4, A, alpha, Cin, Cout, S, R, dy, x3)
     return dx3, db3, dA, dw4, db4, dal, dpq
@@ -1357,6 +1372,157 @@ def score_ema(probs, plan_row, beta, ema, seen):
     _lib.check(_lib_().tamgcn_score_ema(_ptr(probs), _ptr(plan_row), K, float(beta), _ptr(ema), _ptr(seen), _ptr(out), _ptr(label), _ptr(conf),
                                         _stream()), 'tamgcn_score_ema')
     return out, label, conf
+
+
+# a bank of S rings for S live feeds (include/tamgcn.h: feed s is a ring of its own at s * (P cap R); counts / restart int32 [S] | None)
+BANK_MAX_FEEDS = 1024
+
+
+def _bank_geometry(bank, what):
+    """(S, P, cap, R, elem) of a bank tensor: fp64 (S, cap, V, 3) or fp32 (S, C, cap, V, M)."""
+    if isinstance(bank, torch.Tensor) and bank.dim() >= 2 and bank.shape[0] >= 1:
+        try:
+            return (bank.shape[0],) + _ring_geometry(bank[0], what)
+        except RuntimeError:
+            pass
+    raise RuntimeError(f'tam_gcn_amd: {what} takes a non-empty fp64 (S, cap, V, 3) or fp32 (S, C, cap, V, M) bank, got '
+                       f'{getattr(bank, "dtype", type(bank))} {tuple(getattr(bank, "shape", ()))}')
+
+
+def _want_feeds(S, what, counts=None, restart=None):
+    if not 1 <= S <= BANK_MAX_FEEDS:
+        raise RuntimeError(f'tam_gcn_amd: {what}: S = {S} feeds outside 1..{BANK_MAX_FEEDS}')
+    if counts is not None:
+        _want(counts, 'counts', torch.int32, (S,))
+    if restart is not None:
+        _want(restart, 'restart', torch.int32, (S,))
+
+
+def bank_push(frames, bank, state, counts=None, restart=None):
+    """frames fp64 (S, n, V, 3) into bank fp64 (S, cap, V, 3), or fp32 (S, C, n, V, M) into fp32 (S, C, cap, V, M): feed s takes the
+    first min(max(counts[s], 0), n) frames of its slice (all n without counts) at slots (count_s + i) % cap; a feed with
+    restart[s] != 0 is forgotten first (count 0).  state int64 (S, 2) = (count, pushes) per feed, read and advanced on the
+    device; a feed that takes nothing and is not restarted is not touched.  1 <= n <= cap.  No host sync, capturable."""
+    S, P, cap, R, elem = _bank_geometry(bank, 'bank_push')
+    _want(bank, 'bank', bank.dtype)
+    _want(state, 'state', torch.int64, (S, 2))
+    _want_feeds(S, 'bank_push', counts, restart)
+    t = 1 if elem == 8 else 2                       # the time axis
+    if not isinstance(frames, torch.Tensor) or frames.dim() != bank.dim() or frames.shape[:t] + frames.shape[t + 1:] != bank.shape[:t] + bank.shape[t + 1:]:
+        raise RuntimeError(f'tam_gcn_amd: bank_push: frames {tuple(getattr(frames, "shape", ()))} do not fit the bank {tuple(bank.shape)}')
+    _want(frames, 'frames', bank.dtype)
+    _lib.check(_lib_().tamgcn_bank_push(_ptr(frames), S, frames.shape[t], P, R, elem, _ptr(bank), cap, _ptr(state), _ptr(counts), _ptr(restart),
+                                        _stream()), 'tamgcn_bank_push')
+
+
+def bank_plan(state, cap, B, L, hop, counts=None, rows=None):
+    """-> plan int64 (S B, 2): row s B + j is ring_plan's row j on feed s (state int64 (S, 2)); (0, 0) rows for a feed with
+    counts[s] <= 0.  rows > S B: that many rows, the tail (0, 0) (a padded last chunk).  No host sync, capturable."""
+    _want(state, 'state', torch.int64)
+    if state.dim() != 2 or state.shape[1] != 2:
+        raise RuntimeError(f'tam_gcn_amd: bank_plan: state is {tuple(state.shape)}, expected (S, 2)')
+    S = state.shape[0]
+    _want_feeds(S, 'bank_plan', counts)
+    rows = S * B if rows is None else rows
+    if rows < S * B:
+        raise RuntimeError(f'tam_gcn_amd: bank_plan: rows = {rows} below S B = {S * B}')
+    plan = torch.empty(rows, 2, device=state.device, dtype=torch.int64)
+    if rows > S * B:
+        plan[S * B:].zero_()
+    _lib.check(_lib_().tamgcn_bank_plan(_ptr(state), _ptr(counts), S, cap, B, L, hop, _ptr(plan), _stream()), 'tamgcn_bank_plan')
+    return plan
+
+
+def _bank_windows(bank, plan, B, what):
+    """rows of the plan and of the output: the first S B are built, rows past them (a padded chunk) are zeros."""
+    rows = _want_plan(plan)
+    S = bank.shape[0]
+    _want_feeds(S, what)
+    if isinstance(B, bool) or not isinstance(B, int) or B < 1 or rows < S * B:
+        raise RuntimeError(f'tam_gcn_amd: {what}: a plan of {rows} rows for S = {S} feeds of B = {B!r} windows')
+    return S, rows
+
+
+def bank_window_nucla(bank, plan, B, parent, time_steps, center_joint, mode):
+    """bank fp64 (S, cap, V, 3), plan int64 (rows >= S B, 2), parent int32 [V] -> (rows, 3, time_steps, V, 1) fp32: window w < S B is
+    window_nucla's window of plan row w on the ring of feed w // B; rows past S B are zeros."""
+    _want(bank, 'bank', torch.float64)
+    if bank.dim() != 4 or bank.shape[3] != 3 or bank.numel() == 0:
+        raise RuntimeError(f'tam_gcn_amd: bank_window_nucla takes a non-empty (S, cap, V, 3) bank, got {tuple(bank.shape)}')
+    S, rows = _bank_windows(bank, plan, B, 'bank_window_nucla')
+    cap, V = bank.shape[1], bank.shape[2]
+    _want(parent, 'parent', torch.int32, (V,))
+    m = STREAM_MODES[mode] if isinstance(mode, str) else int(mode)
+    out = torch.empty(rows, 3, time_steps, V, 1, device=bank.device, dtype=torch.float32)
+    if rows > S * B:
+        out[S * B:].zero_()
+    _lib.check(_lib_().tamgcn_bank_window_nucla(_ptr(bank), S, cap, _ptr(plan), B, _ptr(parent), V, time_steps, center_joint, m, _ptr(out),
+                                                _stream()), 'tamgcn_bank_window_nucla')
+    return out
+
+
+def bank_window_clip(bank, plan, B, W):
+    """bank fp32 (S, C, cap, V, M), plan int64 (rows >= S B, 2) -> (rows, C, W, V, M) fp32: window w < S B is window_clip's window of
+    plan row w on the ring of feed w // B; rows past S B are zeros."""
+    _want(bank, 'bank', torch.float32)
+    if bank.dim() != 5 or bank.numel() == 0:
+        raise RuntimeError(f'tam_gcn_amd: bank_window_clip takes a non-empty (S, C, cap, V, M) bank, got {tuple(bank.shape)}')
+    S, rows = _bank_windows(bank, plan, B, 'bank_window_clip')
+    _, C_, cap, V, M = bank.shape
+    out = torch.empty(rows, C_, W, V, M, device=bank.device, dtype=torch.float32)
+    if rows > S * B:
+        out[S * B:].zero_()
+    _lib.check(_lib_().tamgcn_bank_window_clip(_ptr(bank), S, cap, _ptr(plan), B, C_, V, M, W, _ptr(out), _stream()), 'tamgcn_bank_window_clip')
+    return out
+
+
+def bank_ema(probs, plan, beta, ema, seen, restart=None):
+    """probs fp32 (S B, K), plan int64 (S B, 2), ema fp64 (S, K) and seen int64 [S] updated in place: per feed, score_ema's update
+    for its B windows, oldest first; restart[s] != 0: the feed's average reads as zeros and its seen as 0 first.
+    -> out fp32 (S, K), label int64 [S] (-1 before a feed's first valid window), conf fp32 [S], advanced int32 [S] (seen moved)."""
+    _want(ema, 'ema', torch.float64)
+    if ema.dim() != 2 or ema.numel() == 0:
+        raise RuntimeError(f'tam_gcn_amd: bank_ema takes a non-empty (S, K) average, got {tuple(ema.shape)}')
+    S, K = ema.shape
+    _want_feeds(S, 'bank_ema', None, restart)
+    _want(seen, 'seen', torch.int64, (S,))
+    _want(probs, 'probs', torch.float32)
+    if probs.dim() != 2 or probs.shape[1] != K or probs.shape[0] < S or probs.shape[0] % S:
+        raise RuntimeError(f'tam_gcn_amd: bank_ema: probs {tuple(probs.shape)} are not (S B, K) for S = {S}, K = {K}')
+    B = probs.shape[0] // S
+    _want(plan, 'plan', torch.int64, (S * B, 2))
+    dev = probs.device
+    out = torch.empty(S, K, device=dev, dtype=torch.float32)
+    label = torch.empty(S, device=dev, dtype=torch.int64)
+    conf = torch.empty(S, device=dev, dtype=torch.float32)
+    advanced = torch.empty(S, device=dev, dtype=torch.int32)
+    _lib.check(_lib_().tamgcn_bank_ema(_ptr(probs), _ptr(plan), _ptr(restart), S, B, K, float(beta), _ptr(ema), _ptr(seen), _ptr(out), _ptr(label),
+                                       _ptr(conf), _ptr(advanced), _stream()), 'tamgcn_bank_ema')
+    return out, label, conf, advanced
+
+
+def bank_decide(label, conf, advanced, state, threshold, hold, deb, log_rows, log_conf, log_count, restart=None):
+    """The debounced decision of every feed and its log (include/tamgcn.h has the rule): label int64 [S], conf fp32 [S], advanced
+    int32 [S] (bank_ema's), state int64 (S, 2) (the bank's), deb int64 (S, 3) = (stable, cand, run) updated in place, log_rows
+    int64 (capacity, 3) = (feed, frame, label), log_conf fp32 [capacity], log_count int64 [2] = (written, dropped).  Events are
+    appended in ascending feed order; a full log drops and counts.  No atomics, no host sync, capturable."""
+    _want(label, 'label', torch.int64)
+    if label.dim() != 1 or label.numel() == 0:
+        raise RuntimeError(f'tam_gcn_amd: bank_decide takes labels [S], got {tuple(label.shape)}')
+    S = label.numel()
+    _want_feeds(S, 'bank_decide', None, restart)
+    _want(conf, 'conf', torch.float32, (S,))
+    _want(advanced, 'advanced', torch.int32, (S,))
+    _want(state, 'state', torch.int64, (S, 2))
+    _want(deb, 'deb', torch.int64, (S, 3))
+    _want(log_rows, 'log_rows', torch.int64)
+    if log_rows.dim() != 2 or log_rows.shape[1] != 3 or log_rows.shape[0] < 1 or log_rows.shape[0] >= 2 ** 31:
+        raise RuntimeError(f'tam_gcn_amd: bank_decide: log_rows is {tuple(log_rows.shape)}, expected (capacity, 3)')
+    cap = log_rows.shape[0]
+    _want(log_conf, 'log_conf', torch.float32, (cap,))
+    _want(log_count, 'log_count', torch.int64, (2,))
+    _lib.check(_lib_().tamgcn_bank_decide(_ptr(label), _ptr(conf), _ptr(advanced), _ptr(restart), _ptr(state), S, float(threshold), int(hold),
+                                          _ptr(deb), _ptr(log_rows), _ptr(log_conf), _ptr(log_count), cap, _stream()), 'tamgcn_bank_decide')
 
 
 # ---------------------------------------------------------------------------

@@ -23,6 +23,15 @@ average as one HIP graph that never synchronises:
     res = sw.run(recording)                                # (len, 20, 3)
     res.frame_label                                        # (len,) int64 on the device
 
+``RingBank`` and ``LiveBank`` are the frame-by-frame use for many feeds at once -- several cameras, or several tracked persons of
+one camera -- S rings in one allocation and one graph replay per tick for all of them:
+
+    bank = RingBank(feeds=32, capacity=128, prep='nucla', V=20)
+    live = LiveBank(model.eval(), bank, window=40, beta=0.8, threshold=0.6, hold=3)
+    for frames, counts, restart in ticks:                  # (32, 1, 20, 3); int32 [32] on the device or None
+        out = live.step(frames, counts, restart)           # out.label, out.conf, out.smoothed, out.logits, out.stable: no sync
+    live.events()                                          # the debounced label changes logged on the device: the only sync
+
 The plan rule of ``SlidingWindow``: windows start at j * hop while j * hop + window <= len; one more window at len - window
 when that leaves frames uncovered; a sequence shorter than the window is one window (0, len).  A frame's scores are the mean
 of the softmax rows of the windows that cover it.  ``LiveClassifier``: per step `hop_windows` windows, window j ending
@@ -36,7 +45,7 @@ from . import ops
 from .evaluation import _state_key
 from .inference import ENGINE_SLOTS, GraphedForward, default_parent
 
-__all__ = ['FrameRing', 'SlidingWindow', 'LiveClassifier', 'plan_offline']
+__all__ = ['FrameRing', 'RingBank', 'SlidingWindow', 'LiveClassifier', 'LiveBank', 'plan_offline']
 
 PREPS = ('nucla', 'clip')
 NUCLA_CENTER_JOINT = 1         # feeder_nucla_gcn centres on joint 1 of the first frame
@@ -101,6 +110,95 @@ class FrameRing:
     @property
     def count(self):
         return int(self.state[0])
+
+
+def _feed_flags(who, name, t, S):
+    """counts / restart of a bank call: None, or S integers in a tensor."""
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.dim() != 1 or t.numel() != S or t.is_floating_point() or t.dtype == torch.bool:
+        raise ValueError(f'{who}: {name} must be None or an integer tensor [{S}], got {getattr(t, "dtype", type(t))} '
+                         f'{tuple(getattr(t, "shape", ()))}')
+    return t
+
+
+class RingBank:
+    """S = feeds independent rings in one allocation, one per camera or tracked person: feed s is the ring FrameRing describes
+    (frame f of feed s in slot f % capacity), and feed(s) returns views (buf[s], state[s]) the single-ring ops accept.
+
+    prep='nucla': buf fp64 (S, capacity, V, 3), push((S, n, V, 3)) in any float dtype.
+    prep='clip':  buf fp32 (S, C, capacity, V, M), push((S, C, n, V, M)) fp32.
+    state int64 (S, 2) = (count, pushes) per feed lives on the device.  1 <= S <= 1024 (ops.BANK_MAX_FEEDS), 1 <= n <= capacity.
+
+    push(frames, counts=None, restart=None), no host synchronisation, capturable: counts int32 [S] on the device (None: every
+    feed takes all n frames): feed s takes the first min(max(counts[s], 0), n) frames of its slice; with 0 nothing of feed s
+    moves, and what is not taken is never read (it may hold NaN).  restart int32 [S]: a non-zero entry forgets feed s before the
+    push: its count goes to 0 and its frames are numbered from 0 again (the buffer is not cleared: no valid window reaches
+    before frame 0).  reset(feeds=None) is the host-side call for all feeds or a list of them; it clears the buffers too."""
+
+    def __init__(self, feeds, capacity, prep='nucla', V=None, C=3, M=1, device='cuda'):
+        who = 'RingBank'
+        self.feeds = _int('feeds', feeds, 1, who)
+        if feeds > ops.BANK_MAX_FEEDS:
+            raise ValueError(f'{who}: feeds = {feeds} above {ops.BANK_MAX_FEEDS}')
+        self.capacity = _int('capacity', capacity, 1, who)
+        if prep not in PREPS:
+            raise ValueError(f'{who}: prep {prep!r} (one of {PREPS})')
+        self.V, self.C, self.M = _int('V', V, 1, who), _int('C', C, 1, who), _int('M', M, 1, who)
+        if prep == 'nucla' and (C != 3 or M != 1):
+            raise ValueError(f"{who}: prep='nucla' holds one person's (V, 3) joints per feed; C = {C}, M = {M}")
+        self.prep = prep
+        dev = _device(device, who)
+        if prep == 'nucla':
+            self.buf = torch.zeros(feeds, capacity, V, 3, dtype=torch.float64, device=dev)
+        else:
+            self.buf = torch.zeros(feeds, C, capacity, V, M, dtype=torch.float32, device=dev)
+        self.state = torch.zeros(feeds, 2, dtype=torch.int64, device=dev)
+
+    def frames_shape(self, n):
+        return (self.feeds, n, self.V, 3) if self.prep == 'nucla' else (self.feeds, self.C, n, self.V, self.M)
+
+    def push(self, frames, counts=None, restart=None):
+        who = 'RingBank.push'
+        if not torch.is_tensor(frames) or not frames.is_cuda:
+            raise RuntimeError(f'{who}: expected a HIP (cuda) tensor; there is no CPU path')
+        t = 1 if self.prep == 'nucla' else 2
+        if frames.dim() != self.buf.dim() or tuple(frames.shape) != self.frames_shape(frames.shape[t]) or not frames.is_floating_point():
+            raise ValueError(f'{who}: frames must be {self.frames_shape("n")} floats, got {tuple(frames.shape)} {frames.dtype}')
+        if not 1 <= frames.shape[t] <= self.capacity:
+            raise ValueError(f'{who}: {frames.shape[t]} frames outside 1..capacity = {self.capacity}')
+        if self.prep == 'clip' and frames.dtype != torch.float32:
+            raise ValueError(f"{who}: prep='clip' takes fp32 frames, got {frames.dtype}")
+        dev = self.buf.device
+        counts, restart = (None if f is None else f.to(device=dev, dtype=torch.int32).contiguous()
+                           for f in (_feed_flags(who, 'counts', counts, self.feeds), _feed_flags(who, 'restart', restart, self.feeds)))
+        ops.bank_push(frames.to(self.buf.dtype).contiguous(), self.buf, self.state, counts, restart)
+
+    def reset(self, feeds=None):
+        if feeds is None:
+            self.buf.zero_()
+            self.state.zero_()
+            return
+        for s in self._feeds('RingBank.reset', feeds):
+            self.buf[s].zero_()
+            self.state[s].zero_()
+
+    def _feeds(self, who, feeds):
+        feeds = [feeds] if isinstance(feeds, int) else list(feeds)
+        for s in feeds:
+            if isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < self.feeds:
+                raise ValueError(f'{who}: feed {s!r} outside 0..{self.feeds - 1}')
+        return feeds
+
+    def feed(self, s):
+        """(buf[s], state[s]): feed s as the ring and state tensors ops.ring_push, ring_plan, window_nucla and window_clip take."""
+        s, = self._feeds('RingBank.feed', s)
+        return self.buf[s], self.state[s]
+
+    @property
+    def counts(self):
+        """The frames every feed has taken, as a list (a synchronisation)."""
+        return self.state[:, 0].tolist()
 
 
 def plan_offline(length, window, hop):
@@ -320,7 +418,46 @@ class SlidingWindow:
         return SlidingResult(logits, probs, scores, label, plan)
 
 
-class LiveClassifier:
+class _LiveChain:
+    """What LiveClassifier and LiveBank share: the capture of self._chain() as one HIP graph after self._warm() ran on a side
+    stream.  The subclass has model, _dev, _who and captures."""
+
+    def _capture(self):
+        dev = self._dev
+        told = hasattr(self.model, '_tamgcn_graphed')                 # GraphedForward's note to a StreamEnsemble
+        if told:
+            before, self.model._tamgcn_graphed = self.model._tamgcn_graphed, True
+        try:
+            with torch.no_grad():
+                side = torch.cuda.Stream(device=dev)
+                side.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(side):
+                    for _ in range(2):
+                        self._warm()
+                torch.cuda.current_stream(dev).wait_stream(side)
+                g = torch.cuda.CUDAGraph()
+                try:
+                    with torch.cuda.graph(g):
+                        out = self._chain()
+                except Exception as e:                                # noqa: BLE001  -- no silent eager fall-back
+                    raise RuntimeError(f'{self._who}: HIP graph capture failed ({type(e).__name__}: {e})') from e
+        finally:
+            if told:
+                self.model._tamgcn_graphed = before
+        # what the graph reads through pointers and the eval caches own (GraphedForward._capture_told has the reasons)
+        keep = [dict(m.__dict__['_tamgcn_eval_cache']) for m in self.model.modules() if '_tamgcn_eval_cache' in m.__dict__]
+        for slot in ENGINE_SLOTS:
+            eng = self.model.__dict__.get(slot)
+            if eng:
+                keep.append(eng._blocks)
+        hook = getattr(self.model, '_tamgcn_keep_alive', None)
+        if hook is not None:
+            keep.append(hook())
+        self._graph, self._out, self._keep = g, out, keep
+        self.captures += 1
+
+
+class LiveClassifier(_LiveChain):
     """model in eval() mode; ring: the FrameRing the frames go to (its prep decides the window form); window frames per window;
     per step hop_windows windows `hop` frames apart (default hop = window), the newest last; beta in [0, 1): the moving average
     ema = beta ema + (1 - beta) probs over the valid windows in the order they are seen (0: the newest window's softmax);
@@ -357,7 +494,8 @@ class LiveClassifier:
             raise ValueError(f'{who}: the model has {getattr(first, "num_point", None)} joints, the ring {ring.V}')
         self._w = _Windows(who, model, ring.prep, time_steps, window_size, stream, parent, ring.V, ring.C, ring.M)
         self.model, self.ring, self.beta, self.eager = model, ring, float(beta), bool(eager)
-        dev = ring.buf.device
+        dev = self._dev = ring.buf.device
+        self._who = who
         self._w.bind(dev)
         self._frames = torch.zeros(ring.frames_shape(self.n), dtype=ring.buf.dtype, device=dev)
         with torch.no_grad():
@@ -394,40 +532,6 @@ class LiveClassifier:
             smoothed, label, conf = ops.score_ema(probs[j], plan[j], self.beta, self.ema, self.seen)
         return label, conf, smoothed, logits
 
-    def _capture(self):
-        dev = self.ring.buf.device
-        told = hasattr(self.model, '_tamgcn_graphed')                 # GraphedForward's note to a StreamEnsemble
-        if told:
-            before, self.model._tamgcn_graphed = self.model._tamgcn_graphed, True
-        try:
-            with torch.no_grad():
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        self._warm()
-                torch.cuda.current_stream(dev).wait_stream(side)
-                g = torch.cuda.CUDAGraph()
-                try:
-                    with torch.cuda.graph(g):
-                        out = self._chain()
-                except Exception as e:                                # noqa: BLE001  -- no silent eager fall-back
-                    raise RuntimeError(f'LiveClassifier: HIP graph capture failed ({type(e).__name__}: {e})') from e
-        finally:
-            if told:
-                self.model._tamgcn_graphed = before
-        # what the graph reads through pointers and the eval caches own (GraphedForward._capture_told has the reasons)
-        keep = [dict(m.__dict__['_tamgcn_eval_cache']) for m in self.model.modules() if '_tamgcn_eval_cache' in m.__dict__]
-        for slot in ENGINE_SLOTS:
-            eng = self.model.__dict__.get(slot)
-            if eng:
-                keep.append(eng._blocks)
-        hook = getattr(self.model, '_tamgcn_keep_alive', None)
-        if hook is not None:
-            keep.append(hook())
-        self._graph, self._out, self._keep = g, out, keep
-        self.captures += 1
-
     def step(self, frames):
         if self.model.training:
             raise RuntimeError('LiveClassifier: the model is in train() mode; call model.eval() before a step')
@@ -452,3 +556,197 @@ class LiveClassifier:
         self.ring.reset()
         self.ema.zero_()
         self.seen.zero_()
+
+
+BankStep = collections.namedtuple('BankStep', 'label conf smoothed logits stable')
+BankEvents = collections.namedtuple('BankEvents', 'rows conf dropped')
+
+
+class LiveBank(_LiveChain):
+    """LiveClassifier for S feeds at once: one graph replay pushes a tick's frames to every feed of a RingBank and classifies
+    them all.  model, window, hop_windows, hop, beta, time_steps / window_size, stream, parent, frames_per_step, eager as
+    LiveClassifier's, and its rules: eval mode only, the state key compared per step with a re-capture when it moved (`captures`
+    counts), a StreamEnsemble on one stream, eager=True the same bits, outputs the graph's own tensors.
+
+    step(frames, counts=None, restart=None) -> BankStep(label int64 [S], conf fp32 [S], smoothed fp32 (S, K), logits fp32
+    (S, hop_windows, K), stable int64 [S] | None): frames in the bank's push form with n = frames_per_step; counts, restart:
+    integer tensors [S] or None, copied like the frames into the chain's own device tensors (changing them never captures again).
+    Per feed the semantics are a LiveClassifier's on a FrameRing that was stepped only on the ticks where counts[s] > 0, with
+    that many frames, and reset() where restart[s] was set.  A feed with counts[s] == 0: no window of the tick is valid, its
+    average and `seen` do not move, label, conf, smoothed and stable repeat its state, its logits rows are unspecified.  A feed
+    with restart[s]: average, seen and debounce state are cleared on the device before the tick's push; label is -1 until its
+    first valid window.  No synchronisation.
+
+    The S hop_windows windows go through the model in chunks of chunk_windows (default: the fewest chunks that keep the model on
+    its small-batch eval family, as in SlidingWindow, made equal in size; the last chunk padded with invalid windows), all inside
+    the one graph.  Past the family's bound one pass of all windows (chunk_windows = S hop_windows) measured faster, with the
+    general path's bits instead of the family's (profiles/stream_bank_bench.txt).
+
+    threshold (None: no decisions, stable is None): the debounced decision per feed, updated after the average for every feed
+    whose `seen` moved this tick, feeds ascending -- conf >= float32(threshold) and label == cand: run += 1; else conf >=
+    float32(threshold): cand = label, run = 1; else cand = -1, run = 0; then, when run >= hold and cand != stable: stable = cand
+    and one event (feed, frame = count - 1, label) with its conf is appended to a log of log_capacity rows on the device (a
+    full log drops the event and counts it).  events() -> BankEvents(rows int64 (n, 3), conf fp32 [n], dropped) on the host: the
+    only synchronisation.  clear_events() empties the log on the device.  state_dict() / load_state_dict() carry the bank's
+    buffers and states, the averages, the debounce state and the log."""
+
+    def __init__(self, model, bank, window, hop_windows=1, hop=None, beta=0.0, time_steps=None, window_size=None, stream='joint',
+                 parent=None, frames_per_step=1, eager=False, chunk_windows=None, threshold=None, hold=1, log_capacity=4096):
+        who = self._who = 'LiveBank'
+        if not isinstance(bank, RingBank):
+            raise ValueError(f'{who}: bank must be a RingBank')
+        self.window, self.B = _int('window', window, 1, who), _int('hop_windows', hop_windows, 1, who)
+        self.hop = _int('hop', window if hop is None else hop, 1, who)
+        self.n = _int('frames_per_step', frames_per_step, 1, who)
+        if not (isinstance(beta, (int, float)) and not isinstance(beta, bool) and 0.0 <= beta < 1.0):
+            raise ValueError(f'{who}: beta = {beta!r} outside [0, 1)')
+        if threshold is not None and not (isinstance(threshold, (int, float)) and not isinstance(threshold, bool) and threshold == threshold):
+            raise ValueError(f'{who}: threshold = {threshold!r} must be None or a number')
+        self.hold = _int('hold', hold, 1, who)
+        self.log_capacity = _int('log_capacity', log_capacity, 1, who)
+        if chunk_windows is not None:
+            _int('chunk_windows', chunk_windows, 1, who)
+        need = self.window + (self.B - 1) * self.hop
+        if bank.capacity < need:
+            raise ValueError(f'{who}: a ring holds {bank.capacity} frames, window + (hop_windows - 1) hop = {need} are needed')
+        if self.n > bank.capacity:
+            raise ValueError(f'{who}: frames_per_step = {self.n} above the rings\' capacity {bank.capacity}')
+        first = model.models[0] if hasattr(model, 'models') else model
+        if getattr(first, 'num_point', None) != bank.V:
+            raise ValueError(f'{who}: the model has {getattr(first, "num_point", None)} joints, the bank {bank.V}')
+        self._w = _Windows(who, model, bank.prep, time_steps, window_size, stream, parent, bank.V, bank.C, bank.M)
+        self.model, self.bank, self.beta, self.eager = model, bank, float(beta), bool(eager)
+        self.threshold = None if threshold is None else float(threshold)
+        S = self.S = bank.feeds
+        if chunk_windows is None:                                     # as few family-sized passes as it takes, of equal size
+            self.chunks = -(-S * self.B // _family_batch(model, self._w.T, bank.V, bank.M))
+            self.chunk = -(-S * self.B // self.chunks)
+        else:
+            self.chunk = min(chunk_windows, S * self.B)
+            self.chunks = -(-S * self.B // self.chunk)
+        dev = self._dev = bank.buf.device
+        self._w.bind(dev)
+        self._frames = torch.zeros(bank.frames_shape(self.n), dtype=bank.buf.dtype, device=dev)
+        self._counts = torch.full((S,), self.n, dtype=torch.int32, device=dev)
+        self._restart = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._all, self._none = True, True                            # _counts holds n everywhere; _restart holds zeros
+        with torch.no_grad():
+            K = self._warm().shape[1]
+        if K > ops.STREAM_MAX_K:
+            raise ValueError(f'{who}: {K} classes above {ops.STREAM_MAX_K}')
+        self.num_class = K
+        self.ema = torch.zeros(S, K, dtype=torch.float64, device=dev)
+        self.seen = torch.zeros(S, dtype=torch.int64, device=dev)
+        self.deb = torch.tensor([-1, -1, 0], dtype=torch.int64, device=dev).repeat(S, 1)       # (stable, cand, run)
+        self.log_rows = torch.zeros(self.log_capacity, 3, dtype=torch.int64, device=dev)
+        self.log_conf = torch.zeros(self.log_capacity, dtype=torch.float32, device=dev)
+        self.log_count = torch.zeros(2, dtype=torch.int64, device=dev)                          # (written, dropped)
+        self._graph = self._out = self._keep = None
+        self._watch = _StateWatch(model)
+        self.captures = 0
+        if not self.eager:
+            self._capture()
+
+    def _logits(self):
+        """plan -> windows -> derive -> forward, chunk by chunk, on the bank as it stands: (plan (S B, 2), logits (S B, K))."""
+        w, bank, S, B = self._w, self.bank, self.S, self.B
+        rows = self.chunks * self.chunk
+        plan = ops.bank_plan(bank.state, bank.capacity, B, self.window, self.hop, self._counts, rows=rows)
+        if w.prep == 'nucla':
+            x = ops.bank_window_nucla(bank.buf, plan, B, w.parent, w.T, NUCLA_CENTER_JOINT, w.stream)
+        else:
+            x = ops.stream_derive(ops.bank_window_clip(bank.buf, plan, B, w.T), w.parent, w.stream)
+        logits = None
+        for c in range(self.chunks):
+            out = w.forward_one_stream(self.model, x[c * self.chunk:(c + 1) * self.chunk])
+            if out.dim() != 2 or out.shape[0] != self.chunk:
+                raise ValueError(f'LiveBank: the model returned {tuple(out.shape)}, expected ({self.chunk}, num_class)')
+            if self.chunks == 1:
+                logits = out
+                break
+            if logits is None:
+                logits = torch.empty(rows, out.shape[1], dtype=torch.float32, device=out.device)
+            logits[c * self.chunk:(c + 1) * self.chunk].copy_(out)       # out may be the family's own buffer
+        return plan[:S * B], logits[:S * B]
+
+    def _warm(self):
+        """The read-only part of the chain (nothing of the bank, the averages or the log moves)."""
+        return self._logits()[1]
+
+    def _chain(self):
+        bank = self.bank
+        ops.bank_push(self._frames, bank.buf, bank.state, self._counts, self._restart)
+        plan, logits = self._logits()
+        probs, _, _ = ops.window_vote(logits, plan)
+        smoothed, label, conf, advanced = ops.bank_ema(probs, plan, self.beta, self.ema, self.seen, self._restart)
+        stable = None
+        if self.threshold is not None:
+            ops.bank_decide(label, conf, advanced, bank.state, self.threshold, self.hold, self.deb, self.log_rows, self.log_conf, self.log_count,
+                            self._restart)
+            stable = self.deb[:, 0]
+        return BankStep(label, conf, smoothed, logits.view(self.S, self.B, -1), stable)
+
+    def _flags(self, name, given, own, default, is_default):
+        """Copy counts / restart into the chain's tensor; None fills the default once.  -> whether `own` now holds the default."""
+        given = _feed_flags('LiveBank.step', name, given, self.S)
+        if given is None:
+            if not is_default:
+                own.fill_(default)
+            return True
+        own.copy_(given)
+        return False
+
+    def step(self, frames, counts=None, restart=None):
+        if self.model.training:
+            raise RuntimeError('LiveBank: the model is in train() mode; call model.eval() before a step')
+        if not torch.is_tensor(frames) or not frames.is_cuda:
+            raise RuntimeError('LiveBank.step: expected a HIP (cuda) tensor; there is no CPU path')
+        if tuple(frames.shape) != tuple(self._frames.shape) or not frames.is_floating_point():
+            raise ValueError(f'LiveBank.step: frames must be {tuple(self._frames.shape)} floats, got {tuple(frames.shape)} {frames.dtype}')
+        moved = self._watch.moved()
+        self._frames.copy_(frames)
+        self._all = self._flags('counts', counts, self._counts, self.n, self._all)
+        self._none = self._flags('restart', restart, self._restart, 0, self._none)
+        with torch.no_grad():
+            if self.eager:                                            # an eager chain folds a new state by itself
+                return self._chain()
+            if moved or self._graph is None:
+                self._capture()
+        self._graph.replay()
+        return self._out
+
+    def invalidate(self):
+        self._watch.invalidate()
+
+    def events(self):
+        """BankEvents(rows int64 (n, 3) = (feed, frame, label), conf fp32 [n], dropped) on the host, in the order tick, then feed."""
+        written, dropped = self.log_count.tolist()                    # the synchronisation
+        return BankEvents(self.log_rows[:written].cpu(), self.log_conf[:written].cpu(), dropped)
+
+    def clear_events(self):
+        self.log_count.zero_()
+
+    def reset(self):
+        self.bank.reset()
+        self.ema.zero_()
+        self.seen.zero_()
+        self.deb.copy_(torch.tensor([-1, -1, 0], dtype=torch.int64, device=self._dev).repeat(self.S, 1))
+        self.clear_events()
+
+    def _resumable(self):
+        return dict(buf=self.bank.buf, state=self.bank.state, ema=self.ema, seen=self.seen, deb=self.deb, log_rows=self.log_rows,
+                    log_conf=self.log_conf, log_count=self.log_count)
+
+    def state_dict(self):
+        """Copies of what a service needs to resume: the bank's buffers and states, the averages, the debounce state, the log."""
+        return {k: v.detach().clone() for k, v in self._resumable().items()}
+
+    def load_state_dict(self, sd):
+        own = self._resumable()
+        if set(sd) != set(own):
+            raise ValueError(f'LiveBank.load_state_dict: keys {sorted(sd)} are not {sorted(own)}')
+        for k, v in own.items():
+            if not torch.is_tensor(sd[k]) or tuple(sd[k].shape) != tuple(v.shape) or sd[k].dtype != v.dtype:
+                raise ValueError(f'LiveBank.load_state_dict: {k} must be {tuple(v.shape)} {v.dtype}')
+        for k, v in own.items():
+            v.copy_(sd[k])                                            # in place: the graph holds these addresses

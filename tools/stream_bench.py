@@ -13,6 +13,15 @@ profiles/stream_infer_bench.txt).
         `steps` live steps per dataset and one sliding pass each -- run it under rocprofv3 --kernel-trace --stats
     python tools/stream_bench.py report <kernel_trace.csv>
         the streaming kernels' times from that run, and the window kernels' bytes per second with the bytes computed from shapes
+    python tools/stream_bench.py bank [rounds] [ticks]                        (profiles/stream_bank_bench.txt)
+        S feeds at once, S = 1 4 8 16 32 64, one frame per feed and tick, on N-UCLA CTR-GCN (window 40 -> 52 steps), COCO CTR-GCN
+        (window 64) and N-UCLA ST-GCN: (a) LiveBank.step, one graph replay for all feeds; (b) S LiveClassifier graph replays one
+        after another (the code as it stood before the bank: the baseline); (c) LiveBank with chunk_windows = S, one forward of
+        all windows, where S is past the small-batch family's bound (elsewhere (c) is (a)).  ms per tick and feeds per 33 ms.
+    python tools/stream_bench.py bank-trace [ticks]
+        `ticks` LiveBank ticks per model at S = 32 with the decision log on -- run it under rocprofv3 --kernel-trace --stats
+    python tools/stream_bench.py bank-report <kernel_trace.csv>
+        the bank kernels' times from that run
 
 The models carry seeded parameters (tests/golden/params.py); their accuracy is not the subject."""
 import csv
@@ -32,6 +41,9 @@ COCO = dict(num_class=10, num_point=17, num_person=1, graph='tam_gcn_amd.graph.c
 SETS = {'nucla': (UCLA, 'nucla', 40, 52), 'coco': (COCO, 'clip', 64, 64)}
 SEQ_LEN, HOP = 2000, 8
 PASSES = 10                    # sliding passes per timed window
+BANK_FEEDS = (1, 4, 8, 16, 32, 64)
+BANK_KERNELS = ('bank_push_kernel', 'bank_advance_kernel', 'bank_plan_kernel', 'bank_window_nucla_kernel', 'bank_window_clip_kernel',
+                'window_softmax_kernel', 'bank_ema_kernel', 'bank_decide_kernel')
 KERNELS = ('ring_push_kernel', 'ring_advance_kernel', 'ring_plan_kernel', 'window_nucla_kernel', 'window_clip_kernel', 'window_softmax_kernel',
            'window_vote_kernel', 'score_ema_kernel')
 
@@ -43,6 +55,98 @@ def _model(margs):
     m = Model(**margs)
     fill_state_(m.state_dict(), seed=0)
     return m.to(DEV).eval()
+
+
+def _bank_sets():
+    """name -> (model, prep, V, window, LiveClassifier / LiveBank keywords)"""
+    from params import fill_state_
+    from tam_gcn_amd.models import stgcn
+    st = stgcn.Model(**UCLA)
+    fill_state_(st.state_dict(), seed=0)
+    return {'nucla ctrgcn': (_model(UCLA), 'nucla', 20, 40, dict(time_steps=52)),
+            'coco ctrgcn': (_model(COCO), 'clip', 17, 64, dict(window_size=64)),
+            'nucla stgcn': (st.to(DEV).eval(), 'nucla', 20, 40, dict(time_steps=52))}
+
+
+def _bank_frames(prep, V, S, n, seed=0):
+    """n ticks of one frame per feed, in the bank's push form: [(S, 1, V, 3) fp64] or [(S, 3, 1, V, 1) fp32]"""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(seed)
+    if prep == 'nucla':
+        seq = rng.normal(size=(S, 1, V, 3)) + 0.05 * np.cumsum(rng.normal(size=(S, n, V, 3)), axis=1)
+        return [torch.from_numpy(np.ascontiguousarray(seq[:, i:i + 1])).to(DEV) for i in range(n)]
+    seq = rng.uniform(-1.0, 1.0, size=(S, 3, n, V, 1)).astype(np.float32)
+    return [torch.from_numpy(np.ascontiguousarray(seq[:, :, i:i + 1])).to(DEV) for i in range(n)]
+
+
+def cmd_bank(rounds, ticks):
+    import torch
+    from tam_gcn_amd import streaming
+    assert torch.cuda.is_available(), 'stream_bench: no GPU'
+    print(f'# {torch.cuda.get_device_name(0)}; {rounds} rounds, legs alternated in one process; {ticks} ticks per timed window; '
+          'one frame per feed and tick, beta 0.8, decision log on (threshold 0.6, hold 3)')
+    for name, (model, prep, V, window, kw) in _bank_sets().items():
+        kw = dict(kw, window=window, beta=0.8)
+        bound = streaming._family_batch(model, kw.get('time_steps') or kw['window_size'], V, 1)
+        alone = [streaming.LiveClassifier(model, streaming.FrameRing(128, prep=prep, V=V, device=DEV), **kw) for _ in range(max(BANK_FEEDS))]
+        print(f'\n{name}: window {window}, the small-batch family takes {bound} windows per forward')
+        print(f'{"S":>3s}  {"leg":<52s} {"ms / tick":>10s}  {"spread":>19s}  {"feeds / 33 ms":>13s}')
+        for S in BANK_FEEDS:
+            frames = _bank_frames(prep, V, S, window + ticks)
+            mk = lambda **more: streaming.LiveBank(model, streaming.RingBank(S, 128, prep=prep, V=V, device=DEV), threshold=0.6, hold=3,     # noqa: E731
+                                                   **kw, **more)
+            bank = mk()
+            legs = {f'(a) LiveBank.step, {bank.chunks} forward(s) of {bank.chunk}': lambda: [bank.step(f) for f in frames[window:]],
+                    f'(b) {S} LiveClassifier replays': lambda: [[alone[s].step(f[s]) for s in range(S)] for f in frames[window:]]}
+            one = mk(chunk_windows=S) if S > bound else None
+            if one is not None:
+                legs[f'(c) LiveBank, one forward of {S}'] = lambda: [one.step(f) for f in frames[window:]]
+            with torch.no_grad():
+                for a in alone[:S]:
+                    a.reset()
+                for f in frames[:window]:                                    # fill every ring, warm every shape
+                    bank.step(f)
+                    if one is not None:
+                        one.step(f)
+                    for s in range(S):
+                        alone[s].step(f[s])
+                res = {k: [] for k in legs}
+                for _ in range(rounds):
+                    for k, fn in legs.items():
+                        res[k].append(_timed(fn) / ticks)
+            for k, v in res.items():
+                med = statistics.median(v)
+                print(f'{S:>3d}  {k:<52s} {med:>10.3f}  {min(v):>8.3f} .. {max(v):>7.3f}  {S * 33.0 / med:>13.0f}')
+            meds = [statistics.median(v) for v in res.values()]
+            print(f'     (b) / (a) = {meds[1] / meds[0]:.2f}x' + (f'   (c) / (a) = {meds[2] / meds[0]:.2f}x' if one is not None else '')
+                  + f'   captures {bank.captures}')
+            del bank, one, legs
+
+
+def cmd_bank_trace(ticks):
+    import torch
+    from tam_gcn_amd import streaming
+    S = 32
+    for name, (model, prep, V, window, kw) in _bank_sets().items():
+        live = streaming.LiveBank(model, streaming.RingBank(S, 128, prep=prep, V=V, device=DEV), window=window, beta=0.8, threshold=0.6, hold=3, **kw)
+        for f in _bank_frames(prep, V, S, window + ticks):
+            live.step(f)
+        torch.cuda.synchronize()
+
+
+def cmd_bank_report(path):
+    by = {}
+    for r in csv.DictReader(open(path)):
+        n = r['Kernel_Name']
+        if any(k in n for k in BANK_KERNELS):
+            short = n.replace('(anonymous namespace)::', '').replace('void ', '').split('(')[0]
+            grid = int(r.get('Grid_Size_X') or r.get('Grid_Size') or 0)
+            by.setdefault((short, grid), []).append((int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3)
+    print('# kernel times of the bank path at S = 32 (rocprofv3 --kernel-trace, a run of its own), per kernel and grid (threads)')
+    print(f'{"kernel":<56s} {"grid":>8s} {"calls":>6s} {"median us":>10s} {"min us":>8s} {"max us":>8s}')
+    for (short, grid), t in sorted(by.items()):
+        print(f'{short:<56s} {grid:>8d} {len(t):>6d} {statistics.median(t):>10.2f} {min(t):>8.2f} {max(t):>8.2f}')
 
 
 def _sequence(prep, V, n, seed=0):
@@ -242,5 +346,11 @@ if __name__ == '__main__':
         cmd_trace(int(sys.argv[2]) if len(sys.argv) > 2 else 200)
     elif what == 'report':
         cmd_report(sys.argv[2])
+    elif what == 'bank':
+        cmd_bank(int(sys.argv[2]) if len(sys.argv) > 2 else 7, int(sys.argv[3]) if len(sys.argv) > 3 else 100)
+    elif what == 'bank-trace':
+        cmd_bank_trace(int(sys.argv[2]) if len(sys.argv) > 2 else 100)
+    elif what == 'bank-report':
+        cmd_bank_report(sys.argv[2])
     else:
         sys.exit(__doc__)
