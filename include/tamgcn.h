@@ -1041,40 +1041,66 @@ typedef struct tamgcn_grad_guard {
 int tamgcn_optim_step_guarded(const tamgcn_optim_desc* d, const tamgcn_grad_guard* g, void* stream);
 
 /* ------------------------------------------------------------------------
- * Live and sliding-window inference from a device-resident frame ring (csrc/streaming.hip, tam_gcn_amd/streaming.py).
- * Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed.
+ * Live and sliding-window inference from device-resident frame rings (csrc/streaming.hip, tam_gcn_amd/streaming.py): a bank of
+ * S rings for S live feeds in one graph.  Added in ABI 401 without a version bump: new entry points, no existing layout or
+ * semantics changed.
  *
- * Frames are numbered absolutely in int64 from 0, the first frame ever pushed; frame f lives in slot f % cap.  A ring is
- * logically (P, cap, R) with elements of `elem` bytes: P = 1, R = V 3, elem = 8 is fp64 (cap, V, 3), the raw form
+ * Frames are numbered absolutely in int64 from 0, the first frame a feed was ever pushed; frame f lives in slot f % cap.  A ring
+ * is logically (P, cap, R) with elements of `elem` bytes: P = 1, R = V 3, elem = 8 is fp64 (cap, V, 3), the raw form
  * tamgcn_feeder_transform reads; P = C, R = V M, elem = 4 is fp32 (C, cap, V, M), the clip feeder's layout with T = cap.
- * A sequence that is resident as a whole is a ring of cap = its length that never wraps.  A plan is int64 (B, 2) =
- * (start, L) per window; L = 0 marks an invalid window, and so does any row with start < 0 or L > cap.  No entry point
- * synchronises, none uses floating-point atomics: two calls give the same bits, a graph replay the eager call's.
+ * A sequence that is resident as a whole is a ring of cap = its length that never wraps.  The bank is S rings in one
+ * allocation, feed s at s (P cap R) elements: fp64 (S, cap, V, 3) or fp32 (S, C, cap, V, M).  state int64 (S, 2) = (count,
+ * pushes) per feed, on the device.  1 <= S <= 1024.  counts and restart are int32 [S] on the device and may be NULL (every feed
+ * takes all n frames; no feed restarts).  take_s = min(max(counts[s], 0), n); fresh_s = restart[s] != 0.  A plan is int64
+ * (S B, 2) = (start, L) per window, window w that of feed w / B; L = 0 marks an invalid window, and so does any row with
+ * start < 0 or L > cap.  No entry point synchronises, none uses atomics: two calls give the same bits, a graph replay the
+ * eager call's.
  *
- *   _ring_push     frames (P, n, R) -> slots (count + i) % cap of every plane, 1 <= n <= cap.  state int64 [2] =
- *                  (count, pushes) on the device, read by this launch and advanced by a one-thread launch behind it.
- *                  16-byte accesses where R elem is a multiple of 16 and both arrays are 16-byte aligned.
- *   _ring_plan     window j of B has length L and ends (B - 1 - j) hop frames before the newest frame: j = B - 1 is the
- *                  newest.  A window that would start before frame 0 or before count - cap (overwritten) gets (0, 0).
- *                  1 <= L <= cap, hop >= 1.
- *   _window_nucla  out (B, 3, time_steps, V, 1) fp32: the arithmetic of tamgcn_feeder_transform on the window's L frames
- *                  with the identity view and idx = np.linspace(0, L - 1, time_steps).astype(int) -- centre on
- *                  center_joint of the window's first frame, per-coordinate min / max over the window,
- *                  (p - lo) / (hi - lo + 1e-6) * 2 - 1 in fp64, the stream `mode` 0..3 -- one body with that kernel, so
- *                  bit-equal to it on a copy of the window's frames.  time_steps <= 64.  Invalid windows: zeros.
- *   _window_clip   out (B, C, W, V, M) fp32: the linear time-resize of tamgcn_clip_resize on the crop (start, L) without
- *                  rotation -- the same taps, src = ((2 t + 1) L - W) / (2 W) clamped at 0 as that kernel computes it in
- *                  fp32, the same blend l0 x[i0] + l1 x[i1] without contraction -- sources fetched at (start + i) % cap.
- *                  L = W copies the frames (l1 = 0; a -0.0 comes out +0.0, as from tamgcn_clip_resize).  Invalid: zeros.
- *   _window_vote   probs[j] = softmax(logits[j]) over K <= 4096 classes: fp64 from the fp32 logits, max shift, the sum class
- *                  ascending, rounded once to fp32.  frame_scores[f], f < n_frames: the mean over j ascending of probs[j]
- *                  (the fp32 values, summed in fp64, rounded once) of the valid windows with start_j <= f < start_j + L_j;
- *                  frame_label[f] int64 its first arg max; no such window: zeros and -1.  frame_scores and frame_label
- *                  may both be NULL: only probs is written.  One launch, two with the frame outputs.
- *   _score_ema     plan_row: one plan row.  Valid: ema = probs when *seen == 0, else beta ema + (1 - beta) probs in fp64,
- *                  then *seen += 1; invalid: nothing moves.  out = (float)ema, *label = the first arg max of ema or -1
- *                  while *seen == 0, *conf = out[*label] (0 with -1).  ema fp64 [K], seen int64 [1], K <= 4096,
- *                  0 <= beta < 1. */
+ *   _bank_push          frames (S, P, n, R), 1 <= n <= cap: feed s stores the first take_s frames of its slice at slots
+ *                       (c_s + i) % cap of every plane, c_s = fresh_s ? 0 : count_s; a unit of a frame i >= take_s is neither
+ *                       read nor stored (it may hold NaN).  A second launch behind it, one thread per feed: fresh_s ->
+ *                       (count, pushes) = (0, 0) first; then count += take_s and pushes += 1 where take_s > 0.  take_s = 0
+ *                       without restart: nothing of feed s moves.  16-byte accesses where R elem is a multiple of 16 (the feed
+ *                       strides then are too) and both arrays are 16-byte aligned.
+ *   _bank_plan          plan (S B, 2): window j of a feed's B has length L and ends (B - 1 - j) hop frames before the feed's
+ *                       newest frame: j = B - 1 is the newest.  A window that would start before frame 0 or before
+ *                       count_s - cap (overwritten) gets (0, 0), and so does every window of a feed with counts[s] <= 0.
+ *                       1 <= L <= cap, hop >= 1.  Run it behind _bank_push: it reads the advanced state.
+ *   _bank_window_nucla  out (S B, 3, time_steps, V, 1) fp32, plan row w on the ring of feed w / B: the arithmetic of
+ *                       tamgcn_feeder_transform on the window's L frames with the identity view and idx = np.linspace(0,
+ *                       L - 1, time_steps).astype(int) -- centre on center_joint of the window's first frame, per-coordinate
+ *                       min / max over the window, (p - lo) / (hi - lo + 1e-6) * 2 - 1 in fp64, the stream `mode` 0..3 -- one
+ *                       body with that kernel, so bit-equal to it on a copy of the window's frames.  time_steps <= 64.
+ *                       Invalid windows: zeros.
+ *   _bank_window_clip   out (S B, C, W, V, M) fp32, plan row w on the ring of feed w / B: the linear time-resize of
+ *                       tamgcn_clip_resize on the crop (start, L) without rotation -- the same taps, src = ((2 t + 1) L - W) /
+ *                       (2 W) clamped at 0 as that kernel computes it in fp32, the same blend l0 x[i0] + l1 x[i1] without
+ *                       contraction -- sources fetched at (start + i) % cap.  L = W copies the frames (l1 = 0; a -0.0 comes
+ *                       out +0.0, as from tamgcn_clip_resize).  Invalid: zeros.
+ *   _window_vote        probs[j] = softmax(logits[j]) over K <= 4096 classes, for the rows of any number of feeds: fp64 from the
+ *                       fp32 logits, max shift, the sum class ascending, rounded once to fp32.  frame_scores[f], f < n_frames
+ *                       (one ring's plan): the mean over j ascending of probs[j] (the fp32 values, summed in fp64, rounded
+ *                       once) of the valid windows with start_j <= f < start_j + L_j; frame_label[f] int64 its first arg max;
+ *                       no such window: zeros and -1.  frame_scores and frame_label may both be NULL: only probs is written.
+ *                       One launch, two with the frame outputs.
+ *   _bank_ema           one workgroup per feed, its B windows (probs and plan rows s B + j) j ascending, on ema (S, K) fp64 and
+ *                       seen int64 [S].  A valid window: ema_s = probs when seen_s == 0, else beta ema_s + (1 - beta) probs in
+ *                       fp64, then seen_s += 1; an invalid one moves nothing.  fresh_s: the average reads as zeros and seen as
+ *                       0 first (both are stored, a valid window or not).  After the last window out[s] = (float)ema_s,
+ *                       label[s] = the first arg max of ema_s or -1 while seen_s == 0, conf[s] = out[s][label[s]] (0 with -1),
+ *                       advanced int32 [S] = 1 where seen moved.  K <= 4096, 0 <= beta < 1.
+ *   _bank_decide        one workgroup; the debounce of every feed, then the events in ascending feed order through a scan.
+ *                       deb int64 (S, 3) = (stable, cand, run), (-1, -1, 0) at the start and where fresh_s.  Where advanced[s]:
+ *                       conf[s] >= threshold and label[s] == cand: run += 1; else conf[s] >= threshold: cand = label[s],
+ *                       run = 1; else cand = -1, run = 0; then, if run >= hold and cand != stable: stable = cand and one event
+ *                       (s, count_s - 1, label[s]) with conf[s].  log_rows int64 (log_capacity, 3), log_conf fp32
+ *                       [log_capacity], log_count int64 [2] = (written, dropped): an event goes to row `written`; a full log
+ *                       drops it and counts it, it never overwrites.  hold >= 1, log_capacity >= 1.
+ *
+ * One ring: _ring_push, _ring_plan, _window_nucla, _window_clip and _score_ema are _bank_push, _bank_plan, _bank_window_nucla,
+ * _bank_window_clip and _bank_ema at S = 1 with NULL counts and restart (the same kernels): ring (P, cap, R), state int64 [2],
+ * plan (B, 2).  _score_ema takes one window (B = 1): plan_row is its plan row, ema fp64 [K], seen int64 [1], and there is no
+ * `advanced`. */
 int tamgcn_ring_push(const void* frames, int n, int P, int R, int elem, void* ring, int cap, long long* state, void* stream);
 int tamgcn_ring_plan(const long long* state, int cap, int B, int L, int hop, long long* plan, void* stream);
 int tamgcn_window_nucla(const double* ring, int cap, const long long* plan, int B, const int* parent, int V, int time_steps,
@@ -1084,38 +1110,6 @@ int tamgcn_window_vote(const float* logits, const long long* plan, int B, int K,
                        long long* frame_label, void* stream);
 int tamgcn_score_ema(const float* probs, const long long* plan_row, int K, double beta, double* ema, long long* seen, float* out,
                      long long* label, float* conf, void* stream);
-
-/* ------------------------------------------------------------------------
- * A bank of S frame rings for S live feeds in one graph (csrc/streaming.hip, tam_gcn_amd/streaming.py RingBank / LiveBank).
- * Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed.
- *
- * The bank is S rings in one allocation, feed s at s (P cap R) elements: fp64 (S, cap, V, 3) or fp32 (S, C, cap, V, M); feed
- * s alone is the ring described above.  state int64 (S, 2) = (count, pushes) per feed.  1 <= S <= 1024.  counts and restart
- * are int32 [S] on the device and may be NULL (every feed takes all n frames; no feed restarts).  take_s =
- * min(max(counts[s], 0), n); fresh_s = restart[s] != 0.  The arithmetic is the single-ring kernels' own (one body each).
- * No entry point synchronises, none uses atomics: two runs give the same bits.
- *
- *   _bank_push          frames (S, P, n, R): feed s stores the first take_s frames of its slice at slots (c_s + i) % cap, c_s =
- *                       fresh_s ? 0 : count_s; a unit of a frame i >= take_s is neither read nor stored (it may hold NaN).
- *                       A second launch behind it: fresh_s -> (count, pushes) = (0, 0) first; then count += take_s and
- *                       pushes += 1 where take_s > 0.  take_s = 0 without restart: nothing of feed s moves.  16-byte
- *                       accesses where R elem and both feed strides are multiples of 16 and both arrays are aligned.
- *   _bank_plan          plan (S B, 2): row s B + j = _ring_plan's row j on feed s's count; (0, 0) rows for a feed with
- *                       counts[s] <= 0.  Run it behind _bank_push: it reads the advanced state.
- *   _bank_window_nucla  out (S B, 3, time_steps, V, 1): _window_nucla's window, plan row w on the ring of feed w / B.
- *   _bank_window_clip   out (S B, C, W, V, M): _window_clip's window, plan row w on the ring of feed w / B.
- *   (softmax)           tamgcn_window_vote without frame outputs serves the S B rows.
- *   _bank_ema           one workgroup per feed: _score_ema's update for the feed's B windows (probs and plan rows s B + j),
- *                       j ascending, on ema (S, K) fp64 and seen int64 [S].  fresh_s: the average reads as zeros and seen as 0
- *                       (both are stored, a valid window or not).  out (S, K), label [S], conf [S] as _score_ema's after
- *                       the last window; advanced int32 [S] = 1 where seen moved.
- *   _bank_decide        one workgroup; the debounce of every feed, then the events in ascending feed order through a scan.
- *                       deb int64 (S, 3) = (stable, cand, run), (-1, -1, 0) at the start and where fresh_s.  Where advanced[s]:
- *                       conf[s] >= threshold and label[s] == cand: run += 1; else conf[s] >= threshold: cand = label[s],
- *                       run = 1; else cand = -1, run = 0; then, if run >= hold and cand != stable: stable = cand and one event
- *                       (s, count_s - 1, label[s]) with conf[s].  log_rows int64 (log_capacity, 3), log_conf fp32
- *                       [log_capacity], log_count int64 [2] = (written, dropped): an event goes to row `written`; a full log
- *                       drops it and counts it, it never overwrites.  hold >= 1, log_capacity >= 1. */
 int tamgcn_bank_push(const void* frames, int S, int n, int P, int R, int elem, void* ring, int cap, long long* state, const int* counts,
                      const int* restart, void* stream);
 int tamgcn_bank_plan(const long long* state, const int* counts, int S, int cap, int B, int L, int hop, long long* plan, void* stream);

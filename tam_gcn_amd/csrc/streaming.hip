@@ -1,14 +1,13 @@
-// Live and sliding-window inference (tam_gcn_amd/streaming.py): a ring of skeleton frames in HBM that is pushed to without the
-// host, the model's input windows built straight from the ring through either feeder's val-path arithmetic (feeder_common.h:
-// the bodies feeder.hip and clipfeeder.hip run), and what a sliding-window user does with the scores: softmax, per-frame
-// voting, an exponential moving average.  And the same for S feeds at once from a bank of S rings (the bank_* kernels: the
-// single-ring bodies at feed w / B's ring, per-feed counts and restarts read on the device, a debounced decision log).
-// include/tamgcn.h has the contract.
+// Live and sliding-window inference (tam_gcn_amd/streaming.py): a bank of S rings of skeleton frames in HBM, one ring per feed,
+// that is pushed to without the host, the model's input windows built straight from the rings through either feeder's val-path
+// arithmetic (feeder_common.h: the bodies feeder.hip and clipfeeder.hip run), and what a sliding-window user does with the
+// scores: softmax, per-frame voting, an exponential moving average per feed, a debounced decision log.  One ring is a bank of
+// S = 1 without counts or restarts: the single-ring entry points forward to the bank's.  include/tamgcn.h has the contract.
 //
-// Frames are numbered absolutely from 0 (the first frame ever pushed); frame f lives in slot f % cap of a ring that is
-// logically (P, cap, R): (1, cap, V 3) fp64 for the N-UCLA transform, (C, cap, V M) fp32 for the clip feeder's layout.  A
-// sequence that is resident as a whole is a ring of cap = its length that never wraps.  No floating-point atomics anywhere:
-// every sum has one order, so two calls give the same bits and a graph replay gives the eager call's.
+// Frames are numbered absolutely from 0 (the first frame a feed was ever pushed); frame f lives in slot f % cap of a ring that is
+// logically (P, cap, R): (1, cap, V 3) fp64 for the N-UCLA transform, (C, cap, V M) fp32 for the clip feeder's layout; feed s is
+// at s * (P cap R).  A sequence that is resident as a whole is a ring of cap = its length that never wraps.  No floating-point
+// atomics anywhere: every sum has one order, so two calls give the same bits and a graph replay gives the eager call's.
 #include "common.h"
 #include "feeder_common.h"
 
@@ -16,49 +15,20 @@ namespace {
 
 constexpr int STREAM_MAX_TS = 64;        // the N-UCLA window's time_steps (the feeder's draw kernel has the same limit)
 constexpr int STREAM_MAX_K = 4096;       // classes: one softmax row as fp64 in LDS
+constexpr int BANK_MAX_FEEDS = 1024;     // bank_decide_kernel: one workgroup, four feeds per thread
 
 // Python's f % cap for cap > 0: slot of frame f (f >= 0 wherever a valid window reads)
 __device__ __forceinline__ long long slot_of(long long f, int cap) { return clip_of(f, cap); }
 
-// ---- the ring --------------------------------------------------------------------------------------------------------
-// where unit e of a (P, n, R) push goes: frame i of the push, offset dst into a (P, cap, units) ring whose count is count()
-// (one text for ring_push_kernel and bank_push_kernel)
-struct PushUnit { int i; long long dst; };
-
-template <class Count>
-__device__ __forceinline__ PushUnit push_unit(long long e, int n, int units, int cap, Count count) {
-    const int u = (int)(e % units);
-    const long long row = e / units;                   // (p, i)
-    const int i = (int)(row % n);
-    const long long p = row / n;
-    const long long slot = slot_of(count() + i, cap);
-    return {i, (p * cap + slot) * units + u};
-}
-
-// One thread per unit U (16 bytes where the rows and addresses allow it, else one element) of the (P, n, R) frames; frame i
-// of the push goes to slot (count + i) % cap of every plane.  count is read here and moved by ring_advance_kernel behind
-// this launch on the same stream, so a graph that holds both pushes to new slots on every replay.
-template <class U>
-__global__ __launch_bounds__(256) void ring_push_kernel(const U* __restrict__ frames, int n, int units, long long total, U* __restrict__ ring,
-                                                        int cap, const long long* __restrict__ state) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const PushUnit w = push_unit(e, n, units, cap, [&] { return state[0]; });
-    ring[w.dst] = frames[e];
-}
-
-__global__ void ring_advance_kernel(long long* __restrict__ state, int n) {
-    state[0] = state[0] + n;
-    state[1] = state[1] + 1;
-}
-
-// ---- the bank: S rings in one allocation, feed s at s * (P cap R) ------------------------------------------------------------
+// ---- the rings -------------------------------------------------------------------------------------------------------
 // what feed s takes of a tick's n frames, and whether it is forgotten first (counts, restart: int32 [S] or null)
 __device__ __forceinline__ int bank_take(const int* __restrict__ counts, int s, int n) { return counts ? min(max(counts[s], 0), n) : n; }
 __device__ __forceinline__ bool bank_fresh(const int* __restrict__ restart, int s) { return restart && restart[s] != 0; }
 
-// blockIdx.y = feed; blockIdx.x, threadIdx.x: ring_push_kernel's unit e of that feed's (P, n, R) slice.  A restarted feed's count
-// reads as 0; a unit of a frame beyond the feed's take stores nothing (and is not loaded).
+// blockIdx.y = feed; one thread per unit U (16 bytes where the rows and addresses allow it, else one element) of the feed's
+// (P, n, R) frames; frame i of the push goes to slot (count + i) % cap of every plane.  A restarted feed's count reads as 0; a
+// unit of a frame beyond the feed's take stores nothing (and is not loaded).  count is read here and moved by
+// bank_advance_kernel behind this launch on the same stream, so a graph that holds both pushes to new slots on every replay.
 template <class U>
 __global__ __launch_bounds__(256) void bank_push_kernel(const U* __restrict__ frames, int n, int units, long long total, U* __restrict__ ring,
                                                         int cap, long long ring_units, const long long* __restrict__ state,
@@ -66,8 +36,12 @@ __global__ __launch_bounds__(256) void bank_push_kernel(const U* __restrict__ fr
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
     const int s = blockIdx.y;
-    const PushUnit w = push_unit(e, n, units, cap, [&] { return bank_fresh(restart, s) ? 0 : state[2 * s]; });
-    if (w.i < bank_take(counts, s, n)) ring[s * ring_units + w.dst] = frames[s * total + e];
+    const int u = (int)(e % units);
+    const long long row = e / units;                   // (p, i)
+    const int i = (int)(row % n);
+    const long long p = row / n;
+    const long long slot = slot_of((bank_fresh(restart, s) ? 0 : state[2 * s]) + i, cap);
+    if (i < bank_take(counts, s, n)) ring[s * ring_units + (p * cap + slot) * units + u] = frames[s * total + e];
 }
 
 // one thread per feed: the restart first, then the clamped count.  A feed that takes nothing and is not restarted keeps its state.
@@ -82,47 +56,31 @@ __global__ __launch_bounds__(256) void bank_advance_kernel(long long* __restrict
     state[2 * s + 1] = (fresh ? 0 : state[2 * s + 1]) + (take > 0 ? 1 : 0);
 }
 
-// Window j of B ends (B - 1 - j) hop frames before the newest frame; (0, 0) where it would start before frame 0 or before
-// count - cap (already overwritten).
-// (row w of plan: window j of its ring)
-__device__ __forceinline__ void plan_row(long long count, int cap, int B, int j, int L, int hop, long long* __restrict__ plan, int w) {
-    const long long start = count - (long long)(B - 1 - j) * hop - L;
-    const bool valid = start >= 0 && start >= count - cap;
-    plan[2 * w] = valid ? start : 0;
-    plan[2 * w + 1] = valid ? L : 0;
-}
-
-__global__ __launch_bounds__(64) void ring_plan_kernel(const long long* __restrict__ state, int cap, int B, int L, int hop,
-                                                       long long* __restrict__ plan) {
-    const int j = blockIdx.x * 64 + threadIdx.x;
-    if (j >= B) return;
-    plan_row(state[0], cap, B, j, L, hop, plan, j);
-}
-
-// window w of S B belongs to feed w / B; a feed that takes no frame this tick has no window
+// Window w of S B is window j = w % B of feed w / B: it ends (B - 1 - j) hop frames before the feed's newest frame; (0, 0) where
+// it would start before frame 0 or before count - cap (already overwritten), and for a feed that takes no frame this tick.
 __global__ __launch_bounds__(64) void bank_plan_kernel(const long long* __restrict__ state, const int* __restrict__ counts, int S, int cap, int B,
                                                        int L, int hop, long long* __restrict__ plan) {
     const int w = blockIdx.x * 64 + threadIdx.x;
     if (w >= S * B) return;
-    const int s = w / B;
-    if (counts && counts[s] <= 0) {
-        plan[2 * w] = 0;
-        plan[2 * w + 1] = 0;
-        return;
-    }
-    plan_row(state[2 * s], cap, B, w - s * B, L, hop, plan, w);
+    const int s = w / B, j = w - s * B;
+    const long long count = state[2 * s];
+    const long long start = count - (long long)(B - 1 - j) * hop - L;
+    const bool valid = !(counts && counts[s] <= 0) && start >= 0 && start >= count - cap;
+    plan[2 * w] = valid ? start : 0;
+    plan[2 * w + 1] = valid ? L : 0;
 }
 
 // a plan row the window builders accept: anything else is an invalid window (zeros)
 __device__ __forceinline__ bool window_ok(long long start, long long L, int cap) { return start >= 0 && L >= 1 && L <= cap; }
 
 // ---- windows -----------------------------------------------------------------------------------------------------------
-// One workgroup per window: feeder_transform_kernel's body on the window's L frames with the identity view and the val
-// path's frame indices.
-__device__ __forceinline__ void window_nucla_body(const double* __restrict__ ring, int cap, const long long* __restrict__ plan,
-                                                  const int* __restrict__ parent, int V, int TS, int center_joint, int mode,
-                                                  float* __restrict__ out) {
+// One workgroup per window, window b of S B on the ring of feed b / B: feeder_transform_kernel's body on the window's L frames
+// with the identity view and the val path's frame indices.
+__global__ __launch_bounds__(256) void bank_window_nucla_kernel(const double* __restrict__ bank, int cap, const long long* __restrict__ plan, int B,
+                                                                const int* __restrict__ parent, int V, int TS, int center_joint, int mode,
+                                                                float* __restrict__ out) {
     const int b = blockIdx.x;
+    const double* ring = bank + (long long)(blockIdx.x / (unsigned)B) * cap * V * 3;
     const long long start = plan[2 * b], L = plan[2 * b + 1];
     float* o = out + (long long)b * 3 * TS * V;
     if (!window_ok(start, L, cap)) {                   // uniform over the workgroup
@@ -140,19 +98,6 @@ __device__ __forceinline__ void window_nucla_body(const double* __restrict__ rin
     feeder_transform_body(point, [&](int t) { return val_frame(t, L, TS); }, L, V, TS, mode, center_joint, I, parent, o);
 }
 
-__global__ __launch_bounds__(256) void window_nucla_kernel(const double* __restrict__ ring, int cap, const long long* __restrict__ plan,
-                                                           const int* __restrict__ parent, int V, int TS, int center_joint, int mode,
-                                                           float* __restrict__ out) {
-    window_nucla_body(ring, cap, plan, parent, V, TS, center_joint, mode, out);
-}
-
-// window b of S B reads the ring of feed b / B
-__global__ __launch_bounds__(256) void bank_window_nucla_kernel(const double* __restrict__ ring, int cap, const long long* __restrict__ plan, int B,
-                                                                const int* __restrict__ parent, int V, int TS, int center_joint, int mode,
-                                                                float* __restrict__ out) {
-    window_nucla_body(ring + (long long)(blockIdx.x / (unsigned)B) * cap * V * 3, cap, plan, parent, V, TS, center_joint, mode, out);
-}
-
 template <int VEC>
 __device__ __forceinline__ void load_span(const float* __restrict__ p, float* v) {
     if constexpr (VEC == 4) {
@@ -165,12 +110,12 @@ __device__ __forceinline__ void load_span(const float* __restrict__ p, float* v)
 }
 
 // One thread per VEC consecutive positions of an output row of W VM floats; blockIdx.x = ((window, channel), tile of 256 VEC
-// positions).  clip_resize_kernel's taps and blend on the crop (start, L), the two source frames fetched at their ring slots.
-// VEC = 4 only where V M is a multiple of four and both arrays are 16-byte aligned: a span then lies inside one frame.
-// BANK: window b reads the ring of feed b / bank_B, (C, cap, VM) floats apart.
-template <int VEC, bool BANK>
-__device__ __forceinline__ void window_clip_body(const float* __restrict__ ring, int cap, const long long* __restrict__ plan, int C, int W, int VM,
-                                                 int tiles, int bank_B, float* __restrict__ out) {
+// positions); window b of S B reads the ring of feed b / B, (C, cap, VM) floats apart.  clip_resize_kernel's taps and blend on
+// the crop (start, L), the two source frames fetched at their ring slots.  VEC = 4 only where V M is a multiple of four and both
+// arrays are 16-byte aligned: a span then lies inside one frame.
+template <int VEC>
+__global__ __launch_bounds__(256) void bank_window_clip_kernel(const float* __restrict__ ring, int cap, const long long* __restrict__ plan, int B,
+                                                               int C, int W, int VM, int tiles, float* __restrict__ out) {
 #pragma clang fp contract(off)
     const unsigned blk = blockIdx.x;
     const int tile = (int)(blk % (unsigned)tiles), bc = (int)(blk / (unsigned)tiles);
@@ -193,7 +138,7 @@ __device__ __forceinline__ void window_clip_body(const float* __restrict__ ring,
         long long a0 = s0 + tp.i0, a1 = s0 + tp.i1;    // i0, i1 < L <= cap
         if (a0 >= cap) a0 -= cap;
         if (a1 >= cap) a1 -= cap;
-        const float* src = ring + (long long)(BANK ? (b / bank_B) * C + c : c) * cap * VM + vm;
+        const float* src = ring + (long long)((b / B) * C + c) * cap * VM + vm;
         float x0[VEC], x1[VEC];
         load_span<VEC>(src + a0 * VM, x0);
         load_span<VEC>(src + a1 * VM, x1);
@@ -206,18 +151,6 @@ __device__ __forceinline__ void window_clip_body(const float* __restrict__ ring,
     } else {
         o[0] = y[0];
     }
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void window_clip_kernel(const float* __restrict__ ring, int cap, const long long* __restrict__ plan, int C, int W,
-                                                          int VM, int tiles, float* __restrict__ out) {
-    window_clip_body<VEC, false>(ring, cap, plan, C, W, VM, tiles, 0, out);
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void bank_window_clip_kernel(const float* __restrict__ ring, int cap, const long long* __restrict__ plan, int B,
-                                                               int C, int W, int VM, int tiles, float* __restrict__ out) {
-    window_clip_body<VEC, true>(ring, cap, plan, C, W, VM, tiles, B, out);
 }
 
 // ---- scores --------------------------------------------------------------------------------------------------------------
@@ -293,53 +226,12 @@ __global__ __launch_bounds__(256) void window_vote_kernel(const float* __restric
     if (tid == 0) frame_label[f] = cover ? lab : -1;
 }
 
-// One window's update of one average, every thread its own classes k = tid, tid + 256, ...: a valid window moves the average
-// (the first one, seen0 == 0, sets it), an invalid one moves nothing.  out = the rounded average; (best, arg) = the thread's
-// first largest class for block_first_argmax.  FRESH (the bank's restart): the average reads as zeros and is stored either way.
-struct EmaBest { double best; int arg; };
-
-template <bool FRESH>
-__device__ __forceinline__ EmaBest ema_window(const float* __restrict__ probs, bool valid, long long seen0, bool fresh, int K, double beta,
-                                              double* __restrict__ ema, float* __restrict__ out) {
-    double best = 0.;
-    int arg = -1;
-    for (int k = threadIdx.x; k < K; k += 256) {
-        double e = (FRESH && fresh) ? 0. : ema[k];
-        if (valid) {
-            const double p = (double)probs[k];
-            e = seen0 == 0 ? p : beta * e + (1.0 - beta) * p;
-            ema[k] = e;
-        } else if (FRESH && fresh) {
-            ema[k] = e;
-        }
-        out[k] = (float)e;
-        if (arg < 0 || e > best) { best = e; arg = k; }
-    }
-    return {best, arg};
-}
-
-// One workgroup.  A valid window moves the average (the first one sets it) and counts in *seen; an invalid one moves nothing.
-__global__ __launch_bounds__(256) void score_ema_kernel(const float* __restrict__ probs, const long long* __restrict__ plan_row, int K, double beta,
-                                                        double* __restrict__ ema, long long* __restrict__ seen, float* __restrict__ out,
-                                                        long long* __restrict__ label, float* __restrict__ conf) {
-    __shared__ double sval[256];
-    __shared__ int sidx[256];
-    const int tid = threadIdx.x;
-    const bool valid = plan_row[1] >= 1;
-    const long long seen0 = seen[0];
-    const EmaBest m = ema_window<false>(probs, valid, seen0, false, K, beta, ema, out);
-    const int lab = block_first_argmax(m.best, m.arg, sval, sidx);     // its barriers stand between every read of *seen and the write
-    if (tid == 0) {
-        const long long now = seen0 + (valid ? 1 : 0);
-        seen[0] = now;
-        label[0] = now > 0 ? lab : -1;
-        conf[0] = now > 0 ? (float)sval[0] : 0.f;                  // out[label]: the reduction carries the value with the index
-    }
-}
-
-// One workgroup per feed: score_ema_kernel's update for the feed's B windows, oldest first, in one launch.  A thread owns the
-// same classes in every window, so the windows need no barrier between them; the arg max is taken once, of the last.  A
-// restarted feed's average reads as zeros and its seen as 0.  advanced[s] = 1 where seen moved.
+// One workgroup per feed: the feed's B windows (probs and plan rows s B + j) update its average oldest first, every thread its
+// own classes k = tid, tid + 256, ... in every window, so the windows need no barrier between them.  A valid window moves the
+// average (the feed's first one ever sets it) and counts in seen[s]; an invalid one moves nothing.  A restarted feed's average
+// reads as zeros and its seen as 0, and both are stored either way.  out = the rounded average after the last window, label its
+// first arg max (taken once), conf = out[label]; -1 and 0 before the feed's first valid window.  advanced (may be null): 1 where
+// seen moved.
 __global__ __launch_bounds__(256) void bank_ema_kernel(const float* __restrict__ probs, const long long* __restrict__ plan,
                                                        const int* __restrict__ restart, int B, int K, double beta, double* __restrict__ ema,
                                                        long long* __restrict__ seen, float* __restrict__ out, long long* __restrict__ label,
@@ -349,28 +241,39 @@ __global__ __launch_bounds__(256) void bank_ema_kernel(const float* __restrict__
     const int s = blockIdx.x, tid = threadIdx.x;
     const bool fresh0 = bank_fresh(restart, s);
     const long long seen0 = fresh0 ? 0 : seen[s];
+    double* avg = ema + (long long)s * K;
+    float* o = out + (long long)s * K;
     long long now = seen0;
-    EmaBest m = {0., -1};
+    double best = 0.;
+    int arg = -1;                                      // the thread's first largest class of the last window
     for (int j = 0; j < B; ++j) {
         const long long w = (long long)s * B + j;
-        const bool valid = plan[2 * w + 1] >= 1;
-        m = ema_window<true>(probs + w * K, valid, now, fresh0 && j == 0, K, beta, ema + (long long)s * K, out + (long long)s * K);
+        const bool valid = plan[2 * w + 1] >= 1, fresh = fresh0 && j == 0;
+        arg = -1;
+        for (int k = tid; k < K; k += 256) {
+            double e = fresh ? 0. : avg[k];
+            if (valid) {
+                const double p = (double)probs[w * K + k];
+                e = now == 0 ? p : beta * e + (1.0 - beta) * p;
+            }
+            if (valid || fresh) avg[k] = e;
+            o[k] = (float)e;
+            if (arg < 0 || e > best) { best = e; arg = k; }
+        }
         now += valid ? 1 : 0;
     }
-    const int lab = block_first_argmax(m.best, m.arg, sval, sidx); // its barriers stand between every read of seen[s] and the write
+    const int lab = block_first_argmax(best, arg, sval, sidx);     // its barriers stand between every read of seen[s] and the write
     if (tid == 0) {
         seen[s] = now;
         label[s] = now > 0 ? lab : -1;
-        conf[s] = now > 0 ? (float)sval[0] : 0.f;
-        advanced[s] = now > seen0 ? 1 : 0;
+        conf[s] = now > 0 ? (float)sval[0] : 0.f;      // out[label]: the reduction carries the value with the index
+        if (advanced) advanced[s] = now > seen0 ? 1 : 0;
     }
 }
 
 // One workgroup of 256 threads, thread t owning feeds 4 t .. 4 t + 3 (S <= 1024): the debounce update of every feed, then an
 // exclusive scan of "this feed has an event" over the feeds in ascending order gives every event its row, so the log has one
 // order and no atomics.  deb int64 (S, 3) = (stable, cand, run); count int64 [2] = (written, dropped).
-constexpr int BANK_MAX_FEEDS = 1024;
-
 __global__ __launch_bounds__(256) void bank_decide_kernel(const long long* __restrict__ label, const float* __restrict__ conf,
                                                           const int* __restrict__ advanced, const int* __restrict__ restart,
                                                           const long long* __restrict__ state, int S, float threshold, long long hold,
@@ -436,71 +339,123 @@ __global__ __launch_bounds__(256) void bank_decide_kernel(const long long* __res
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-}  // namespace
+// ---- one host body per operation: `who` is the entry point that was called; one ring is S = 1 with null counts and restart ------
+#define TG_FEEDS(who, S) TG_CHECK((S) >= 1 && (S) <= BANK_MAX_FEEDS, "%s: S = %d feeds outside 1..%d", who, S, BANK_MAX_FEEDS)
 
-extern "C" int tamgcn_ring_push(const void* frames, int n, int P, int R, int elem, void* ring, int cap, long long* state, void* stream) {
-    TG_CHECK(frames && ring && state, "tamgcn_ring_push: null pointer");
-    TG_CHECK(elem == 4 || elem == 8, "tamgcn_ring_push: elem %d (4: fp32 clip layout, 8: fp64 N-UCLA layout)", elem);
-    TG_CHECK(P > 0 && R > 0 && cap > 0, "tamgcn_ring_push: bad dims P=%d R=%d cap=%d", P, R, cap);
-    TG_CHECK(n >= 1 && n <= cap, "tamgcn_ring_push: n = %d frames outside 1..cap = %d", n, cap);
-    TG_CHECK((long long)R * elem <= (1LL << 30), "tamgcn_ring_push: a frame row of %lld bytes is too large", (long long)R * elem);
+int push(const char* who, const void* frames, int S, int n, int P, int R, int elem, void* ring, int cap, long long* state, const int* counts,
+         const int* restart, hipStream_t stream) {
+    TG_CHECK(frames && ring && state, "%s: null pointer", who);
+    TG_FEEDS(who, S);
+    TG_CHECK(elem == 4 || elem == 8, "%s: elem %d (4: fp32 clip layout, 8: fp64 N-UCLA layout)", who, elem);
+    TG_CHECK(P > 0 && R > 0 && cap > 0, "%s: bad dims P=%d R=%d cap=%d", who, P, R, cap);
+    TG_CHECK(n >= 1 && n <= cap, "%s: n = %d frames outside 1..cap = %d", who, n, cap);
+    TG_CHECK((long long)R * elem <= (1LL << 30), "%s: a frame row of %lld bytes is too large", who, (long long)R * elem);
     const long long rowbytes = (long long)R * elem;
-    const bool vec = rowbytes % 16 == 0 && aligned16(frames) && aligned16(ring);
-    const int units = (int)(vec ? rowbytes / 16 : R);
-    const long long total = (long long)P * n * units;
-    TG_CHECK((long long)P * cap * units < (1LL << 40) && total < (1LL << 31) * 256, "tamgcn_ring_push: ring too large (P=%d cap=%d R=%d)", P, cap, R);
-    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (vec) hipLaunchKernelGGL(ring_push_kernel<uint4>, grid, block, 0, (hipStream_t)stream, (const uint4*)frames, n, units, total, (uint4*)ring, cap, state);
-    else if (elem == 8) hipLaunchKernelGGL(ring_push_kernel<unsigned long long>, grid, block, 0, (hipStream_t)stream, (const unsigned long long*)frames, n, units, total, (unsigned long long*)ring, cap, state);
-    else hipLaunchKernelGGL(ring_push_kernel<unsigned>, grid, block, 0, (hipStream_t)stream, (const unsigned*)frames, n, units, total, (unsigned*)ring, cap, state);
-    tamgcn_note_kernel("ring_push_kernel<%d>", vec ? 16 : elem);
-    TG_LAUNCH_CHECK("tamgcn_ring_push");
-    hipLaunchKernelGGL(ring_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, n);
-    TG_LAUNCH_CHECK("tamgcn_ring_push (advance)");
+    const bool vec = rowbytes % 16 == 0 && aligned16(frames) && aligned16(ring);       // the feed strides P n rowbytes and P cap rowbytes
+    const int units = (int)(vec ? rowbytes / 16 : R);                                  // are multiples of 16 with the rows
+    const long long total = (long long)P * n * units, ring_units = (long long)P * cap * units;
+    TG_CHECK(ring_units * S < (1LL << 40) && total < (1LL << 31) * 256, "%s: bank too large (S=%d P=%d cap=%d R=%d)", who, S, P, cap, R);
+    const dim3 grid((unsigned)((total + 255) / 256), (unsigned)S), block(256);
+    if (vec) hipLaunchKernelGGL(bank_push_kernel<uint4>, grid, block, 0, stream, (const uint4*)frames, n, units, total, (uint4*)ring, cap, ring_units, state, counts, restart);
+    else if (elem == 8) hipLaunchKernelGGL(bank_push_kernel<unsigned long long>, grid, block, 0, stream, (const unsigned long long*)frames, n, units, total, (unsigned long long*)ring, cap, ring_units, state, counts, restart);
+    else hipLaunchKernelGGL(bank_push_kernel<unsigned>, grid, block, 0, stream, (const unsigned*)frames, n, units, total, (unsigned*)ring, cap, ring_units, state, counts, restart);
+    tamgcn_note_kernel("bank_push_kernel<%d>", vec ? 16 : elem);
+    TG_LAUNCH_CHECK(who);
+    hipLaunchKernelGGL(bank_advance_kernel, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, stream, state, S, n, counts, restart);
+    TG_LAUNCH_CHECK(who);
     return 0;
 }
 
-extern "C" int tamgcn_ring_plan(const long long* state, int cap, int B, int L, int hop, long long* plan, void* stream) {
-    TG_CHECK(state && plan, "tamgcn_ring_plan: null pointer");
-    TG_CHECK(cap > 0 && B > 0 && hop >= 1, "tamgcn_ring_plan: bad dims cap=%d B=%d hop=%d", cap, B, hop);
-    TG_CHECK(L >= 1 && L <= cap, "tamgcn_ring_plan: window L = %d outside 1..cap = %d", L, cap);
-    hipLaunchKernelGGL(ring_plan_kernel, dim3((unsigned)ceil_div(B, 64)), dim3(64), 0, (hipStream_t)stream, state, cap, B, L, hop, plan);
-    tamgcn_note_kernel("ring_plan_kernel");
-    TG_LAUNCH_CHECK("tamgcn_ring_plan");
+int plan_windows(const char* who, const long long* state, const int* counts, int S, int cap, int B, int L, int hop, long long* plan,
+                 hipStream_t stream) {
+    TG_CHECK(state && plan, "%s: null pointer", who);
+    TG_FEEDS(who, S);
+    TG_CHECK(cap > 0 && B > 0 && hop >= 1, "%s: bad dims cap=%d B=%d hop=%d", who, cap, B, hop);
+    TG_CHECK(L >= 1 && L <= cap, "%s: window L = %d outside 1..cap = %d", who, L, cap);
+    TG_CHECK((long long)S * B < (1LL << 30), "%s: S B = %lld windows", who, (long long)S * B);
+    hipLaunchKernelGGL(bank_plan_kernel, dim3((unsigned)ceil_div(S * B, 64)), dim3(64), 0, stream, state, counts, S, cap, B, L, hop, plan);
+    tamgcn_note_kernel("bank_plan_kernel");
+    TG_LAUNCH_CHECK(who);
     return 0;
+}
+
+int window_nucla(const char* who, const double* ring, int S, int cap, const long long* plan, int B, const int* parent, int V, int time_steps,
+                 int center_joint, int mode, float* out, hipStream_t stream) {
+    TG_CHECK(ring && plan && parent && out, "%s: null pointer", who);
+    TG_FEEDS(who, S);
+    TG_CHECK(cap > 0 && B > 0 && V > 0, "%s: bad dims cap=%d B=%d V=%d", who, cap, B, V);
+    TG_CHECK(time_steps > 0 && time_steps <= STREAM_MAX_TS, "%s: time_steps %d outside 1..%d", who, time_steps, STREAM_MAX_TS);
+    TG_CHECK((long long)cap * V <= (1LL << 30) && V <= (1 << 20), "%s: a ring of cap V = %lld positions is too large", who, (long long)cap * V);
+    TG_CHECK(center_joint >= 0 && center_joint < V, "%s: centre joint %d outside 0..%d", who, center_joint, V - 1);
+    TG_CHECK(mode >= 0 && mode <= 3, "%s: mode %d (0 joint, 1 bone, 2 motion, 3 bone-motion)", who, mode);
+    TG_CHECK((long long)S * B < (1LL << 30), "%s: S B = %lld windows", who, (long long)S * B);
+    hipLaunchKernelGGL(bank_window_nucla_kernel, dim3((unsigned)(S * B)), dim3(256), 0, stream, ring, cap, plan, B, parent, V, time_steps, center_joint,
+                       mode, out);
+    tamgcn_note_kernel("bank_window_nucla_kernel");
+    TG_LAUNCH_CHECK(who);
+    return 0;
+}
+
+int window_clip(const char* who, const float* ring, int S, int cap, const long long* plan, int B, int C, int V, int M, int W, float* out,
+                hipStream_t stream) {
+    TG_CHECK(ring && plan && out, "%s: null pointer", who);
+    TG_FEEDS(who, S);
+    TG_CHECK(cap > 0 && B > 0 && C > 0 && V > 0 && M > 0 && W > 0, "%s: bad dims cap=%d B=%d C=%d V=%d M=%d W=%d", who, cap, B, C, V, M, W);
+    TG_CHECK((long long)cap * V * M <= (1LL << 30) && (long long)W * V * M <= (1LL << 30),
+             "%s: a channel plane above 2^30 elements (cap=%d W=%d V=%d M=%d)", who, cap, W, V, M);
+    TG_CHECK((long long)S * B < (1LL << 30) && (long long)S * C < (1LL << 30), "%s: S B = %lld windows, S C = %lld planes", who, (long long)S * B,
+             (long long)S * C);
+    const int VM = V * M, rowlen = W * VM;
+    const bool vec = VM % 4 == 0 && aligned16(ring) && aligned16(out);      // the feed stride C cap VM is a multiple of four with VM
+    const int tiles = ceil_div(rowlen, 256 * (vec ? 4 : 1));
+    const long long blocks = (long long)S * B * C * tiles;
+    TG_CHECK(blocks < (1LL << 31), "%s: %lld workgroups", who, blocks);
+    const dim3 grid((unsigned)blocks), block(256);
+    if (vec) hipLaunchKernelGGL(bank_window_clip_kernel<4>, grid, block, 0, stream, ring, cap, plan, B, C, W, VM, tiles, out);
+    else hipLaunchKernelGGL(bank_window_clip_kernel<1>, grid, block, 0, stream, ring, cap, plan, B, C, W, VM, tiles, out);
+    tamgcn_note_kernel("bank_window_clip_kernel<%d>", vec ? 4 : 1);
+    TG_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// advanced may be null (tamgcn_score_ema has no such output)
+int score_ema(const char* who, const float* probs, const long long* plan, const int* restart, int S, int B, int K, double beta, double* ema,
+              long long* seen, float* out, long long* label, float* conf, int* advanced, hipStream_t stream) {
+    TG_CHECK(probs && plan && ema && seen && out && label && conf, "%s: null pointer", who);
+    TG_FEEDS(who, S);
+    TG_CHECK(B > 0 && (long long)S * B < (1LL << 30), "%s: B = %d windows per feed", who, B);
+    TG_CHECK(K > 0 && K <= STREAM_MAX_K, "%s: K = %d outside 1..%d", who, K, STREAM_MAX_K);
+    TG_CHECK(beta >= 0.0 && beta < 1.0, "%s: beta = %g outside [0, 1)", who, beta);   // NaN fails too
+    hipLaunchKernelGGL(bank_ema_kernel, dim3((unsigned)S), dim3(256), 0, stream, probs, plan, restart, B, K, beta, ema, seen, out, label, conf,
+                       advanced);
+    tamgcn_note_kernel("bank_ema_kernel");
+    TG_LAUNCH_CHECK(who);
+    return 0;
+}
+
+}  // namespace
+
+// ---- one ring: the bank's bodies at S = 1, every frame taken, no restart ---------------------------------------------------------
+extern "C" int tamgcn_ring_push(const void* frames, int n, int P, int R, int elem, void* ring, int cap, long long* state, void* stream) {
+    return push("tamgcn_ring_push", frames, 1, n, P, R, elem, ring, cap, state, nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int tamgcn_ring_plan(const long long* state, int cap, int B, int L, int hop, long long* plan, void* stream) {
+    return plan_windows("tamgcn_ring_plan", state, nullptr, 1, cap, B, L, hop, plan, (hipStream_t)stream);
 }
 
 extern "C" int tamgcn_window_nucla(const double* ring, int cap, const long long* plan, int B, const int* parent, int V, int time_steps,
                                    int center_joint, int mode, float* out, void* stream) {
-    TG_CHECK(ring && plan && parent && out, "tamgcn_window_nucla: null pointer");
-    TG_CHECK(cap > 0 && B > 0 && V > 0, "tamgcn_window_nucla: bad dims cap=%d B=%d V=%d", cap, B, V);
-    TG_CHECK(time_steps > 0 && time_steps <= STREAM_MAX_TS, "tamgcn_window_nucla: time_steps %d outside 1..%d", time_steps, STREAM_MAX_TS);
-    TG_CHECK((long long)cap * V <= (1LL << 30) && V <= (1 << 20), "tamgcn_window_nucla: a ring of cap V = %lld positions is too large", (long long)cap * V);
-    TG_CHECK(center_joint >= 0 && center_joint < V, "tamgcn_window_nucla: centre joint %d outside 0..%d", center_joint, V - 1);
-    TG_CHECK(mode >= 0 && mode <= 3, "tamgcn_window_nucla: mode %d (0 joint, 1 bone, 2 motion, 3 bone-motion)", mode);
-    hipLaunchKernelGGL(window_nucla_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, ring, cap, plan, parent, V, time_steps, center_joint,
-                       mode, out);
-    tamgcn_note_kernel("window_nucla_kernel");
-    TG_LAUNCH_CHECK("tamgcn_window_nucla");
-    return 0;
+    return window_nucla("tamgcn_window_nucla", ring, 1, cap, plan, B, parent, V, time_steps, center_joint, mode, out, (hipStream_t)stream);
 }
 
 extern "C" int tamgcn_window_clip(const float* ring, int cap, const long long* plan, int B, int C, int V, int M, int W, float* out, void* stream) {
-    TG_CHECK(ring && plan && out, "tamgcn_window_clip: null pointer");
-    TG_CHECK(cap > 0 && B > 0 && C > 0 && V > 0 && M > 0 && W > 0, "tamgcn_window_clip: bad dims cap=%d B=%d C=%d V=%d M=%d W=%d", cap, B, C, V, M, W);
-    TG_CHECK((long long)cap * V * M <= (1LL << 30) && (long long)W * V * M <= (1LL << 30),
-             "tamgcn_window_clip: a channel plane above 2^30 elements (cap=%d W=%d V=%d M=%d)", cap, W, V, M);
-    const int VM = V * M, rowlen = W * VM;
-    const bool vec = VM % 4 == 0 && aligned16(ring) && aligned16(out);
-    const int tiles = ceil_div(rowlen, 256 * (vec ? 4 : 1));
-    const long long blocks = (long long)B * C * tiles;
-    TG_CHECK(blocks < (1LL << 31), "tamgcn_window_clip: %lld workgroups", blocks);
-    const dim3 grid((unsigned)blocks), block(256);
-    if (vec) hipLaunchKernelGGL(window_clip_kernel<4>, grid, block, 0, (hipStream_t)stream, ring, cap, plan, C, W, VM, tiles, out);
-    else hipLaunchKernelGGL(window_clip_kernel<1>, grid, block, 0, (hipStream_t)stream, ring, cap, plan, C, W, VM, tiles, out);
-    tamgcn_note_kernel("window_clip_kernel<%d>", vec ? 4 : 1);
-    TG_LAUNCH_CHECK("tamgcn_window_clip");
-    return 0;
+    return window_clip("tamgcn_window_clip", ring, 1, cap, plan, B, C, V, M, W, out, (hipStream_t)stream);
+}
+
+extern "C" int tamgcn_score_ema(const float* probs, const long long* plan_row, int K, double beta, double* ema, long long* seen, float* out,
+                                long long* label, float* conf, void* stream) {
+    return score_ema("tamgcn_score_ema", probs, plan_row, nullptr, 1, 1, K, beta, ema, seen, out, label, conf, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int tamgcn_window_vote(const float* logits, const long long* plan, int B, int K, int n_frames, float* probs, float* frame_scores,
@@ -521,107 +476,30 @@ extern "C" int tamgcn_window_vote(const float* logits, const long long* plan, in
     return 0;
 }
 
-extern "C" int tamgcn_score_ema(const float* probs, const long long* plan_row, int K, double beta, double* ema, long long* seen, float* out,
-                                long long* label, float* conf, void* stream) {
-    TG_CHECK(probs && plan_row && ema && seen && out && label && conf, "tamgcn_score_ema: null pointer");
-    TG_CHECK(K > 0 && K <= STREAM_MAX_K, "tamgcn_score_ema: K = %d outside 1..%d", K, STREAM_MAX_K);
-    TG_CHECK(beta >= 0.0 && beta < 1.0, "tamgcn_score_ema: beta = %g outside [0, 1)", beta);   // NaN fails too
-    hipLaunchKernelGGL(score_ema_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, probs, plan_row, K, beta, ema, seen, out, label, conf);
-    tamgcn_note_kernel("score_ema_kernel");
-    TG_LAUNCH_CHECK("tamgcn_score_ema");
-    return 0;
-}
-
 // ---- the bank ------------------------------------------------------------------------------------------------------------------
 extern "C" int tamgcn_bank_push(const void* frames, int S, int n, int P, int R, int elem, void* ring, int cap, long long* state, const int* counts,
                                 const int* restart, void* stream) {
-    TG_CHECK(frames && ring && state, "tamgcn_bank_push: null pointer");
-    TG_CHECK(S >= 1 && S <= BANK_MAX_FEEDS, "tamgcn_bank_push: S = %d feeds outside 1..%d", S, BANK_MAX_FEEDS);
-    TG_CHECK(elem == 4 || elem == 8, "tamgcn_bank_push: elem %d (4: fp32 clip layout, 8: fp64 N-UCLA layout)", elem);
-    TG_CHECK(P > 0 && R > 0 && cap > 0, "tamgcn_bank_push: bad dims P=%d R=%d cap=%d", P, R, cap);
-    TG_CHECK(n >= 1 && n <= cap, "tamgcn_bank_push: n = %d frames outside 1..cap = %d", n, cap);
-    TG_CHECK((long long)R * elem <= (1LL << 30), "tamgcn_bank_push: a frame row of %lld bytes is too large", (long long)R * elem);
-    const long long rowbytes = (long long)R * elem;
-    // the feed strides P n rowbytes and P cap rowbytes are multiples of 16 with the rows
-    const bool vec = rowbytes % 16 == 0 && aligned16(frames) && aligned16(ring) && ((long long)P * n * rowbytes) % 16 == 0 &&
-                     ((long long)P * cap * rowbytes) % 16 == 0;
-    const int units = (int)(vec ? rowbytes / 16 : R);
-    const long long total = (long long)P * n * units, ring_units = (long long)P * cap * units;
-    TG_CHECK(ring_units * S < (1LL << 40) && total < (1LL << 31) * 256, "tamgcn_bank_push: bank too large (S=%d P=%d cap=%d R=%d)", S, P, cap, R);
-    const dim3 grid((unsigned)((total + 255) / 256), (unsigned)S), block(256);
-    if (vec) hipLaunchKernelGGL(bank_push_kernel<uint4>, grid, block, 0, (hipStream_t)stream, (const uint4*)frames, n, units, total, (uint4*)ring, cap, ring_units, state, counts, restart);
-    else if (elem == 8) hipLaunchKernelGGL(bank_push_kernel<unsigned long long>, grid, block, 0, (hipStream_t)stream, (const unsigned long long*)frames, n, units, total, (unsigned long long*)ring, cap, ring_units, state, counts, restart);
-    else hipLaunchKernelGGL(bank_push_kernel<unsigned>, grid, block, 0, (hipStream_t)stream, (const unsigned*)frames, n, units, total, (unsigned*)ring, cap, ring_units, state, counts, restart);
-    tamgcn_note_kernel("bank_push_kernel<%d>", vec ? 16 : elem);
-    TG_LAUNCH_CHECK("tamgcn_bank_push");
-    hipLaunchKernelGGL(bank_advance_kernel, dim3((unsigned)ceil_div(S, 256)), dim3(256), 0, (hipStream_t)stream, state, S, n, counts, restart);
-    TG_LAUNCH_CHECK("tamgcn_bank_push (advance)");
-    return 0;
+    return push("tamgcn_bank_push", frames, S, n, P, R, elem, ring, cap, state, counts, restart, (hipStream_t)stream);
 }
 
 extern "C" int tamgcn_bank_plan(const long long* state, const int* counts, int S, int cap, int B, int L, int hop, long long* plan, void* stream) {
-    TG_CHECK(state && plan, "tamgcn_bank_plan: null pointer");
-    TG_CHECK(S >= 1 && S <= BANK_MAX_FEEDS, "tamgcn_bank_plan: S = %d feeds outside 1..%d", S, BANK_MAX_FEEDS);
-    TG_CHECK(cap > 0 && B > 0 && hop >= 1, "tamgcn_bank_plan: bad dims cap=%d B=%d hop=%d", cap, B, hop);
-    TG_CHECK(L >= 1 && L <= cap, "tamgcn_bank_plan: window L = %d outside 1..cap = %d", L, cap);
-    TG_CHECK((long long)S * B < (1LL << 30), "tamgcn_bank_plan: S B = %lld windows", (long long)S * B);
-    hipLaunchKernelGGL(bank_plan_kernel, dim3((unsigned)ceil_div(S * B, 64)), dim3(64), 0, (hipStream_t)stream, state, counts, S, cap, B, L, hop, plan);
-    tamgcn_note_kernel("bank_plan_kernel");
-    TG_LAUNCH_CHECK("tamgcn_bank_plan");
-    return 0;
+    return plan_windows("tamgcn_bank_plan", state, counts, S, cap, B, L, hop, plan, (hipStream_t)stream);
 }
 
 extern "C" int tamgcn_bank_window_nucla(const double* ring, int S, int cap, const long long* plan, int B, const int* parent, int V, int time_steps,
                                         int center_joint, int mode, float* out, void* stream) {
-    TG_CHECK(ring && plan && parent && out, "tamgcn_bank_window_nucla: null pointer");
-    TG_CHECK(S >= 1 && S <= BANK_MAX_FEEDS, "tamgcn_bank_window_nucla: S = %d feeds outside 1..%d", S, BANK_MAX_FEEDS);
-    TG_CHECK(cap > 0 && B > 0 && V > 0, "tamgcn_bank_window_nucla: bad dims cap=%d B=%d V=%d", cap, B, V);
-    TG_CHECK(time_steps > 0 && time_steps <= STREAM_MAX_TS, "tamgcn_bank_window_nucla: time_steps %d outside 1..%d", time_steps, STREAM_MAX_TS);
-    TG_CHECK((long long)cap * V <= (1LL << 30) && V <= (1 << 20), "tamgcn_bank_window_nucla: a ring of cap V = %lld positions is too large", (long long)cap * V);
-    TG_CHECK(center_joint >= 0 && center_joint < V, "tamgcn_bank_window_nucla: centre joint %d outside 0..%d", center_joint, V - 1);
-    TG_CHECK(mode >= 0 && mode <= 3, "tamgcn_bank_window_nucla: mode %d (0 joint, 1 bone, 2 motion, 3 bone-motion)", mode);
-    TG_CHECK((long long)S * B < (1LL << 30), "tamgcn_bank_window_nucla: S B = %lld windows", (long long)S * B);
-    hipLaunchKernelGGL(bank_window_nucla_kernel, dim3((unsigned)(S * B)), dim3(256), 0, (hipStream_t)stream, ring, cap, plan, B, parent, V, time_steps,
-                       center_joint, mode, out);
-    tamgcn_note_kernel("bank_window_nucla_kernel");
-    TG_LAUNCH_CHECK("tamgcn_bank_window_nucla");
-    return 0;
+    return window_nucla("tamgcn_bank_window_nucla", ring, S, cap, plan, B, parent, V, time_steps, center_joint, mode, out, (hipStream_t)stream);
 }
 
 extern "C" int tamgcn_bank_window_clip(const float* ring, int S, int cap, const long long* plan, int B, int C, int V, int M, int W, float* out,
                                        void* stream) {
-    TG_CHECK(ring && plan && out, "tamgcn_bank_window_clip: null pointer");
-    TG_CHECK(S >= 1 && S <= BANK_MAX_FEEDS, "tamgcn_bank_window_clip: S = %d feeds outside 1..%d", S, BANK_MAX_FEEDS);
-    TG_CHECK(cap > 0 && B > 0 && C > 0 && V > 0 && M > 0 && W > 0, "tamgcn_bank_window_clip: bad dims cap=%d B=%d C=%d V=%d M=%d W=%d", cap, B, C, V, M, W);
-    TG_CHECK((long long)cap * V * M <= (1LL << 30) && (long long)W * V * M <= (1LL << 30),
-             "tamgcn_bank_window_clip: a channel plane above 2^30 elements (cap=%d W=%d V=%d M=%d)", cap, W, V, M);
-    TG_CHECK((long long)S * B < (1LL << 30) && (long long)S * C < (1LL << 30), "tamgcn_bank_window_clip: S B = %lld windows, S C = %lld planes",
-             (long long)S * B, (long long)S * C);
-    const int VM = V * M, rowlen = W * VM;
-    const bool vec = VM % 4 == 0 && aligned16(ring) && aligned16(out);      // the feed stride C cap VM is a multiple of four with VM
-    const int tiles = ceil_div(rowlen, 256 * (vec ? 4 : 1));
-    const long long blocks = (long long)S * B * C * tiles;
-    TG_CHECK(blocks < (1LL << 31), "tamgcn_bank_window_clip: %lld workgroups", blocks);
-    const dim3 grid((unsigned)blocks), block(256);
-    if (vec) hipLaunchKernelGGL(bank_window_clip_kernel<4>, grid, block, 0, (hipStream_t)stream, ring, cap, plan, B, C, W, VM, tiles, out);
-    else hipLaunchKernelGGL(bank_window_clip_kernel<1>, grid, block, 0, (hipStream_t)stream, ring, cap, plan, B, C, W, VM, tiles, out);
-    tamgcn_note_kernel("bank_window_clip_kernel<%d>", vec ? 4 : 1);
-    TG_LAUNCH_CHECK("tamgcn_bank_window_clip");
-    return 0;
+    return window_clip("tamgcn_bank_window_clip", ring, S, cap, plan, B, C, V, M, W, out, (hipStream_t)stream);
 }
 
 extern "C" int tamgcn_bank_ema(const float* probs, const long long* plan, const int* restart, int S, int B, int K, double beta, double* ema,
                                long long* seen, float* out, long long* label, float* conf, int* advanced, void* stream) {
-    TG_CHECK(probs && plan && ema && seen && out && label && conf && advanced, "tamgcn_bank_ema: null pointer");
-    TG_CHECK(S >= 1 && S <= BANK_MAX_FEEDS, "tamgcn_bank_ema: S = %d feeds outside 1..%d", S, BANK_MAX_FEEDS);
-    TG_CHECK(B > 0 && (long long)S * B < (1LL << 30), "tamgcn_bank_ema: B = %d windows per feed", B);
-    TG_CHECK(K > 0 && K <= STREAM_MAX_K, "tamgcn_bank_ema: K = %d outside 1..%d", K, STREAM_MAX_K);
-    TG_CHECK(beta >= 0.0 && beta < 1.0, "tamgcn_bank_ema: beta = %g outside [0, 1)", beta);   // NaN fails too
-    hipLaunchKernelGGL(bank_ema_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, probs, plan, restart, B, K, beta, ema, seen, out, label,
-                       conf, advanced);
-    tamgcn_note_kernel("bank_ema_kernel");
-    TG_LAUNCH_CHECK("tamgcn_bank_ema");
-    return 0;
+    TG_CHECK(advanced, "tamgcn_bank_ema: null pointer");
+    return score_ema("tamgcn_bank_ema", probs, plan, restart, S, B, K, beta, ema, seen, out, label, conf, advanced, (hipStream_t)stream);
 }
 
 extern "C" int tamgcn_bank_decide(const long long* label, const float* conf, const int* advanced, const int* restart, const long long* state, int S,

@@ -1264,41 +1264,22 @@ def clip_resize(raw, clip_ids, crop, W, rot=None):
     return out
 
 
-# live and sliding-window inference (csrc/streaming.hip; include/tamgcn.h has the ring, the plan and every rule)
+# live and sliding-window inference (csrc/streaming.hip; include/tamgcn.h has the rings, the plan and every rule): a bank of S
+# rings for S live feeds, feed s a ring of its own at s * (P cap R); counts / restart int32 [S] | None.  One ring is a bank of one feed.
 STREAM_MAX_TS = 64            # time_steps of window_nucla
 STREAM_MAX_K = 4096           # classes of window_vote / score_ema
+BANK_MAX_FEEDS = 1024
 
 
-def _ring_geometry(ring, what):
-    """(P, cap, R, elem) of a ring tensor: fp64 (cap, V, 3) or fp32 (C, cap, V, M)."""
-    if isinstance(ring, torch.Tensor) and ring.dtype == torch.float64 and ring.dim() == 3 and ring.shape[2] == 3 and ring.numel():
-        return 1, ring.shape[0], ring.shape[1] * 3, 8
-    if isinstance(ring, torch.Tensor) and ring.dtype == torch.float32 and ring.dim() == 4 and ring.numel():
-        return ring.shape[0], ring.shape[1], ring.shape[2] * ring.shape[3], 4
-    raise RuntimeError(f'tam_gcn_amd: {what} takes a non-empty fp64 (cap, V, 3) or fp32 (C, cap, V, M) ring, got '
-                       f'{getattr(ring, "dtype", type(ring))} {tuple(getattr(ring, "shape", ()))}')
-
-
-def ring_push(frames, ring, state):
-    """frames fp64 (n, V, 3) into ring fp64 (cap, V, 3), or fp32 (C, n, V, M) into fp32 (C, cap, V, M): slots (count + i) % cap;
-    state int64 [2] = (count, pushes), read and advanced on the device.  1 <= n <= cap.  No host sync, capturable."""
-    P, cap, R, elem = _ring_geometry(ring, 'ring_push')
-    _want(ring, 'ring', ring.dtype)
-    _want(state, 'state', torch.int64, (2,))
-    t = 0 if elem == 8 else 1                       # the time axis
-    if not isinstance(frames, torch.Tensor) or frames.dim() != ring.dim() or frames.shape[:t] + frames.shape[t + 1:] != ring.shape[:t] + ring.shape[t + 1:]:
-        raise RuntimeError(f'tam_gcn_amd: ring_push: frames {tuple(getattr(frames, "shape", ()))} do not fit the ring {tuple(ring.shape)}')
-    _want(frames, 'frames', ring.dtype)
-    _lib.check(_lib_().tamgcn_ring_push(_ptr(frames), frames.shape[t], P, R, elem, _ptr(ring), cap, _ptr(state), _stream()), 'tamgcn_ring_push')
-
-
-def ring_plan(state, cap, B, L, hop):
-    """-> plan int64 (B, 2) = (start, L): window j ends (B - 1 - j) hop frames before the newest frame of the ring whose state
-    is `state`; (0, 0) where the window starts before frame 0 or is overwritten.  No host sync, capturable."""
-    _want(state, 'state', torch.int64, (2,))
-    plan = torch.empty(B, 2, device=state.device, dtype=torch.int64)
-    _lib.check(_lib_().tamgcn_ring_plan(_ptr(state), cap, B, L, hop, _ptr(plan), _stream()), 'tamgcn_ring_plan')
-    return plan
+def _bank_geometry(bank, what):
+    """(S, P, cap, R, elem) of a bank tensor: fp64 (S, cap, V, 3) or fp32 (S, C, cap, V, M)."""
+    if isinstance(bank, torch.Tensor) and bank.numel():
+        if bank.dtype == torch.float64 and bank.dim() == 4 and bank.shape[3] == 3:
+            return bank.shape[0], 1, bank.shape[1], bank.shape[2] * 3, 8
+        if bank.dtype == torch.float32 and bank.dim() == 5:
+            return bank.shape[0], bank.shape[1], bank.shape[2], bank.shape[3] * bank.shape[4], 4
+    raise RuntimeError(f'tam_gcn_amd: {what} takes a non-empty fp64 (S, cap, V, 3) or fp32 (S, C, cap, V, M) bank, got '
+                       f'{getattr(bank, "dtype", type(bank))} {tuple(getattr(bank, "shape", ()))}')
 
 
 def _want_plan(plan):
@@ -1306,35 +1287,6 @@ def _want_plan(plan):
     if plan.dim() != 2 or plan.shape[1] != 2 or plan.shape[0] < 1:
         raise RuntimeError(f'tam_gcn_amd: plan is {tuple(plan.shape)}, expected (B, 2)')
     return plan.shape[0]
-
-
-def window_nucla(ring, plan, parent, time_steps, center_joint, mode):
-    """ring fp64 (cap, V, 3), plan int64 (B, 2), parent int32 [V] -> (B, 3, time_steps, V, 1) fp32: feeder_transform's val path
-    on every window (identity view, np.linspace indices), zeros for an invalid one."""
-    _want(ring, 'ring', torch.float64)
-    if ring.dim() != 3 or ring.shape[2] != 3 or ring.numel() == 0:
-        raise RuntimeError(f'tam_gcn_amd: window_nucla takes a non-empty (cap, V, 3) ring, got {tuple(ring.shape)}')
-    cap, V = ring.shape[0], ring.shape[1]
-    B = _want_plan(plan)
-    _want(parent, 'parent', torch.int32, (V,))
-    m = STREAM_MODES[mode] if isinstance(mode, str) else int(mode)
-    out = torch.empty(B, 3, time_steps, V, 1, device=ring.device, dtype=torch.float32)
-    _lib.check(_lib_().tamgcn_window_nucla(_ptr(ring), cap, _ptr(plan), B, _ptr(parent), V, time_steps, center_joint, m, _ptr(out), _stream()),
-               'tamgcn_window_nucla')
-    return out
-
-
-def window_clip(ring, plan, W):
-    """ring fp32 (C, cap, V, M), plan int64 (B, 2) -> (B, C, W, V, M) fp32: clip_resize's linear time-resize of every window
-    (no rotation), zeros for an invalid one."""
-    _want(ring, 'ring', torch.float32)
-    if ring.dim() != 4 or ring.numel() == 0:
-        raise RuntimeError(f'tam_gcn_amd: window_clip takes a non-empty (C, cap, V, M) ring, got {tuple(ring.shape)}')
-    C_, cap, V, M = ring.shape
-    B = _want_plan(plan)
-    out = torch.empty(B, C_, W, V, M, device=ring.device, dtype=torch.float32)
-    _lib.check(_lib_().tamgcn_window_clip(_ptr(ring), cap, _ptr(plan), B, C_, V, M, W, _ptr(out), _stream()), 'tamgcn_window_clip')
-    return out
 
 
 def window_vote(logits, plan, n_frames=None):
@@ -1354,39 +1306,6 @@ def window_vote(logits, plan, n_frames=None):
     _lib.check(_lib_().tamgcn_window_vote(_ptr(logits), _ptr(plan), B, K, n_frames or 0, _ptr(probs), _ptr(fs), _ptr(fl), _stream()),
                'tamgcn_window_vote')
     return probs, fs, fl
-
-
-def score_ema(probs, plan_row, beta, ema, seen):
-    """probs fp32 [K], plan_row int64 [2], ema fp64 [K] and seen int64 [1] updated in place on the device (an invalid window moves
-    nothing) -> out fp32 [K] = the average, label int64 [1] (-1 before the first valid window), conf fp32 [1]."""
-    _want(probs, 'probs', torch.float32)
-    K = probs.numel()
-    _want(plan_row, 'plan_row', torch.int64, (2,))
-    _want(ema, 'ema', torch.float64, (K,))
-    _want(seen, 'seen', torch.int64, (1,))
-    if probs.dim() != 1:
-        raise RuntimeError(f'tam_gcn_amd: score_ema takes one row of probabilities, got {tuple(probs.shape)}')
-    out = torch.empty(K, device=probs.device, dtype=torch.float32)
-    label = torch.empty(1, device=probs.device, dtype=torch.int64)
-    conf = torch.empty(1, device=probs.device, dtype=torch.float32)
-    _lib.check(_lib_().tamgcn_score_ema(_ptr(probs), _ptr(plan_row), K, float(beta), _ptr(ema), _ptr(seen), _ptr(out), _ptr(label), _ptr(conf),
-                                        _stream()), 'tamgcn_score_ema')
-    return out, label, conf
-
-
-# a bank of S rings for S live feeds (include/tamgcn.h: feed s is a ring of its own at s * (P cap R); counts / restart int32 [S] | None)
-BANK_MAX_FEEDS = 1024
-
-
-def _bank_geometry(bank, what):
-    """(S, P, cap, R, elem) of a bank tensor: fp64 (S, cap, V, 3) or fp32 (S, C, cap, V, M)."""
-    if isinstance(bank, torch.Tensor) and bank.dim() >= 2 and bank.shape[0] >= 1:
-        try:
-            return (bank.shape[0],) + _ring_geometry(bank[0], what)
-        except RuntimeError:
-            pass
-    raise RuntimeError(f'tam_gcn_amd: {what} takes a non-empty fp64 (S, cap, V, 3) or fp32 (S, C, cap, V, M) bank, got '
-                       f'{getattr(bank, "dtype", type(bank))} {tuple(getattr(bank, "shape", ()))}')
 
 
 def _want_feeds(S, what, counts=None, restart=None):
@@ -1499,6 +1418,43 @@ def bank_ema(probs, plan, beta, ema, seen, restart=None):
     _lib.check(_lib_().tamgcn_bank_ema(_ptr(probs), _ptr(plan), _ptr(restart), S, B, K, float(beta), _ptr(ema), _ptr(seen), _ptr(out), _ptr(label),
                                        _ptr(conf), _ptr(advanced), _stream()), 'tamgcn_bank_ema')
     return out, label, conf, advanced
+
+
+# one ring: the bank's ops on views with a leading feed axis of one (RingBank.feed(s) gives such rings)
+def _one_feed(t):
+    """A ring's tensor as the one-feed bank's (a view); what is no tensor goes on to the bank op's refusal."""
+    return t[None] if isinstance(t, torch.Tensor) else t
+
+
+def ring_push(frames, ring, state):
+    """frames fp64 (n, V, 3) into ring fp64 (cap, V, 3), or fp32 (C, n, V, M) into fp32 (C, cap, V, M): slots (count + i) % cap;
+    state int64 [2] = (count, pushes), read and advanced on the device.  1 <= n <= cap.  No host sync, capturable."""
+    bank_push(_one_feed(frames), _one_feed(ring), _one_feed(state))
+
+
+def ring_plan(state, cap, B, L, hop):
+    """-> plan int64 (B, 2) = (start, L): window j ends (B - 1 - j) hop frames before the newest frame of the ring whose state
+    is `state`; (0, 0) where the window starts before frame 0 or is overwritten.  No host sync, capturable."""
+    return bank_plan(_one_feed(state), cap, B, L, hop)
+
+
+def window_nucla(ring, plan, parent, time_steps, center_joint, mode):
+    """ring fp64 (cap, V, 3), plan int64 (B, 2), parent int32 [V] -> (B, 3, time_steps, V, 1) fp32: feeder_transform's val path
+    on every window (identity view, np.linspace indices), zeros for an invalid one."""
+    return bank_window_nucla(_one_feed(ring), plan, _want_plan(plan), parent, time_steps, center_joint, mode)
+
+
+def window_clip(ring, plan, W):
+    """ring fp32 (C, cap, V, M), plan int64 (B, 2) -> (B, C, W, V, M) fp32: clip_resize's linear time-resize of every window
+    (no rotation), zeros for an invalid one."""
+    return bank_window_clip(_one_feed(ring), plan, _want_plan(plan), W)
+
+
+def score_ema(probs, plan_row, beta, ema, seen):
+    """probs fp32 [K], plan_row int64 [2], ema fp64 [K] and seen int64 [1] updated in place on the device (an invalid window moves
+    nothing) -> out fp32 [K] = the average, label int64 [1] (-1 before the first valid window), conf fp32 [1]."""
+    out, label, conf, _ = bank_ema(_one_feed(probs), _one_feed(plan_row), beta, _one_feed(ema), seen)
+    return out[0], label, conf
 
 
 def bank_decide(label, conf, advanced, state, threshold, hold, deb, log_rows, log_conf, log_count, restart=None):

@@ -64,52 +64,9 @@ def _device(device, who):
     return dev
 
 
-class FrameRing:
-    """capacity frames in HBM; frame f (counted from 0, the first frame ever pushed) lives in slot f % capacity.
-
-    prep='nucla': buf fp64 (capacity, V, 3), push((n, V, 3)) in any float dtype (cast to fp64 on the device).
-    prep='clip':  buf fp32 (C, capacity, V, M), push((C, n, V, M)) fp32.
-    push() makes no host synchronisation and is capturable; 1 <= n <= capacity.  state int64 [2] = (frames, pushes) lives on
-    the device; `count` reads it (a synchronisation).  reset() forgets every frame."""
-
-    def __init__(self, capacity, prep='nucla', V=None, C=3, M=1, device='cuda'):
-        who = 'FrameRing'
-        self.capacity = _int('capacity', capacity, 1, who)
-        if prep not in PREPS:
-            raise ValueError(f'{who}: prep {prep!r} (one of {PREPS})')
-        self.V, self.C, self.M = _int('V', V, 1, who), _int('C', C, 1, who), _int('M', M, 1, who)
-        if prep == 'nucla' and (C != 3 or M != 1):
-            raise ValueError(f"{who}: prep='nucla' holds one person's (V, 3) joints; C = {C}, M = {M}")
-        self.prep = prep
-        dev = _device(device, who)
-        if prep == 'nucla':
-            self.buf = torch.zeros(capacity, V, 3, dtype=torch.float64, device=dev)
-        else:
-            self.buf = torch.zeros(C, capacity, V, M, dtype=torch.float32, device=dev)
-        self.state = torch.zeros(2, dtype=torch.int64, device=dev)
-
-    def frames_shape(self, n):
-        return (n, self.V, 3) if self.prep == 'nucla' else (self.C, n, self.V, self.M)
-
-    def push(self, frames):
-        if not torch.is_tensor(frames) or not frames.is_cuda:
-            raise RuntimeError('FrameRing.push: expected a HIP (cuda) tensor; there is no CPU path')
-        t = 0 if self.prep == 'nucla' else 1
-        if frames.dim() != self.buf.dim() or tuple(frames.shape) != self.frames_shape(frames.shape[t]) or not frames.is_floating_point():
-            raise ValueError(f'FrameRing.push: frames must be {self.frames_shape("n")} floats, got {tuple(frames.shape)} {frames.dtype}')
-        if not 1 <= frames.shape[t] <= self.capacity:
-            raise ValueError(f'FrameRing.push: {frames.shape[t]} frames outside 1..capacity = {self.capacity}')
-        if self.prep == 'clip' and frames.dtype != torch.float32:
-            raise ValueError(f"FrameRing.push: prep='clip' takes fp32 frames, got {frames.dtype}")
-        ops.ring_push(frames.to(self.buf.dtype).contiguous(), self.buf, self.state)
-
-    def reset(self):
-        self.buf.zero_()
-        self.state.zero_()
-
-    @property
-    def count(self):
-        return int(self.state[0])
+def _ring_frames(ring, n):
+    """The push form of n frames for one ring of a FrameRing or a RingBank."""
+    return (n, ring.V, 3) if ring.prep == 'nucla' else (ring.C, n, ring.V, ring.M)
 
 
 def _feed_flags(who, name, t, S):
@@ -123,10 +80,11 @@ def _feed_flags(who, name, t, S):
 
 
 class RingBank:
-    """S = feeds independent rings in one allocation, one per camera or tracked person: feed s is the ring FrameRing describes
-    (frame f of feed s in slot f % capacity), and feed(s) returns views (buf[s], state[s]) the single-ring ops accept.
+    """S = feeds independent rings in one allocation, one per camera or tracked person: frame f of feed s (counted from 0, the
+    first frame the feed was ever pushed) lives in slot f % capacity, and feed(s) returns views (buf[s], state[s]) the
+    single-ring ops accept.
 
-    prep='nucla': buf fp64 (S, capacity, V, 3), push((S, n, V, 3)) in any float dtype.
+    prep='nucla': buf fp64 (S, capacity, V, 3), push((S, n, V, 3)) in any float dtype (cast to fp64 on the device).
     prep='clip':  buf fp32 (S, C, capacity, V, M), push((S, C, n, V, M)) fp32.
     state int64 (S, 2) = (count, pushes) per feed lives on the device.  1 <= S <= 1024 (ops.BANK_MAX_FEEDS), 1 <= n <= capacity.
 
@@ -136,8 +94,8 @@ class RingBank:
     push: its count goes to 0 and its frames are numbered from 0 again (the buffer is not cleared: no valid window reaches
     before frame 0).  reset(feeds=None) is the host-side call for all feeds or a list of them; it clears the buffers too."""
 
-    def __init__(self, feeds, capacity, prep='nucla', V=None, C=3, M=1, device='cuda'):
-        who = 'RingBank'
+    def __init__(self, feeds, capacity, prep='nucla', V=None, C=3, M=1, device='cuda', _who='RingBank'):
+        who = _who                                                    # FrameRing: the refusals carry the front's name
         self.feeds = _int('feeds', feeds, 1, who)
         if feeds > ops.BANK_MAX_FEEDS:
             raise ValueError(f'{who}: feeds = {feeds} above {ops.BANK_MAX_FEEDS}')
@@ -149,22 +107,23 @@ class RingBank:
             raise ValueError(f"{who}: prep='nucla' holds one person's (V, 3) joints per feed; C = {C}, M = {M}")
         self.prep = prep
         dev = _device(device, who)
-        if prep == 'nucla':
-            self.buf = torch.zeros(feeds, capacity, V, 3, dtype=torch.float64, device=dev)
-        else:
-            self.buf = torch.zeros(feeds, C, capacity, V, M, dtype=torch.float32, device=dev)
+        self.buf = torch.zeros(self.frames_shape(capacity), dtype=torch.float64 if prep == 'nucla' else torch.float32, device=dev)
         self.state = torch.zeros(feeds, 2, dtype=torch.int64, device=dev)
 
     def frames_shape(self, n):
-        return (self.feeds, n, self.V, 3) if self.prep == 'nucla' else (self.feeds, self.C, n, self.V, self.M)
+        return (self.feeds,) + _ring_frames(self, n)
 
     def push(self, frames, counts=None, restart=None):
-        who = 'RingBank.push'
+        self._push('RingBank.push', (self.feeds,), frames, counts, restart)
+
+    def _push(self, who, lead, frames, counts=None, restart=None):
+        """frames in the form lead + one ring's: lead = (feeds,) for the bank's own push, () for a FrameRing's."""
         if not torch.is_tensor(frames) or not frames.is_cuda:
             raise RuntimeError(f'{who}: expected a HIP (cuda) tensor; there is no CPU path')
-        t = 1 if self.prep == 'nucla' else 2
-        if frames.dim() != self.buf.dim() or tuple(frames.shape) != self.frames_shape(frames.shape[t]) or not frames.is_floating_point():
-            raise ValueError(f'{who}: frames must be {self.frames_shape("n")} floats, got {tuple(frames.shape)} {frames.dtype}')
+        t = len(lead) + (0 if self.prep == 'nucla' else 1)
+        form = lambda n: lead + _ring_frames(self, n)                  # noqa: E731
+        if frames.dim() != len(form(0)) or tuple(frames.shape) != form(frames.shape[t]) or not frames.is_floating_point():
+            raise ValueError(f'{who}: frames must be {form("n")} floats, got {tuple(frames.shape)} {frames.dtype}')
         if not 1 <= frames.shape[t] <= self.capacity:
             raise ValueError(f'{who}: {frames.shape[t]} frames outside 1..capacity = {self.capacity}')
         if self.prep == 'clip' and frames.dtype != torch.float32:
@@ -172,7 +131,8 @@ class RingBank:
         dev = self.buf.device
         counts, restart = (None if f is None else f.to(device=dev, dtype=torch.int32).contiguous()
                            for f in (_feed_flags(who, 'counts', counts, self.feeds), _feed_flags(who, 'restart', restart, self.feeds)))
-        ops.bank_push(frames.to(self.buf.dtype).contiguous(), self.buf, self.state, counts, restart)
+        frames = frames.to(self.buf.dtype).contiguous()
+        ops.bank_push(frames.view(self.frames_shape(frames.shape[t])), self.buf, self.state, counts, restart)
 
     def reset(self, feeds=None):
         if feeds is None:
@@ -199,6 +159,34 @@ class RingBank:
     def counts(self):
         """The frames every feed has taken, as a list (a synchronisation)."""
         return self.state[:, 0].tolist()
+
+
+class FrameRing:
+    """capacity frames in HBM; frame f (counted from 0, the first frame ever pushed) lives in slot f % capacity.  A FrameRing is a
+    RingBank of one feed: buf and state are feed 0's views, and every check and launch is the bank's.
+
+    prep='nucla': buf fp64 (capacity, V, 3), push((n, V, 3)) in any float dtype (cast to fp64 on the device).
+    prep='clip':  buf fp32 (C, capacity, V, M), push((C, n, V, M)) fp32.
+    push() makes no host synchronisation and is capturable; 1 <= n <= capacity.  state int64 [2] = (frames, pushes) lives on
+    the device; `count` reads it (a synchronisation).  reset() forgets every frame."""
+
+    def __init__(self, capacity, prep='nucla', V=None, C=3, M=1, device='cuda'):
+        bank = self._bank = RingBank(1, capacity, prep, V, C, M, device, _who='FrameRing')
+        self.capacity, self.prep, self.V, self.C, self.M = bank.capacity, bank.prep, bank.V, bank.C, bank.M
+        self.buf, self.state = bank.feed(0)
+
+    def frames_shape(self, n):
+        return _ring_frames(self, n)
+
+    def push(self, frames):
+        self._bank._push('FrameRing.push', (), frames)
+
+    def reset(self):
+        self._bank.reset()
+
+    @property
+    def count(self):
+        return int(self.state[0])
 
 
 def plan_offline(length, window, hop):
@@ -276,7 +264,7 @@ class _StateWatch:
 
 
 class _Windows:
-    """What SlidingWindow and LiveClassifier share: the checked arguments and plan -> model input."""
+    """What SlidingWindow and the live chain share: the checked arguments and plan -> model input."""
 
     def __init__(self, who, model, prep, time_steps, window_size, stream, parent, V, C, M):
         if prep not in PREPS:
@@ -321,11 +309,11 @@ class _Windows:
             raise ValueError(f'parent must hold {self.V} joint indices in [0, {self.V})')
         self.parent = torch.tensor(parent, dtype=torch.int32, device=dev)
 
-    def build(self, ring, plan):
-        """ring tensor, plan int64 (B, 2) -> the model's input (B, C, T, V, M) of the configured stream."""
+    def build(self, bank, plan, B):
+        """bank tensor of S rings, plan int64 (rows >= S B, 2) -> the model's input (rows, C, T, V, M) of the configured stream."""
         if self.prep == 'nucla':
-            return ops.window_nucla(ring, plan, self.parent, self.T, NUCLA_CENTER_JOINT, self.stream)
-        return ops.stream_derive(ops.window_clip(ring, plan, self.T), self.parent, self.stream)
+            return ops.bank_window_nucla(bank, plan, B, self.parent, self.T, NUCLA_CENTER_JOINT, self.stream)
+        return ops.stream_derive(ops.bank_window_clip(bank, plan, B, self.T), self.parent, self.stream)
 
     def forward_one_stream(self, fn, x):
         """fn(x) with a StreamEnsemble that was left to choose kept on the grouped, one-stream arrangement (CapturedEval's rule)."""
@@ -407,7 +395,7 @@ class SlidingWindow:
         with torch.no_grad():
             for c in range(chunks):
                 rows_c = plan[c * bw:(c + 1) * bw]
-                out = w.forward_one_stream(self._fwd, w.build(seq, rows_c))
+                out = w.forward_one_stream(self._fwd, w.build(seq[None], rows_c, bw))     # the sequence: one ring that never wraps
                 if logits is None:
                     if out.dim() != 2 or out.shape[0] != bw:
                         raise ValueError(f'SlidingWindow: the model returned {tuple(out.shape)}, expected ({bw}, num_class)')
@@ -418,11 +406,111 @@ class SlidingWindow:
         return SlidingResult(logits, probs, scores, label, plan)
 
 
-class _LiveChain:
-    """What LiveClassifier and LiveBank share: the capture of self._chain() as one HIP graph after self._warm() ran on a side
-    stream.  The subclass has model, _dev, _who and captures."""
+BankStep = collections.namedtuple('BankStep', 'label conf smoothed logits stable')
+BankEvents = collections.namedtuple('BankEvents', 'rows conf dropped')
+
+
+class LiveBank:
+    """The live chain for S feeds at once: one graph replay pushes a tick's frames to every feed of a RingBank and classifies
+    them all.  model in eval() mode; bank: the RingBank the frames go to (its prep decides the window form); window frames per
+    window; per step and feed hop_windows windows `hop` frames apart (default hop = window), the newest last; beta in [0, 1): the
+    moving average ema = beta ema + (1 - beta) probs over a feed's valid windows in the order they are seen (0: the newest
+    window's softmax); time_steps / window_size, stream, parent as SlidingWindow's; frames_per_step (default 1): the n frames per
+    feed every step takes; eager=True runs the chain launch by launch instead of replaying a graph (the same bits).
+
+    step(frames, counts=None, restart=None) -> BankStep(label int64 [S], conf fp32 [S], smoothed fp32 (S, K), logits fp32
+    (S, hop_windows, K), stable int64 [S] | None): frames in the bank's push form with n = frames_per_step; counts, restart:
+    integer tensors [S] or None, copied like the frames into the chain's own device tensors (changing them never captures again).
+    The chain is push -> plan -> window -> stream derivation -> forward -> softmax -> average -> decision; its outputs are device
+    tensors, the graph's own, overwritten by the next step (clone to keep them).  Per feed the semantics are those of a feed
+    that was stepped only on the ticks where counts[s] > 0, with that many frames, and reset() where restart[s] was set.  A feed
+    with counts[s] == 0: no window of the tick is valid, its average and `seen` do not move, label, conf, smoothed and stable
+    repeat its state, its logits rows are unspecified.  A feed with restart[s]: average, seen and debounce state are cleared on
+    the device before the tick's push; label is -1 until its first valid window.  No synchronisation.
+
+    CapturedEval's rules: step() raises while the model is in train() mode; the model's state key (evaluation._state_key, read
+    per step through _StateWatch: see there for what a step sees at once) is compared per step and the chain is captured again
+    when it moved (`captures` counts; such a step synchronises); a StreamEnsemble stays on one stream.  invalidate() makes the
+    next step compare the whole key (after replacing a parameter object).
+
+    The S hop_windows windows go through the model in chunks of chunk_windows (default: the fewest chunks that keep the model on
+    its small-batch eval family, as in SlidingWindow, made equal in size; the last chunk padded with invalid windows), all inside
+    the one graph.  Past the family's bound one pass of all windows (chunk_windows = S hop_windows) measured faster, with the
+    general path's bits instead of the family's (profiles/stream_bank_bench.txt).
+
+    threshold (None: no decisions, stable is None): the debounced decision per feed, updated after the average for every feed
+    whose `seen` moved this tick, feeds ascending -- conf >= float32(threshold) and label == cand: run += 1; else conf >=
+    float32(threshold): cand = label, run = 1; else cand = -1, run = 0; then, when run >= hold and cand != stable: stable = cand
+    and one event (feed, frame = count - 1, label) with its conf is appended to a log of log_capacity rows on the device (a
+    full log drops the event and counts it).  events() -> BankEvents(rows int64 (n, 3), conf fp32 [n], dropped) on the host: the
+    only synchronisation.  clear_events() empties the log on the device.  reset() clears the bank, the averages, their counts,
+    the debounce state and the log.  state_dict() / load_state_dict() carry the bank's buffers and states, the averages, the
+    debounce state and the log."""
+
+    def __init__(self, model, bank, window, hop_windows=1, hop=None, beta=0.0, time_steps=None, window_size=None, stream='joint',
+                 parent=None, frames_per_step=1, eager=False, chunk_windows=None, threshold=None, hold=1, log_capacity=4096, _front=None):
+        who = self._who = _front or 'LiveBank'                        # LiveClassifier: `bank` is its FrameRing, the refusals carry its name
+        kind, noun = (FrameRing, 'ring') if _front else (RingBank, 'bank')
+        if not isinstance(bank, kind):
+            raise ValueError(f'{who}: {noun} must be a {kind.__name__}')
+        self.window, self.B = _int('window', window, 1, who), _int('hop_windows', hop_windows, 1, who)
+        self.hop = _int('hop', window if hop is None else hop, 1, who)
+        self.n = _int('frames_per_step', frames_per_step, 1, who)
+        if not (isinstance(beta, (int, float)) and not isinstance(beta, bool) and 0.0 <= beta < 1.0):
+            raise ValueError(f'{who}: beta = {beta!r} outside [0, 1)')
+        if threshold is not None and not (isinstance(threshold, (int, float)) and not isinstance(threshold, bool) and threshold == threshold):
+            raise ValueError(f'{who}: threshold = {threshold!r} must be None or a number')
+        self.hold = _int('hold', hold, 1, who)
+        self.log_capacity = _int('log_capacity', log_capacity, 1, who)
+        if chunk_windows is not None:
+            _int('chunk_windows', chunk_windows, 1, who)
+        need = self.window + (self.B - 1) * self.hop
+        if bank.capacity < need:
+            raise ValueError(f'{who}: a ring holds {bank.capacity} frames, window + (hop_windows - 1) hop = {need} are needed')
+        if self.n > bank.capacity:
+            raise ValueError(f'{who}: frames_per_step = {self.n} above the rings\' capacity {bank.capacity}')
+        first = model.models[0] if hasattr(model, 'models') else model
+        if getattr(first, 'num_point', None) != bank.V:
+            raise ValueError(f'{who}: the model has {getattr(first, "num_point", None)} joints, the {noun} {bank.V}')
+        self._w = _Windows(who, model, bank.prep, time_steps, window_size, stream, parent, bank.V, bank.C, bank.M)
+        self._form = tuple(bank.frames_shape(self.n))                 # what step() takes: the caller's push form
+        if _front:
+            bank = bank._bank
+        self.model, self.bank, self.beta, self.eager = model, bank, float(beta), bool(eager)
+        self.threshold = None if threshold is None else float(threshold)
+        S = self.S = bank.feeds
+        if chunk_windows is None:                                     # as few family-sized passes as it takes, of equal size
+            self.chunks = -(-S * self.B // _family_batch(model, self._w.T, bank.V, bank.M))
+            self.chunk = -(-S * self.B // self.chunks)
+        else:
+            self.chunk = min(chunk_windows, S * self.B)
+            self.chunks = -(-S * self.B // self.chunk)
+        dev = self._dev = bank.buf.device
+        self._w.bind(dev)
+        self._frames = torch.zeros(bank.frames_shape(self.n), dtype=bank.buf.dtype, device=dev)
+        # a LiveClassifier's step has no counts or restart: None, and the kernels load neither (four dependent loads less per step)
+        self._counts = None if _front else torch.full((S,), self.n, dtype=torch.int32, device=dev)
+        self._restart = None if _front else torch.zeros(S, dtype=torch.int32, device=dev)
+        self._all, self._none = True, True                            # _counts holds n everywhere; _restart holds zeros
+        with torch.no_grad():
+            K = self._warm().shape[1]
+        if K > ops.STREAM_MAX_K:
+            raise ValueError(f'{who}: {K} classes above {ops.STREAM_MAX_K}')
+        self.num_class = K
+        self.ema = torch.zeros(S, K, dtype=torch.float64, device=dev)
+        self.seen = torch.zeros(S, dtype=torch.int64, device=dev)
+        self.deb = torch.tensor([-1, -1, 0], dtype=torch.int64, device=dev).repeat(S, 1)       # (stable, cand, run)
+        self.log_rows = torch.zeros(self.log_capacity, 3, dtype=torch.int64, device=dev)
+        self.log_conf = torch.zeros(self.log_capacity, dtype=torch.float32, device=dev)
+        self.log_count = torch.zeros(2, dtype=torch.int64, device=dev)                          # (written, dropped)
+        self._graph = self._out = self._keep = None
+        self._watch = _StateWatch(model)
+        self.captures = 0
+        if not self.eager:
+            self._capture()
 
     def _capture(self):
+        """self._chain() as one HIP graph, after self._warm() ran on a side stream."""
         dev = self._dev
         told = hasattr(self.model, '_tamgcn_graphed')                 # GraphedForward's note to a StreamEnsemble
         if told:
@@ -456,211 +544,17 @@ class _LiveChain:
         self._graph, self._out, self._keep = g, out, keep
         self.captures += 1
 
-
-class LiveClassifier(_LiveChain):
-    """model in eval() mode; ring: the FrameRing the frames go to (its prep decides the window form); window frames per window;
-    per step hop_windows windows `hop` frames apart (default hop = window), the newest last; beta in [0, 1): the moving average
-    ema = beta ema + (1 - beta) probs over the valid windows in the order they are seen (0: the newest window's softmax);
-    time_steps / window_size, stream, parent as SlidingWindow's; eager=True runs the chain launch by launch instead of
-    replaying a graph (the same bits).
-
-    step(frames) takes the same n frames per call -- frames_per_step, default 1 -- in the ring's push form, copies them into
-    the chain's input and runs push -> plan -> window -> derive -> forward -> softmax -> average.  -> (label int64 [1], conf
-    fp32 [1], smoothed fp32 [K], logits fp32 (hop_windows, K)): device tensors, no synchronisation; they are the graph's own
-    outputs, overwritten by the next step (clone to keep them).  label is -1 until the first valid window.
-
-    CapturedEval's rules: step() raises while the model is in train() mode; the model's state key (evaluation._state_key, read
-    per step through _StateWatch: see there for what a step sees at once) is compared per step and the chain is captured again
-    when it moved (`captures` counts; such a step synchronises); a StreamEnsemble stays on one stream.  reset() clears the ring,
-    the average and its count; invalidate() makes the next step compare the whole key (after replacing a parameter object)."""
-
-    def __init__(self, model, ring, window, hop_windows=1, hop=None, beta=0.0, time_steps=None, window_size=None, stream='joint',
-                 parent=None, frames_per_step=1, eager=False):
-        who = 'LiveClassifier'
-        if not isinstance(ring, FrameRing):
-            raise ValueError(f'{who}: ring must be a FrameRing')
-        self.window, self.B = _int('window', window, 1, who), _int('hop_windows', hop_windows, 1, who)
-        self.hop = _int('hop', window if hop is None else hop, 1, who)
-        self.n = _int('frames_per_step', frames_per_step, 1, who)
-        if not (isinstance(beta, (int, float)) and 0.0 <= beta < 1.0):
-            raise ValueError(f'{who}: beta = {beta!r} outside [0, 1)')
-        need = self.window + (self.B - 1) * self.hop
-        if ring.capacity < need:
-            raise ValueError(f'{who}: the ring holds {ring.capacity} frames, window + (hop_windows - 1) hop = {need} are needed')
-        if self.n > ring.capacity:
-            raise ValueError(f'{who}: frames_per_step = {self.n} above the ring\'s capacity {ring.capacity}')
-        first = model.models[0] if hasattr(model, 'models') else model
-        if getattr(first, 'num_point', None) != ring.V:
-            raise ValueError(f'{who}: the model has {getattr(first, "num_point", None)} joints, the ring {ring.V}')
-        self._w = _Windows(who, model, ring.prep, time_steps, window_size, stream, parent, ring.V, ring.C, ring.M)
-        self.model, self.ring, self.beta, self.eager = model, ring, float(beta), bool(eager)
-        dev = self._dev = ring.buf.device
-        self._who = who
-        self._w.bind(dev)
-        self._frames = torch.zeros(ring.frames_shape(self.n), dtype=ring.buf.dtype, device=dev)
-        with torch.no_grad():
-            K = self._warm().shape[1]
-        if K > ops.STREAM_MAX_K:
-            raise ValueError(f'{who}: {K} classes above {ops.STREAM_MAX_K}')
-        self.num_class = K
-        self.ema = torch.zeros(K, dtype=torch.float64, device=dev)
-        self.seen = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._graph = self._out = self._keep = None
-        self._watch = _StateWatch(model)
-        self.captures = 0
-        if not self.eager:
-            self._capture()
-
-    def _logits(self):
-        """plan -> window -> derive -> forward on the ring as it stands: (plan, logits)."""
-        w = self._w
-        plan = ops.ring_plan(self.ring.state, self.ring.capacity, self.B, self.window, self.hop)
-        logits = w.forward_one_stream(self.model, w.build(self.ring.buf, plan))
-        if logits.dim() != 2 or logits.shape[0] != self.B:
-            raise ValueError(f'LiveClassifier: the model returned {tuple(logits.shape)}, expected ({self.B}, num_class)')
-        return plan, logits
-
-    def _warm(self):
-        """The read-only part of the chain (nothing of the ring or the average moves): allocator, engines, folded coefficients."""
-        return self._logits()[1]
-
-    def _chain(self):
-        ops.ring_push(self._frames, self.ring.buf, self.ring.state)
-        plan, logits = self._logits()
-        probs, _, _ = ops.window_vote(logits, plan)
-        for j in range(self.B):                                       # oldest first
-            smoothed, label, conf = ops.score_ema(probs[j], plan[j], self.beta, self.ema, self.seen)
-        return label, conf, smoothed, logits
-
-    def step(self, frames):
-        if self.model.training:
-            raise RuntimeError('LiveClassifier: the model is in train() mode; call model.eval() before a step')
-        if not torch.is_tensor(frames) or not frames.is_cuda:
-            raise RuntimeError('LiveClassifier.step: expected a HIP (cuda) tensor; there is no CPU path')
-        if tuple(frames.shape) != tuple(self._frames.shape) or not frames.is_floating_point():
-            raise ValueError(f'LiveClassifier.step: frames must be {tuple(self._frames.shape)} floats, got {tuple(frames.shape)} {frames.dtype}')
-        moved = self._watch.moved()
-        self._frames.copy_(frames)
-        with torch.no_grad():
-            if self.eager:                                            # an eager chain folds a new state by itself
-                return self._chain()
-            if moved or self._graph is None:
-                self._capture()
-        self._graph.replay()
-        return self._out
-
-    def invalidate(self):
-        self._watch.invalidate()
-
-    def reset(self):
-        self.ring.reset()
-        self.ema.zero_()
-        self.seen.zero_()
-
-
-BankStep = collections.namedtuple('BankStep', 'label conf smoothed logits stable')
-BankEvents = collections.namedtuple('BankEvents', 'rows conf dropped')
-
-
-class LiveBank(_LiveChain):
-    """LiveClassifier for S feeds at once: one graph replay pushes a tick's frames to every feed of a RingBank and classifies
-    them all.  model, window, hop_windows, hop, beta, time_steps / window_size, stream, parent, frames_per_step, eager as
-    LiveClassifier's, and its rules: eval mode only, the state key compared per step with a re-capture when it moved (`captures`
-    counts), a StreamEnsemble on one stream, eager=True the same bits, outputs the graph's own tensors.
-
-    step(frames, counts=None, restart=None) -> BankStep(label int64 [S], conf fp32 [S], smoothed fp32 (S, K), logits fp32
-    (S, hop_windows, K), stable int64 [S] | None): frames in the bank's push form with n = frames_per_step; counts, restart:
-    integer tensors [S] or None, copied like the frames into the chain's own device tensors (changing them never captures again).
-    Per feed the semantics are a LiveClassifier's on a FrameRing that was stepped only on the ticks where counts[s] > 0, with
-    that many frames, and reset() where restart[s] was set.  A feed with counts[s] == 0: no window of the tick is valid, its
-    average and `seen` do not move, label, conf, smoothed and stable repeat its state, its logits rows are unspecified.  A feed
-    with restart[s]: average, seen and debounce state are cleared on the device before the tick's push; label is -1 until its
-    first valid window.  No synchronisation.
-
-    The S hop_windows windows go through the model in chunks of chunk_windows (default: the fewest chunks that keep the model on
-    its small-batch eval family, as in SlidingWindow, made equal in size; the last chunk padded with invalid windows), all inside
-    the one graph.  Past the family's bound one pass of all windows (chunk_windows = S hop_windows) measured faster, with the
-    general path's bits instead of the family's (profiles/stream_bank_bench.txt).
-
-    threshold (None: no decisions, stable is None): the debounced decision per feed, updated after the average for every feed
-    whose `seen` moved this tick, feeds ascending -- conf >= float32(threshold) and label == cand: run += 1; else conf >=
-    float32(threshold): cand = label, run = 1; else cand = -1, run = 0; then, when run >= hold and cand != stable: stable = cand
-    and one event (feed, frame = count - 1, label) with its conf is appended to a log of log_capacity rows on the device (a
-    full log drops the event and counts it).  events() -> BankEvents(rows int64 (n, 3), conf fp32 [n], dropped) on the host: the
-    only synchronisation.  clear_events() empties the log on the device.  state_dict() / load_state_dict() carry the bank's
-    buffers and states, the averages, the debounce state and the log."""
-
-    def __init__(self, model, bank, window, hop_windows=1, hop=None, beta=0.0, time_steps=None, window_size=None, stream='joint',
-                 parent=None, frames_per_step=1, eager=False, chunk_windows=None, threshold=None, hold=1, log_capacity=4096):
-        who = self._who = 'LiveBank'
-        if not isinstance(bank, RingBank):
-            raise ValueError(f'{who}: bank must be a RingBank')
-        self.window, self.B = _int('window', window, 1, who), _int('hop_windows', hop_windows, 1, who)
-        self.hop = _int('hop', window if hop is None else hop, 1, who)
-        self.n = _int('frames_per_step', frames_per_step, 1, who)
-        if not (isinstance(beta, (int, float)) and not isinstance(beta, bool) and 0.0 <= beta < 1.0):
-            raise ValueError(f'{who}: beta = {beta!r} outside [0, 1)')
-        if threshold is not None and not (isinstance(threshold, (int, float)) and not isinstance(threshold, bool) and threshold == threshold):
-            raise ValueError(f'{who}: threshold = {threshold!r} must be None or a number')
-        self.hold = _int('hold', hold, 1, who)
-        self.log_capacity = _int('log_capacity', log_capacity, 1, who)
-        if chunk_windows is not None:
-            _int('chunk_windows', chunk_windows, 1, who)
-        need = self.window + (self.B - 1) * self.hop
-        if bank.capacity < need:
-            raise ValueError(f'{who}: a ring holds {bank.capacity} frames, window + (hop_windows - 1) hop = {need} are needed')
-        if self.n > bank.capacity:
-            raise ValueError(f'{who}: frames_per_step = {self.n} above the rings\' capacity {bank.capacity}')
-        first = model.models[0] if hasattr(model, 'models') else model
-        if getattr(first, 'num_point', None) != bank.V:
-            raise ValueError(f'{who}: the model has {getattr(first, "num_point", None)} joints, the bank {bank.V}')
-        self._w = _Windows(who, model, bank.prep, time_steps, window_size, stream, parent, bank.V, bank.C, bank.M)
-        self.model, self.bank, self.beta, self.eager = model, bank, float(beta), bool(eager)
-        self.threshold = None if threshold is None else float(threshold)
-        S = self.S = bank.feeds
-        if chunk_windows is None:                                     # as few family-sized passes as it takes, of equal size
-            self.chunks = -(-S * self.B // _family_batch(model, self._w.T, bank.V, bank.M))
-            self.chunk = -(-S * self.B // self.chunks)
-        else:
-            self.chunk = min(chunk_windows, S * self.B)
-            self.chunks = -(-S * self.B // self.chunk)
-        dev = self._dev = bank.buf.device
-        self._w.bind(dev)
-        self._frames = torch.zeros(bank.frames_shape(self.n), dtype=bank.buf.dtype, device=dev)
-        self._counts = torch.full((S,), self.n, dtype=torch.int32, device=dev)
-        self._restart = torch.zeros(S, dtype=torch.int32, device=dev)
-        self._all, self._none = True, True                            # _counts holds n everywhere; _restart holds zeros
-        with torch.no_grad():
-            K = self._warm().shape[1]
-        if K > ops.STREAM_MAX_K:
-            raise ValueError(f'{who}: {K} classes above {ops.STREAM_MAX_K}')
-        self.num_class = K
-        self.ema = torch.zeros(S, K, dtype=torch.float64, device=dev)
-        self.seen = torch.zeros(S, dtype=torch.int64, device=dev)
-        self.deb = torch.tensor([-1, -1, 0], dtype=torch.int64, device=dev).repeat(S, 1)       # (stable, cand, run)
-        self.log_rows = torch.zeros(self.log_capacity, 3, dtype=torch.int64, device=dev)
-        self.log_conf = torch.zeros(self.log_capacity, dtype=torch.float32, device=dev)
-        self.log_count = torch.zeros(2, dtype=torch.int64, device=dev)                          # (written, dropped)
-        self._graph = self._out = self._keep = None
-        self._watch = _StateWatch(model)
-        self.captures = 0
-        if not self.eager:
-            self._capture()
-
     def _logits(self):
         """plan -> windows -> derive -> forward, chunk by chunk, on the bank as it stands: (plan (S B, 2), logits (S B, K))."""
         w, bank, S, B = self._w, self.bank, self.S, self.B
         rows = self.chunks * self.chunk
         plan = ops.bank_plan(bank.state, bank.capacity, B, self.window, self.hop, self._counts, rows=rows)
-        if w.prep == 'nucla':
-            x = ops.bank_window_nucla(bank.buf, plan, B, w.parent, w.T, NUCLA_CENTER_JOINT, w.stream)
-        else:
-            x = ops.stream_derive(ops.bank_window_clip(bank.buf, plan, B, w.T), w.parent, w.stream)
+        x = w.build(bank.buf, plan, B)
         logits = None
         for c in range(self.chunks):
             out = w.forward_one_stream(self.model, x[c * self.chunk:(c + 1) * self.chunk])
             if out.dim() != 2 or out.shape[0] != self.chunk:
-                raise ValueError(f'LiveBank: the model returned {tuple(out.shape)}, expected ({self.chunk}, num_class)')
+                raise ValueError(f'{self._who}: the model returned {tuple(out.shape)}, expected ({self.chunk}, num_class)')
             if self.chunks == 1:
                 logits = out
                 break
@@ -688,7 +582,7 @@ class LiveBank(_LiveChain):
 
     def _flags(self, name, given, own, default, is_default):
         """Copy counts / restart into the chain's tensor; None fills the default once.  -> whether `own` now holds the default."""
-        given = _feed_flags('LiveBank.step', name, given, self.S)
+        given = _feed_flags(f'{self._who}.step', name, given, self.S)
         if given is None:
             if not is_default:
                 own.fill_(default)
@@ -697,14 +591,15 @@ class LiveBank(_LiveChain):
         return False
 
     def step(self, frames, counts=None, restart=None):
+        who = self._who
         if self.model.training:
-            raise RuntimeError('LiveBank: the model is in train() mode; call model.eval() before a step')
+            raise RuntimeError(f'{who}: the model is in train() mode; call model.eval() before a step')
         if not torch.is_tensor(frames) or not frames.is_cuda:
-            raise RuntimeError('LiveBank.step: expected a HIP (cuda) tensor; there is no CPU path')
-        if tuple(frames.shape) != tuple(self._frames.shape) or not frames.is_floating_point():
-            raise ValueError(f'LiveBank.step: frames must be {tuple(self._frames.shape)} floats, got {tuple(frames.shape)} {frames.dtype}')
+            raise RuntimeError(f'{who}.step: expected a HIP (cuda) tensor; there is no CPU path')
+        if tuple(frames.shape) != self._form or not frames.is_floating_point():
+            raise ValueError(f'{who}.step: frames must be {self._form} floats, got {tuple(frames.shape)} {frames.dtype}')
         moved = self._watch.moved()
-        self._frames.copy_(frames)
+        self._frames.copy_(frames)                                    # a FrameRing's form lacks only the feed axis of one
         self._all = self._flags('counts', counts, self._counts, self.n, self._all)
         self._none = self._flags('restart', restart, self._restart, 0, self._none)
         with torch.no_grad():
@@ -750,3 +645,39 @@ class LiveBank(_LiveChain):
                 raise ValueError(f'LiveBank.load_state_dict: {k} must be {tuple(v.shape)} {v.dtype}')
         for k, v in own.items():
             v.copy_(sd[k])                                            # in place: the graph holds these addresses
+
+
+class LiveClassifier:
+    """The frame-by-frame use on one FrameRing: a thin front on LiveBank's chain at S = 1, all hop_windows windows in one pass
+    through the model, no decisions.  model, ring (its prep decides the window form), window, hop_windows, hop, beta, time_steps /
+    window_size, stream, parent, frames_per_step, eager as LiveBank's, and its rules: eval mode only, the state key compared per
+    step with a re-capture when it moved (`captures` counts), a StreamEnsemble on one stream, eager=True the same bits.
+
+    step(frames) takes the same n frames per call -- frames_per_step, default 1 -- in the ring's push form, copies them into
+    the chain's input and runs push -> plan -> window -> derive -> forward -> softmax -> average.  -> (label int64 [1], conf
+    fp32 [1], smoothed fp32 [K], logits fp32 (hop_windows, K)): device tensors, no synchronisation; they are the graph's own
+    outputs, overwritten by the next step (clone to keep them).  label is -1 until the first valid window.
+
+    ema fp64 [K] and seen int64 [1] are the average and the number of valid windows it has seen.  reset() clears the ring, the
+    average and its count; invalidate() makes the next step compare the whole key (after replacing a parameter object)."""
+
+    def __init__(self, model, ring, window, hop_windows=1, hop=None, beta=0.0, time_steps=None, window_size=None, stream='joint',
+                 parent=None, frames_per_step=1, eager=False):
+        live = self._live = LiveBank(model, ring, window, hop_windows, hop, beta, time_steps, window_size, stream, parent, frames_per_step,
+                                     eager, chunk_windows=hop_windows, _front='LiveClassifier')
+        self.model, self.ring, self.eager, self.num_class = model, ring, live.eager, live.num_class
+        self.ema, self.seen = live.ema[0], live.seen
+
+    @property
+    def captures(self):
+        return self._live.captures
+
+    def step(self, frames):
+        out = self._live.step(frames)
+        return out.label, out.conf, out.smoothed[0], out.logits[0]
+
+    def invalidate(self):
+        self._live.invalidate()
+
+    def reset(self):
+        self._live.reset()

@@ -16,14 +16,15 @@ profiles/stream_infer_bench.txt).
     python tools/stream_bench.py bank [rounds] [ticks]                        (profiles/stream_bank_bench.txt)
         S feeds at once, S = 1 4 8 16 32 64, one frame per feed and tick, on N-UCLA CTR-GCN (window 40 -> 52 steps), COCO CTR-GCN
         (window 64) and N-UCLA ST-GCN: (a) LiveBank.step, one graph replay for all feeds; (b) S LiveClassifier graph replays one
-        after another (the code as it stood before the bank: the baseline); (c) LiveBank with chunk_windows = S, one forward of
+        after another (S one-feed chains: the baseline); (c) LiveBank with chunk_windows = S, one forward of
         all windows, where S is past the small-batch family's bound (elsewhere (c) is (a)).  ms per tick and feeds per 33 ms.
     python tools/stream_bench.py bank-trace [ticks]
         `ticks` LiveBank ticks per model at S = 32 with the decision log on -- run it under rocprofv3 --kernel-trace --stats
     python tools/stream_bench.py bank-report <kernel_trace.csv>
         the bank kernels' times from that run
 
-The models carry seeded parameters (tests/golden/params.py); their accuracy is not the subject."""
+One ring is a bank of one feed, so `trace` and `report` show the bank_* kernels at S = 1; profiles recorded before that carry the
+former ring_*, window_* and score_ema kernel names.  The models carry seeded parameters (tests/golden/params.py); their accuracy is not the subject."""
 import csv
 import os
 import statistics
@@ -44,8 +45,7 @@ PASSES = 10                    # sliding passes per timed window
 BANK_FEEDS = (1, 4, 8, 16, 32, 64)
 BANK_KERNELS = ('bank_push_kernel', 'bank_advance_kernel', 'bank_plan_kernel', 'bank_window_nucla_kernel', 'bank_window_clip_kernel',
                 'window_softmax_kernel', 'bank_ema_kernel', 'bank_decide_kernel')
-KERNELS = ('ring_push_kernel', 'ring_advance_kernel', 'ring_plan_kernel', 'window_nucla_kernel', 'window_clip_kernel', 'window_softmax_kernel',
-           'window_vote_kernel', 'score_ema_kernel')
+KERNELS = BANK_KERNELS[:-1] + ('window_vote_kernel',)      # one ring is a one-feed bank: the same kernels, and the per-frame vote
 
 
 def _model(margs):
