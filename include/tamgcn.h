@@ -16,9 +16,14 @@
  *   - return value 0 = launched; <0 = rejected before any launch
  *     (tamgcn_last_error() gives the reason for the calling thread);
  *   - calls are re-entrant per stream: no global mutable state;
- *   - skeletons whose joint count V is not a multiple of 4 (NTU: 25): the 16-byte kernels read the last piece of a frame
- *     whole, i.e. up to 12 bytes past the last element of a SOURCE activation -- such buffers must be readable for 16 bytes
- *     behind their end (the Python layer allocates that slack and copies caller tensors that lack it).
+ *   - READ SLACK.  Skeletons whose joint count V is not a multiple of 4 (NTU: 25): the 16-byte kernels read the last piece
+ *     of a frame whole, i.e. up to 12 bytes past the last element of a SOURCE activation.  The contract is one statement,
+ *     for every entry point: 16 readable bytes behind the last element of each such buffer (one whole piece; what is read
+ *     there is discarded).  The buffers it binds are the activations streamed in 16-byte pieces from dword-aligned rows:
+ *     tamgcn_conv / _conv_pair d->src, the tamgcn_tconv_* d->src and d->mask, x3 and dy of the tamgcn_ctrgc_tiled_* and
+ *     tamgcn_vgen_* aggregation and dE-accumulation entry points, and d->x of the f2v / f2g stages.  Every other operand is
+ *     read inside its extent.  The Python layer allocates that slack (ops.empty) and copies caller tensors that lack it
+ *     (ops.with_slack); tests/slack_audit.py holds every launch to it.
  *
  * "src" operands.  Most kernels read their activation operand through a fused
  * per-channel affine/mix prologue so that train-mode BatchNorm apply (forward)
@@ -330,8 +335,8 @@ int tamgcn_ctrgc_tiled_de_tail(const tamgcn_ctrgc_desc* d, const float* dE, floa
  *   _vgen_de_acc     as tamgcn_ctrgc_tiled_de_acc
  *   _vgen_de_tail    as tamgcn_ctrgc_bwd_de_tail      (channel groups, dpq [groups][S*2*R][N][V])
  * S in {1, 3}, Cout % 16 == 0, R a multiple of 4 up to 32.  V = 20, 25 and 32 are accepted too (the library's own
- * routing keeps their dedicated kernels).  x3, E and dy are read in 16-byte pieces from dword-aligned rows: keep 12
- * readable bytes behind each of them.
+ * routing keeps their dedicated kernels).  x3 and dy are read in 16-byte pieces from dword-aligned rows: READ SLACK (top of
+ * this file) applies to them.  E is loaded element by element and needs none.
  * tamgcn_vgen_supported: 1 for 2 <= V <= 32, else 0.  tamgcn_vgen_lds_bytes: the family's largest dynamic-LDS request
  * for (S, V, R), < 0 outside its range. */
 int tamgcn_vgen_supported(int V);
@@ -794,8 +799,8 @@ int tamgcn_f2_tcn(const tamgcn_f2_tcn_desc* d, void* stream);
  *              d->xpart (N, ceil(T_out/4), Cout, VP): sums of out over each FOUR-frame tile (as f2), columns V..VP-1 zero
  * Columns V..VP-1 of E, sum, diff and xpart are exactly zero whatever the inputs' pad columns hold (those are never trusted).
  * Alignment: x and out 4 bytes, everything else 16.  The contiguous input is read in 16-byte pieces from dword-aligned
- * addresses; the last piece of a frame reaches VP - V floats (at most 12 bytes) past it, so 12 readable bytes must follow x
- * (tam_gcn_amd.ops.empty / with_slack); what is read there is discarded.  Each entry point computes its LDS request from the
+ * addresses; the last piece of a frame reaches VP - V floats (at most 12 bytes) past it, so READ SLACK (top of this file: 16
+ * readable bytes) applies to x (tam_gcn_amd.ops.empty / with_slack); what is read there is discarded.  Each entry point computes its LDS request from the
  * geometry of d->V and refuses one above 160 KB (none arises for Cin, K <= 256, R <= 32, Cb <= 64).  Deterministic: two runs
  * are bit-equal.
  * Added in ABI 401 without a version bump: new entry points, no existing layout or semantics changed.  V = 17 and 18 were added
@@ -809,8 +814,8 @@ int tamgcn_f2v_tcn(const tamgcn_f2_tcn_desc* d, void* stream);
  * (tam_gcn_amd/csrc/f2g.hip, tam_gcn_amd/f2g.py).  The f2 descriptors, the algebra above and f2v's buffer layout, all
  * unchanged: the block's input and output contiguous (N, C, T, V); E (N, S, Cout, V, VP), sum, diff, the gemm operands, h
  * (N, C, T, VP) and xpart (N, tiles, C, VP) with frames of VP = (V + 3) & ~3 floats; columns V..VP-1 of E, sum, diff and xpart
- * exactly zero whatever the inputs' pad columns hold; at V % 4 == 0, VP = V and nothing is padded.  Alignment and the 12
- * readable bytes behind x: as f2v.  The kernels are instantiated per frame pitch VP (8, 12, 16, 20, 24, 28), not per joint
+ * exactly zero whatever the inputs' pad columns hold; at V % 4 == 0, VP = V and nothing is padded.  Alignment and the read
+ * slack behind x: as f2v.  The kernels are instantiated per frame pitch VP (8, 12, 16, 20, 24, 28), not per joint
  * count; 17, 18, 20 and 25 are accepted too (the run-time-V form of the f2 / f2v kernels at the same V).  Any other d->V is
  * refused on the host before any launch, the message naming the entry point and "V=<value>".  No grouped entry points.
  *   tamgcn_f2g_supported(V)  1 for 8 <= V <= 28, else 0

@@ -211,6 +211,8 @@ def pair_supported(tensors, N, chans, T, V):
 def conv_pair(src, w0, w1, bias0=None, bias1=None, y0=None, ycoff0=0, y1=None, ycoff1=0, stats=False):
     """y0[:, ycoff0:+M0] = w0 . src + bias0 and y1[:, ycoff1:+M1] = w1 . src + bias1 in one launch, w0 (M0, K, 1, 1),
     w1 (M1, K, 1, 1); returns (y0, part0, y1, part1), bit-identical to the two conv() calls."""
+    if src.x1.shape[-1] % 4:                               # as conv(): the same kernels stream src (pair_supported admits no such V today)
+        src = S(with_slack(src.x1), with_slack(src.x2), src.coef, src.coff, src.act)
     x = src.x1
     N, _, T, V = x.shape
     M0, M1, K = w0.shape[0], w1.shape[0], w0.shape[1]

@@ -10,7 +10,8 @@ Three parts, test-side only:
              overlap, at least one of them a write, where the earlier one in host order does not happen-before the later.
   Recorder   a context manager that produces such a trace from a real run: it wraps the loaded library, ops._ptr, the
              ordering primitives of torch.cuda and the methods of functional.Fork, and sees ATen work through a
-             TorchDispatchMode.  It needs torch; the two parts above do not.
+             TorchDispatchMode.  It needs torch; the two parts above do not.  The wrapped library, ops._ptr, the address ->
+             extent map and the walk over a call's descriptors are LibraryTap, shared with slack_audit.SlackAuditor.
 """
 import bisect
 import ctypes as C
@@ -509,39 +510,20 @@ FORK_METHODS = ('on', 'refork', 'mark', 'wait', 'join', '__exit__')
 FACTORIES = ('aten::empty', 'aten::new_empty', 'aten::empty_like', 'aten::empty_strided', 'aten::new_empty_strided')
 
 
-class Recorder:
-    """with Recorder() as rec: ... ; rec.trace is the host-order trace, rec.unresolved the library pointers without an extent,
-    rec.mismatch the descriptors whose channel-slice geometry did not fit the tensor's extent."""
+class LibraryTap:
+    """What every audit of a real run shares (Recorder below, slack_audit.SlackAuditor): the loaded library behind a proxy whose
+    tamgcn_* calls go through self._call(name, fn, args), ops._ptr reporting the tensors it is given, the map from a device
+    address to the extent of the tensor, storage or allocator block that holds it, and the walk over an entry point's
+    arguments and descriptors that lists every device pointer of the call with its role."""
 
     SNAP_EVERY = 200
 
-    def __init__(self, sync_first=True):
-        self.trace, self.unresolved, self.mismatch = [], [], []
-        self.forks = []                                    # (method, call site) of every functional.Fork call that did something
-        self._via, self._quiet = [], 0
-        self._events, self._keep = {}, []
+    def __init__(self, lib=None):
+        self.unresolved = []
         self._tensors, self._storages, self._blocks = _Ranges(), _Ranges(), _Ranges()
-        self._sync_first = sync_first
         self._snap_age = 0
-
-    # ---- where ------------------------------------------------------------------------------------------------------
-    def _where(self):
-        """(innermost tam_gcn_amd frame as 'file:line', every tam_gcn_amd frame inside-out)."""
-        f, chain = sys._getframe(1), []
-        while f is not None:
-            fn = f.f_code.co_filename
-            if fn.startswith(PKG):
-                chain.append(f'{fn[len(PKG):]}:{f.f_lineno}')
-            f = f.f_back
-        return (chain[0] if chain else None), tuple(chain)
-
-    def _log(self, entry):
-        site, chain = self._where()
-        entry.setdefault('site', site)
-        entry['chain'] = chain
-        if self._via:
-            entry['via'] = self._via[-1]
-        self.trace.append(entry)
+        self._saved = []
+        self._lib_given = lib                              # a stand-in for the loaded library (CPU tests)
 
     # ---- extents ----------------------------------------------------------------------------------------------------
     def _extent(self, p):
@@ -591,12 +573,37 @@ class Recorder:
             if self._storages.add(lo, lo + n) or fresh:
                 self._tensors.purge(lo, lo + n)
 
-    # ---- library launches -------------------------------------------------------------------------------------------
-    def _call(self, name, fn, args):
-        params = self._funcs.get(name)
-        if params is None or not any(d.kind == 'stream' for d in params):
-            return fn(*args)
-        raw = []                                           # (address, mode, role, container, getter, field)
+    def _walk(self, hname, obj, prefix, raw, fname):
+        def get(nm, obj=obj):
+            return getattr(obj, nm)
+        for d in self._structs[hname]:
+            v = getattr(obj, d.name)
+            role = f'{prefix}.{d.name}'
+            if d.kind in ('r', 'w'):
+                vals = list(v) if d.count else [v]
+                for k, p in enumerate(vals):
+                    if p:
+                        raw.append((p, d.kind, role if not d.count else f'{role}[{k}]', hname, get, d.name))
+            elif d.kind == 'struct':
+                self._walk_src(d.base, v, role, raw, hname, get, d.name)
+            elif d.kind == 'desc':
+                if v:
+                    self._walk_src(d.base, v.contents, role, raw, hname, get, d.name)
+
+    def _walk_src(self, base, obj, role, raw, owner, owner_get, owner_field):
+        if base != 'tamgcn_src':
+            self._walk(base, obj, role, raw, None)
+            return
+        for d in self._structs[base]:
+            p = getattr(obj, d.name)
+            if d.kind in ('r', 'w') and p:
+                # container 'src:<owner struct>': refined by the owner's geometry of this source
+                raw.append((p, d.kind, f'{role}.{d.name}', 'src:' + owner, (owner_get, obj), (owner_field, d.name)))
+
+    def _pointers(self, name, params, args):
+        """(stream, [(address, mode, role, container, getter, field)], arg): every device pointer of one call; arg(name) is the
+        value of a parameter."""
+        raw = []
         argmap = {d.name: a for d, a in zip(params, args)}
 
         def arg(nm):
@@ -626,6 +633,93 @@ class Recorder:
                 for k, obj in enumerate(objs):
                     prefix = d.name if len(objs) == 1 else f'{d.name}[{k}]'
                     self._walk(d.base, obj, prefix, raw, name)
+        return stream, raw, arg
+
+    def _call(self, name, fn, args):
+        return fn(*args)
+
+    def _install_library(self):
+        """The proxy in place of the loaded library and the reporting ops._ptr; both are undone by _restore()."""
+        from tam_gcn_amd import _lib, ops
+        tap = self
+        self._lib_mod = _lib
+        self._structs, self._funcs = parse_header()
+        bad = completeness_problems(_lib, self._structs, self._funcs)
+        if bad:
+            raise AssertionError('unclassified pointers: ' + '; '.join(bad[:5]))
+        before = _lib._lib
+        real = self._lib_given if self._lib_given is not None else _lib.load()
+        self._real = real
+
+        class Proxy:
+            def __getattr__(self, name):
+                fn = getattr(real, name)
+                if not name.startswith('tamgcn_'):
+                    return fn
+
+                def call(*args):
+                    return tap._call(name, fn, args)
+                return call
+
+        self._saved.append((_lib, '_lib', real if self._lib_given is None else before))
+        _lib._lib = Proxy()
+        real_ptr = ops._ptr
+
+        def _ptr(t):
+            p = real_ptr(t)
+            if t is not None:
+                tap._register_tensor(t)
+                tap._register_storage(t, False)
+            return p
+        self._patch(ops, '_ptr', _ptr)
+
+    def _patch(self, owner, attr, new):
+        self._saved.append((owner, attr, getattr(owner, attr)))
+        setattr(owner, attr, new)
+
+    def _restore(self):
+        for owner, attr, old in reversed(self._saved):
+            setattr(owner, attr, old)
+        self._saved = []
+
+
+class Recorder(LibraryTap):
+    """with Recorder() as rec: ... ; rec.trace is the host-order trace, rec.unresolved the library pointers without an extent,
+    rec.mismatch the descriptors whose channel-slice geometry did not fit the tensor's extent."""
+
+    def __init__(self, sync_first=True):
+        LibraryTap.__init__(self)
+        self.trace, self.mismatch = [], []
+        self.forks = []                                    # (method, call site) of every functional.Fork call that did something
+        self._via, self._quiet = [], 0
+        self._events, self._keep = {}, []
+        self._sync_first = sync_first
+
+    # ---- where ------------------------------------------------------------------------------------------------------
+    def _where(self):
+        """(innermost tam_gcn_amd frame as 'file:line', every tam_gcn_amd frame inside-out)."""
+        f, chain = sys._getframe(1), []
+        while f is not None:
+            fn = f.f_code.co_filename
+            if fn.startswith(PKG):
+                chain.append(f'{fn[len(PKG):]}:{f.f_lineno}')
+            f = f.f_back
+        return (chain[0] if chain else None), tuple(chain)
+
+    def _log(self, entry):
+        site, chain = self._where()
+        entry.setdefault('site', site)
+        entry['chain'] = chain
+        if self._via:
+            entry['via'] = self._via[-1]
+        self.trace.append(entry)
+
+    # ---- library launches -------------------------------------------------------------------------------------------
+    def _call(self, name, fn, args):
+        params = self._funcs.get(name)
+        if params is None or not any(d.kind == 'stream' for d in params):
+            return fn(*args)
+        stream, raw, _ = self._pointers(name, params, args)
         acc, ok = [], True
         for p, mode, role, container, get, field in raw:
             hi, res = self._extent(p)
@@ -639,33 +733,6 @@ class Recorder:
         if rc == 0:
             self._log(dict(op='launch', stream=stream, label=name, acc=acc, resolved=ok))
         return rc
-
-    def _walk(self, hname, obj, prefix, raw, fname):
-        def get(nm, obj=obj):
-            return getattr(obj, nm)
-        for d in self._structs[hname]:
-            v = getattr(obj, d.name)
-            role = f'{prefix}.{d.name}'
-            if d.kind in ('r', 'w'):
-                vals = list(v) if d.count else [v]
-                for k, p in enumerate(vals):
-                    if p:
-                        raw.append((p, d.kind, role if not d.count else f'{role}[{k}]', hname, get, d.name))
-            elif d.kind == 'struct':
-                self._walk_src(d.base, v, role, raw, hname, get, d.name)
-            elif d.kind == 'desc':
-                if v:
-                    self._walk_src(d.base, v.contents, role, raw, hname, get, d.name)
-
-    def _walk_src(self, base, obj, role, raw, owner, owner_get, owner_field):
-        if base != 'tamgcn_src':
-            self._walk(base, obj, role, raw, None)
-            return
-        for d in self._structs[base]:
-            p = getattr(obj, d.name)
-            if d.kind in ('r', 'w') and p:
-                # container 'src:<owner struct>': refined by the owner's geometry of this source
-                raw.append((p, d.kind, f'{role}.{d.name}', 'src:' + owner, (owner_get, obj), (owner_field, d.name)))
 
     # ---- channel slices ---------------------------------------------------------------------------------------------
     # geometry of a tamgcn_src inside a descriptor: owner struct -> field -> (N, channels used, elements per channel)
@@ -844,36 +911,9 @@ class Recorder:
     def __enter__(self):
         import torch
         from torch.utils._python_dispatch import TorchDispatchMode
-        from tam_gcn_amd import _lib, functional, ops
+        from tam_gcn_amd import functional
         rec = self
-        self._lib_mod = _lib
-        self._structs, self._funcs = parse_header()
-        bad = completeness_problems(_lib, self._structs, self._funcs)
-        if bad:
-            raise AssertionError('unclassified pointers: ' + '; '.join(bad[:5]))
-        real = _lib.load()
-
-        class Proxy:
-            def __getattr__(self, name):
-                fn = getattr(real, name)
-                if not name.startswith('tamgcn_'):
-                    return fn
-
-                def call(*args):
-                    return rec._call(name, fn, args)
-                return call
-
-        self._saved = [(_lib, '_lib', real)]
-        _lib._lib = Proxy()
-        real_ptr = ops._ptr
-
-        def _ptr(t):
-            p = real_ptr(t)
-            if t is not None:
-                rec._register_tensor(t)
-                rec._register_storage(t, False)
-            return p
-        self._patch(ops, '_ptr', _ptr)
+        self._install_library()
 
         def prim(owner, attr, make):
             orig = getattr(owner, attr)
@@ -945,15 +985,10 @@ class Recorder:
         self._mode.__enter__()
         return self
 
-    def _patch(self, owner, attr, new):
-        self._saved.append((owner, attr, getattr(owner, attr)))
-        setattr(owner, attr, new)
-
     def __exit__(self, *exc):
         self._mode.__exit__(*exc)
         self._mt.__exit__(*exc)
-        for owner, attr, old in reversed(self._saved):
-            setattr(owner, attr, old)
+        self._restore()
         self._keep = []
         return False
 
