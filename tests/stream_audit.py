@@ -2,9 +2,10 @@
 
 Three parts, test-side only:
 
-  header     parse_header() reads include/tamgcn.h: every struct field and every parameter of every entry point, with
-             `const T*` = read and `T*` = write.  STRUCT_MAP ties the header's structs to the ctypes classes of
-             tam_gcn_amd/_lib.py; completeness_problems() lists every pointer of the binding that has no classification.
+  header     parse_header() lives in the package (tam_gcn_amd/_abi.py) and is re-exported here: it reads every struct field
+             and every parameter of every entry point of include/tamgcn.h, with `const T*` = read and `T*` = write.
+             tam_gcn_amd/_lib.py derives its ctypes classes (_lib.STRUCTS) and signatures from the same parse;
+             completeness_problems() checks a binding against a parse and lists every pointer that has no classification.
   Checker    pure Python over a trace (a list of dicts, see the constructors launch() .. protect() below): vector clocks
              per stream and one for the host; a hazard is a pair of accesses on different streams whose byte ranges
              overlap, at least one of them a write, where the earlier one in host order does not happen-before the later.
@@ -16,134 +17,19 @@ Three parts, test-side only:
 import bisect
 import ctypes as C
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'tamgcn.h')
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from tam_gcn_amd._abi import BASE_TYPES, HEADER, Decl, _parse_decl, parse_header  # noqa: E402,F401  (re-exported)
+
 PKG = os.path.join(ROOT, 'tam_gcn_amd') + os.sep
 
+
 # =====================================================================================================================
-# the header
+# the binding against the header
 # =====================================================================================================================
-BASE_TYPES = ('unsigned char', 'long long', 'unsigned', 'int', 'float', 'double', 'void', 'char')
-
-# header struct -> ctypes class of tam_gcn_amd/_lib.py
-STRUCT_MAP = {
-    'tamgcn_src': 'Src',
-    'tamgcn_conv_desc': 'ConvDesc',
-    'tamgcn_wgrad_desc': 'WgradDesc',
-    'tamgcn_conv_pair_desc': 'ConvPairDesc',
-    'tamgcn_wgrad_pair_desc': 'WgradPairDesc',
-    'tamgcn_reduce_desc': 'ReduceDesc',
-    'tamgcn_bn_fwd_desc': 'BnFwdDesc',
-    'tamgcn_bn_bwd_desc': 'BnBwdDesc',
-    'tamgcn_ctrgc_desc': 'CtrgcDesc',
-    'tamgcn_tconv_desc': 'TconvDesc',
-    'tamgcn_ce_desc': 'CeDesc',
-    'tamgcn_f2_gcn_desc': 'F2GcnDesc',
-    'tamgcn_f2_gemm_desc': 'F2GemmDesc',
-    'tamgcn_f2_tcn_desc': 'F2TcnDesc',
-    'tamgcn_f2s_gcn_desc': 'F2sGcnDesc',
-    'tamgcn_f2s_tcn_desc': 'F2sTcnDesc',
-    'tamgcn_f2s_tcn_bwd_desc': 'F2sTcnBwdDesc',
-    'tamgcn_f2s_gcn_bwd_desc': 'F2sGcnBwdDesc',
-    'tamgcn_optim_desc': 'OptimDesc',
-    'tamgcn_grad_guard': 'GradGuard',
-}
-
-
-class Decl:
-    """One field or parameter.  kind: 'scalar' | 'r' | 'w' (device or host array read / written) | 'stream' |
-    'struct' (by value) | 'desc' (pointer to a struct of the header)."""
-    __slots__ = ('name', 'base', 'ptr', 'const', 'count', 'kind')
-
-    def __init__(self, name, base, ptr, const, count, structs):
-        self.name, self.base, self.ptr, self.const, self.count = name, base, ptr, const, count
-        if not ptr:
-            self.kind = 'struct' if base in structs else 'scalar'
-        elif base in structs:
-            self.kind = 'desc'
-        elif base == 'void' and name == 'stream' and not const:
-            self.kind = 'stream'
-        else:
-            self.kind = 'r' if const else 'w'
-
-    def __repr__(self):
-        return f'<{self.kind} {"const " if self.const else ""}{self.base}{"*" if self.ptr else ""} {self.name}' \
-               f'{"[%d]" % self.count if self.count else ""}>'
-
-
-def _parse_decl(text, structs, defines):
-    """'const float* w[TAMGCN_TCONV_MAXB]' / 'int N, K' -> [Decl]."""
-    s = ' '.join(text.split())
-    const = s.startswith('const ')
-    if const:
-        s = s[6:]
-    base = None
-    for t in sorted(tuple(BASE_TYPES) + tuple(structs), key=len, reverse=True):
-        if s == t or s.startswith(t + ' ') or s.startswith(t + '*'):
-            base, s = t, s[len(t):].strip()
-            break
-    if base is None:
-        raise ValueError(f'tamgcn.h: unknown type in {text!r}')
-    ptr = s.startswith('*')
-    if ptr:
-        s = s[1:].strip()
-        if '*' in s:
-            raise ValueError(f'tamgcn.h: pointer to pointer in {text!r}')
-    out = []
-    for nm in [p.strip() for p in s.split(',')] if s else ['']:
-        m = re.fullmatch(r'(\w*)(?:\[(\w+)\])?', nm)
-        if not m:
-            raise ValueError(f'tamgcn.h: cannot parse {text!r}')
-        cnt = m.group(2)
-        if cnt is not None:
-            cnt = int(cnt) if cnt.isdigit() else defines[cnt]
-        out.append(Decl(m.group(1), base, ptr, const, cnt, structs))
-    if ptr and len(out) != 1:
-        raise ValueError(f'tamgcn.h: several names behind one pointer type in {text!r}')
-    return out
-
-
-def parse_header(path=HEADER):
-    """(structs, funcs): {struct name: [Decl]} and {entry point: [Decl]} (a `void` parameter list is [])."""
-    with open(path) as f:
-        text = f.read()
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    text = re.sub(r'//[^\n]*', ' ', text)
-    defines = {m.group(1): int(m.group(2)) for m in re.finditer(r'^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$', text, re.M)}
-    text = re.sub(r'^[ \t]*#[^\n]*$', ' ', text, flags=re.M)
-    text = text.replace('extern "C" {', ' ')
-    structs = {}
-    pat = re.compile(r'typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;', re.S)
-    for m in pat.finditer(text):                           # names first: a struct may hold another by value
-        if m.group(1) != m.group(3):
-            raise ValueError(f'tamgcn.h: struct {m.group(1)} is typedef-ed as {m.group(3)}')
-        structs[m.group(1)] = None
-    for m in pat.finditer(text):
-        fields = []
-        for stmt in m.group(2).split(';'):
-            if stmt.strip():
-                fields += _parse_decl(stmt, structs, defines)
-        structs[m.group(1)] = fields
-    rest = pat.sub(';', text)
-    funcs = {}
-    for stmt in rest.split(';'):
-        s = ' '.join(stmt.split())
-        if s in ('', '}'):
-            continue
-        m = re.fullmatch(r'(.+?)\b(tamgcn_\w+) ?\((.*)\)', s)
-        if not m:
-            raise ValueError(f'tamgcn.h: statement not understood: {s[:80]!r}')
-        params = []
-        if m.group(3).strip() != 'void':
-            for p in m.group(3).split(','):
-                params += _parse_decl(p, structs, defines)
-        funcs[m.group(2)] = params
-    return structs, funcs
-
-
 def _is_struct(t):
     return isinstance(t, type) and issubclass(t, C.Structure)
 
@@ -163,19 +49,20 @@ def completeness_problems(lib_module, structs=None, funcs=None):
     if structs is None:
         structs, funcs = parse_header()
     bad = []
-    by_class = {v: k for k, v in STRUCT_MAP.items()}
+    struct_map = {h: c.__name__ for h, c in lib_module.STRUCTS.items()}     # header struct -> ctypes class of the binding
+    by_class = {v: k for k, v in struct_map.items()}
     classes = {n: c for n, c in vars(lib_module).items() if _is_struct(c) and c.__module__ == lib_module.__name__}
     for n in classes:
         if n not in by_class:
-            bad.append(f'_lib.{n}: no header struct mapped to it (STRUCT_MAP)')
-    for h, n in STRUCT_MAP.items():
+            bad.append(f'_lib.{n}: no header struct mapped to it (_lib.STRUCTS)')
+    for h, n in struct_map.items():
         if h not in structs:
-            bad.append(f'STRUCT_MAP: {h} is not a struct of tamgcn.h')
-        if n not in classes:
-            bad.append(f'STRUCT_MAP: _lib.{n} does not exist')
+            bad.append(f'_lib.STRUCTS: {h} is not a struct of tamgcn.h')
+        if classes.get(n) is not lib_module.STRUCTS[h]:
+            bad.append(f'_lib.STRUCTS: {h} is not the module attribute _lib.{n}')
     for h in structs:
-        if h not in STRUCT_MAP:
-            bad.append(f'tamgcn.h struct {h}: no ctypes class mapped (STRUCT_MAP)')
+        if h not in struct_map:
+            bad.append(f'tamgcn.h struct {h}: no ctypes class mapped (_lib.STRUCTS)')
 
     def match(where, ct, d):
         """ctypes type `ct` against header declaration `d` (None: missing)."""
@@ -206,7 +93,7 @@ def completeness_problems(lib_module, structs=None, funcs=None):
         elif d.kind != 'scalar':
             bad.append(f'{where}: scalar in the binding, header has {d!r}')
 
-    for h, n in STRUCT_MAP.items():
+    for h, n in struct_map.items():
         if h not in structs or n not in classes:
             continue
         hf = {d.name: d for d in structs[h]}

@@ -1,18 +1,13 @@
 """The C-ABI library loads and exports every symbol include/tamgcn.h declares
 (no compute calls: this runs without a GPU)."""
 import ctypes
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 def _declared():
-    src = open(os.path.join(ROOT, 'include', 'tamgcn.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    return sorted(set(re.findall(r'\b(tamgcn_[a-z0-9_]+)\s*\(', src)))
+    from tam_gcn_amd._abi import parse_header
+    return sorted(parse_header()[1])
 
 
 def test_library_builds_and_exports_every_declared_symbol():

@@ -38,10 +38,10 @@ def test_the_table_covers_the_binding():
             if A._is_pointer_type(ct) and ct._type_ is C.c_float:       # a host array of floats (tamgcn_score_sweep's alphas)
                 assert S.CLASSES[(name, d.name)].cls == S.FLAT
                 n += 1
-    for h, cname in A.STRUCT_MAP.items():
+    for h, cls in _lib.STRUCTS.items():
         if h == 'tamgcn_src':
             continue
-        for (fname, ct), d in zip(getattr(_lib, cname)._fields_, structs[h]):
+        for (fname, ct), d in zip(cls._fields_, structs[h]):
             base = ct._type_ if A._is_array_type(ct) else ct
             if base is C.c_void_p and d.kind == 'r' and d.base == 'float':
                 assert (h, fname) in S.CLASSES, (h, fname)

@@ -1,4 +1,4 @@
-"""The stream-schedule checker on synthetic traces, and the header parser / struct map against include/tamgcn.h and
+"""The stream-schedule checker on synthetic traces, and the header parser / derived binding against include/tamgcn.h and
 tam_gcn_amd/_lib.py.  No GPU: the checker is pure Python, the traces are written by hand in the vocabulary of
 functional.Fork (fork = side.wait_stream(main), join = main.wait_stream(side), mark / wait = event record / wait)."""
 import ctypes as C
@@ -244,14 +244,14 @@ def test_unknown_trace_entries_are_refused():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the header and the struct map
+# the header and the binding derived from it
 # ---------------------------------------------------------------------------------------------------------------------
 def test_every_pointer_of_the_binding_is_classified_by_the_header():
     from tam_gcn_amd import _lib
     structs, funcs = A.parse_header()
     assert A.completeness_problems(_lib, structs, funcs) == []
     assert set(funcs) == set(_lib.SIGNATURES)
-    assert set(structs) == set(A.STRUCT_MAP)
+    assert set(structs) == set(_lib.STRUCTS)
 
 
 def test_header_parser_reads_const_as_read_and_plain_as_write():
@@ -288,7 +288,7 @@ def test_an_unclassified_pointer_fails_the_completeness_check(tmp_path):
     class Src(C.Structure):                                   # a pointer field the header does not have
         _fields_ = list(_lib.Src._fields_) + [('x3', C.c_void_p)]
     Src.__module__ = _lib.__name__
-    bad = A.completeness_problems(variant(Src=Src), structs, funcs)
+    bad = A.completeness_problems(variant(Src=Src, STRUCTS=dict(_lib.STRUCTS, tamgcn_src=Src)), structs, funcs)
     assert any('Src.x3' in b for b in bad), bad
 
     class Extra(C.Structure):                                 # a structure of the binding without a header struct
