@@ -1,8 +1,8 @@
-"""Build libtamgcn.so (HIP, gfx950 only) in-tree with hipcc.
+"""Build libtamgcn.so and its extension library libtamgcn_xmodal.so (HIP, gfx950 only) in-tree with hipcc.
 
     python -m tam_gcn_amd.build [--force]
 
-The shared object is git-ignored but travels to the GPU box with the
+The shared objects are git-ignored but travel to the GPU box with the
 snapshot; nothing is JIT-compiled at import time.
 """
 import os
@@ -12,6 +12,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = ['lib.hip', 'conv.hip', 'wgrad.hip', 'reduce.hip', 'bn.hip', 'elementwise.hip', 'dropout.hip', 'ctrgc.hip', 'ctrgc_de.hip', 'ctrgc_tiled.hip', 'vgen.hip', 'stemhead.hip', 'celoss.hip', 'feeder.hip', 'clipfeeder.hip', 'streaming.hip', 'f2.hip', 'f2v.hip', 'f2g.hip', 'f2s.hip', 'f2s_bwd.hip', 'saliency.hip', 'guidance.hip', 'tconv.hip', 'optim.hip', 'evalmeter.hip']
 LIB = os.path.join(HERE, 'libtamgcn.so')
+# the cross-modal head (crossmodal.py): a library and a header (include/tamgcn_xmodal.h) of its own, the core ABI stays as it is
+XM_SRC = ['xm_lib.hip', 'xm_hidden.hip', 'xm_gate.hip', 'xm_pool.hip']
+XM_LIB = os.path.join(HERE, 'libtamgcn_xmodal.so')
 ARCH = 'gfx950'
 
 
@@ -35,15 +38,42 @@ def needs_build():
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def xm_sources():
+    return [os.path.join(HERE, 'csrc', 'xmodal', s) for s in XM_SRC]
+
+
+def needs_build_xmodal():
+    if not os.path.exists(XM_LIB):
+        return True
+    xm = os.path.join(HERE, 'csrc', 'xmodal')
+    deps = xm_sources() + [os.path.join(xm, h) for h in os.listdir(xm) if h.endswith('.h')] + \
+        [os.path.join(HERE, 'csrc', 'common.h'), os.path.join(HERE, '..', 'include', 'tamgcn.h'), os.path.join(HERE, '..', 'include', 'tamgcn_xmodal.h')]
+    t = os.path.getmtime(XM_LIB)
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_xmodal(force=False, verbose=True):
+    """libtamgcn_xmodal.so from csrc/xmodal/*.hip."""
+    if not force and not needs_build_xmodal():
+        return XM_LIB
+    return _compile_and_link(xm_sources(), XM_LIB, '.o', (), verbose)
+
+
 def build(force=False, verbose=True, out=None, defines=()):
-    """out/defines: instrumented side builds for tools/ (e.g. -DTAMGCN_TRACE); the product is LIB."""
-    lib = out or LIB
-    if out is None and not force and not needs_build():
-        return LIB
+    """Both libraries; returns LIB.  out/defines: instrumented side builds for tools/ (e.g. -DTAMGCN_TRACE) of the core
+    library alone; the product is LIB."""
+    if out is None:
+        build_xmodal(force, verbose)
+        if not force and not needs_build():
+            return LIB
+    return _compile_and_link(sources(), out or LIB, '.o' if out is None else '.side.o', defines, verbose)
+
+
+def _compile_and_link(srcs, lib, osuffix, defines, verbose):
     objs = []
     procs = []
-    for s in sources():
-        o = os.path.splitext(s)[0] + ('.o' if out is None else '.side.o')
+    for s in srcs:
+        o = os.path.splitext(s)[0] + osuffix
         objs.append(o)
         cmd = [_hipcc(), f'--offload-arch={ARCH}', '-O3', '-std=c++17', '-fPIC', *[f'-D{d}' for d in defines], '-c', s, '-o', o]
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

@@ -17,6 +17,10 @@ backward is itself a registered op:
     tamgcn::feeder_transform(raw, offsets, rot, idx, parent, V, time_steps, center_joint, mode) -> clips   :85-130
     tamgcn::guidance_reduce(h, M) -> (intensity, pooled, minmax);  tamgcn::guidance_weights(intensity, minmax, joints, k) -> weights;
     tamgcn::guidance_apply(weights, rgb | None, frames, H, W, want_map) -> (rgb * map, map)                 visual.py:53-87
+    tamgcn::xmodal_head(f, f_rgb, W1, b1, bn_w, bn_b, running_mean, running_var, num_batches_tracked, W2, b2, Wc, bc, training,
+                        momentum, eps) -> (logits, saved...);  tamgcn::xmodal_head_backward(...) -> 10 gradients
+                                                 the cross-modal attention head, models/resnet_gcn_attention.py:60-70, :89-120; it updates the
+                                                 BatchNorm buffers in place, so its autograd node is XModalHeadFn (below)
 
     tamgcn::tcn_gcn_unit_eval(x, xpart, params, geom) -> (out, xpart)   the whole eval-mode TCN_GCN_unit (:266-284) for small
                                                  batches, BatchNorm folded; registered by tam_gcn_amd/f2.py with the engine that uses it
@@ -422,3 +426,125 @@ def _(weights, rgb, frames, H, W, want_map):
     N = weights.shape[0]
     out = weights.new_empty(0) if rgb is None else weights.new_empty(N, rgb.shape[1], H, W)
     return out, (weights.new_empty(N, 1, H, W) if want_map else weights.new_empty(0))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# cross-modal attention head (tam_gcn_amd/crossmodal.py; reference models/resnet_gcn_attention.py:60-70, :89-120): everything
+# between the pooled skeleton feature f (N, D) / the image map f_rgb (N, R, H, W) and the logits, on libtamgcn_xmodal.so
+# (include/tamgcn_xmodal.h) plus the core's head_fc.  Three new launches forward, four (five with d f) backward; the gated
+# copy of the map is never written.  Besides the logits the forward returns what the backward reads (cross_entropy_opts does the
+# same with g): pooled g, att, m (N, R), a1, xhat (N, Hd), invstd (Hd).
+# ---------------------------------------------------------------------------------------------------------------
+def _a16(t):
+    """contiguous and 16-byte aligned, as include/tamgcn_xmodal.h asks of everything but the map (a parameter that is a view into
+    a flat arena at an odd offset is copied)"""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _xm_dims(f, f_rgb, W1, W2, Wc, training):
+    if f.dim() != 2 or f_rgb.dim() != 4 or f_rgb.shape[0] != f.shape[0]:
+        raise ValueError(f'xmodal_head: f must be (N, D) and f_rgb (N, R, H, W) for the same N, got {tuple(f.shape)} and {tuple(f_rgb.shape)}')
+    N, D = f.shape
+    Hd, R, K = W1.shape[0], W2.shape[0], Wc.shape[0]
+    if tuple(W1.shape) != (Hd, D) or tuple(W2.shape) != (R, Hd) or tuple(Wc.shape) != (K, R) or f_rgb.shape[1] != R:
+        raise ValueError(f'xmodal_head: W1 {tuple(W1.shape)}, W2 {tuple(W2.shape)}, Wc {tuple(Wc.shape)} do not chain from D = {D} '
+                         f'to the R = {f_rgb.shape[1]} channels of f_rgb')
+    P = f_rgb.shape[2] * f_rgb.shape[3]
+    if D % 4 or Hd % 4 or R % 4 or min(D, Hd, R) < 4:
+        raise ValueError(f'xmodal_head: D = {D}, Hd = {Hd} and R = {R} must be positive multiples of 4')
+    if P < 1 or K < 1:
+        raise ValueError(f'xmodal_head: H * W = {P} and K = {K} must be at least 1')
+    if N == 1 and training:
+        raise ValueError(f'Expected more than 1 value per channel when training, got input size {torch.Size((N, Hd))}')
+    if not 1 <= N <= 1024:
+        raise ValueError(f'xmodal_head: N = {N} clips outside 1..1024')
+    if N * R * P >= 2 ** 31:
+        raise ValueError(f'xmodal_head: f_rgb has {N * R * P} elements, the limit is 2^31 - 1')
+    return N, D, Hd, R, P, K
+
+
+@torch.library.custom_op('tamgcn::xmodal_head', mutates_args=('running_mean', 'running_var', 'num_batches_tracked'))
+def xmodal_head(f: Tensor, f_rgb: Tensor, W1: Tensor, b1: Tensor, bn_w: Tensor, bn_b: Tensor, running_mean: Tensor, running_var: Tensor,
+                num_batches_tracked: Tensor, W2: Tensor, b2: Tensor, Wc: Tensor, bc: Tensor, training: bool, momentum: float,
+                eps: float) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import _xm_lib
+    N, D, Hd, R, P, K = _xm_dims(f, f_rgb, W1, W2, Wc, training)
+    for name, t in (('running_mean', running_mean), ('running_var', running_var)):
+        if not (t.is_contiguous() and t.data_ptr() % 16 == 0 and tuple(t.shape) == (Hd,)):
+            raise RuntimeError(f'xmodal_head: {name} must be a contiguous, 16-byte aligned ({Hd},) buffer: it is updated in place')
+    if num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1:
+        raise RuntimeError('xmodal_head: num_batches_tracked must be one int64')
+    lib, p, st = _xm_lib.load(), ops._ptr, ops._stream()
+    f, frgb = _a16(f), f_rgb.contiguous()                         # the map may start at any dword
+    a1, xhat = f.new_empty(N, Hd), f.new_empty(N, Hd)
+    mean, invstd = f.new_empty(Hd), f.new_empty(Hd)
+    att, m, g = f.new_empty(N, R), f.new_empty(N, R), ops.empty(N, R, like=f)
+    _xm_lib.check(lib.tamgcn_xm_hidden_fwd(p(f), p(_a16(W1)), p(_a16(b1)), p(_a16(bn_w)), p(_a16(bn_b)), p(running_mean), p(running_var),
+                                           p(num_batches_tracked), N, D, Hd, int(training), momentum, eps, p(a1), p(xhat), p(mean), p(invstd), st),
+                  'tamgcn_xm_hidden_fwd')
+    _xm_lib.check(lib.tamgcn_xm_gate_fwd(p(a1), p(_a16(W2)), p(_a16(b2)), N, Hd, R, p(att), st), 'tamgcn_xm_gate_fwd')
+    _xm_lib.check(lib.tamgcn_xm_pool_fwd(p(frgb), p(att), N, R, P, p(m), p(g), st), 'tamgcn_xm_pool_fwd')
+    return ops.head_fc_fwd(g, _c(Wc), _c(bc)), g, att, m, a1, xhat, invstd
+
+
+@xmodal_head.register_fake
+def _(f, f_rgb, W1, b1, bn_w, bn_b, running_mean, running_var, num_batches_tracked, W2, b2, Wc, bc, training, momentum, eps):
+    N, Hd, R = f.shape[0], W1.shape[0], W2.shape[0]
+    return (f.new_empty(N, Wc.shape[0]), f.new_empty(N, R), f.new_empty(N, R), f.new_empty(N, R), f.new_empty(N, Hd), f.new_empty(N, Hd),
+            f.new_empty(Hd))
+
+
+@torch.library.custom_op('tamgcn::xmodal_head_backward', mutates_args=())
+def xmodal_head_backward(dlogits: Tensor, f: Tensor, W1: Tensor, bn_w: Tensor, W2: Tensor, Wc: Tensor, g: Tensor, att: Tensor, m: Tensor,
+                         a1: Tensor, xhat: Tensor, invstd: Tensor, H: int, W: int, training: bool, need_f: bool,
+                         need_f_rgb: bool) -> list[Tensor]:
+    """[df, df_rgb, dW1, db1, dbn_w, dbn_b, dW2, db2, dWc, dbc]; df / df_rgb have 0 elements when not asked for"""
+    from . import _xm_lib
+    lib, p, st = _xm_lib.load(), ops._ptr, ops._stream()
+    N, D = f.shape
+    Hd, R, P = W1.shape[0], W2.shape[0], H * W
+    f, W1, W2 = _a16(f), _a16(W1), _a16(W2)
+    dWc, dbc, dg = ops.head_fc_bwd(_c(dlogits), g, _c(Wc))
+    dz2 = f.new_empty(N, R)
+    df_rgb = f.new_empty(N, R, H, W) if need_f_rgb else f.new_empty(0)
+    _xm_lib.check(lib.tamgcn_xm_pool_bwd(p(dg), p(m), p(att), N, R, P, p(dz2), p(df_rgb) if need_f_rgb else None, st), 'tamgcn_xm_pool_bwd')
+    dW2, db2, da1 = torch.empty_like(W2), f.new_empty(R), f.new_empty(N, Hd)
+    _xm_lib.check(lib.tamgcn_xm_gate_bwd(p(dz2), p(a1), p(W2), N, Hd, R, p(dW2), p(db2), p(da1), st), 'tamgcn_xm_gate_bwd')
+    dgam, dbet, dW1, db1, dz1 = f.new_empty(Hd), f.new_empty(Hd), torch.empty_like(W1), f.new_empty(Hd), f.new_empty(N, Hd)
+    df = f.new_empty(N, D) if need_f else f.new_empty(0)
+    _xm_lib.check(lib.tamgcn_xm_hidden_bwd(p(da1), p(a1), p(xhat), p(invstd), p(_a16(bn_w)), p(f), p(W1), N, D, Hd, int(training), p(dgam), p(dbet),
+                                           p(dW1), p(db1), p(dz1), p(df) if need_f else None, st), 'tamgcn_xm_hidden_bwd')
+    return [df, df_rgb, dW1, db1, dgam, dbet, dW2, db2, dWc, dbc]
+
+
+@xmodal_head_backward.register_fake
+def _(dlogits, f, W1, bn_w, W2, Wc, g, att, m, a1, xhat, invstd, H, W, training, need_f, need_f_rgb):
+    N, Hd, R = f.shape[0], W1.shape[0], W2.shape[0]
+    return [torch.empty_like(f) if need_f else f.new_empty(0), f.new_empty(N, R, H, W) if need_f_rgb else f.new_empty(0), torch.empty_like(W1),
+            f.new_empty(Hd), f.new_empty(Hd), f.new_empty(Hd), torch.empty_like(W2), f.new_empty(R), torch.empty_like(Wc),
+            f.new_empty(Wc.shape[0])]
+
+
+class XModalHeadFn(torch.autograd.Function):
+    """logits = XModalHeadFn.apply(f, f_rgb, W1, ..., eps): the autograd node of tamgcn::xmodal_head.  torch.library refuses
+    register_autograd on an operator that mutates its arguments, and this one updates the three BatchNorm buffers in its first
+    kernel -- so, as for the training block nodes above, the node is an autograd.Function around the two registered ops.  d f and
+    d f_rgb are computed only when those inputs require them."""
+
+    @staticmethod
+    def forward(ctx, f, f_rgb, W1, b1, bn_w, bn_b, running_mean, running_var, num_batches_tracked, W2, b2, Wc, bc, training, momentum, eps):
+        logits, *saved = torch.ops.tamgcn.xmodal_head(f, f_rgb, W1, b1, bn_w, bn_b, running_mean, running_var, num_batches_tracked, W2, b2,
+                                                      Wc, bc, training, momentum, eps)
+        ctx.save_for_backward(f, W1, bn_w, W2, Wc, *saved)
+        ctx.H, ctx.W, ctx.training = f_rgb.shape[2], f_rgb.shape[3], training
+        return logits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits):
+        need_f, need_f_rgb = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        df, df_rgb, dW1, db1, dgam, dbet, dW2, db2, dWc, dbc = torch.ops.tamgcn.xmodal_head_backward(
+            dlogits, *ctx.saved_tensors, ctx.H, ctx.W, ctx.training, need_f, need_f_rgb)
+        return (df if need_f else None, df_rgb if need_f_rgb else None, dW1, db1, dgam, dbet, None, None, None, dW2, db2, dWc, dbc,
+                None, None, None)
