@@ -1,4 +1,4 @@
-"""Build libtamgcn.so and its extension library libtamgcn_xmodal.so (HIP, gfx950 only) in-tree with hipcc.
+"""Build libtamgcn.so and its extension libraries libtamgcn_xmodal.so and libtamgcn_rgb.so (HIP, gfx950 only) in-tree with hipcc.
 
     python -m tam_gcn_amd.build [--force]
 
@@ -15,6 +15,9 @@ LIB = os.path.join(HERE, 'libtamgcn.so')
 # the cross-modal head (crossmodal.py): a library and a header (include/tamgcn_xmodal.h) of its own, the core ABI stays as it is
 XM_SRC = ['xm_lib.hip', 'xm_hidden.hip', 'xm_gate.hip', 'xm_pool.hip']
 XM_LIB = os.path.join(HERE, 'libtamgcn_xmodal.so')
+# the RGB feeder (feeder/rgb_feeder.py): likewise a library and a header (include/tamgcn_rgb.h) of its own
+RGB_SRC = ['rgb_lib.hip', 'rgb_resize.hip', 'rgb_batch.hip']
+RGB_LIB = os.path.join(HERE, 'libtamgcn_rgb.so')
 ARCH = 'gfx950'
 
 
@@ -59,11 +62,34 @@ def build_xmodal(force=False, verbose=True):
     return _compile_and_link(xm_sources(), XM_LIB, '.o', (), verbose)
 
 
+def rgb_sources():
+    return [os.path.join(HERE, 'csrc', 'rgb', s) for s in RGB_SRC]
+
+
+def needs_build_rgb():
+    if not os.path.exists(RGB_LIB):
+        return True
+    rgb = os.path.join(HERE, 'csrc', 'rgb')
+    deps = rgb_sources() + [os.path.join(rgb, h) for h in os.listdir(rgb) if h.endswith('.h')] + \
+        [os.path.join(HERE, 'csrc', 'common.h'), os.path.join(HERE, 'csrc', 'feeder_common.h'),
+         os.path.join(HERE, '..', 'include', 'tamgcn.h'), os.path.join(HERE, '..', 'include', 'tamgcn_rgb.h')]
+    t = os.path.getmtime(RGB_LIB)
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_rgb(force=False, verbose=True):
+    """libtamgcn_rgb.so from csrc/rgb/*.hip."""
+    if not force and not needs_build_rgb():
+        return RGB_LIB
+    return _compile_and_link(rgb_sources(), RGB_LIB, '.o', (), verbose)
+
+
 def build(force=False, verbose=True, out=None, defines=()):
-    """Both libraries; returns LIB.  out/defines: instrumented side builds for tools/ (e.g. -DTAMGCN_TRACE) of the core
+    """The three libraries; returns LIB.  out/defines: instrumented side builds for tools/ (e.g. -DTAMGCN_TRACE) of the core
     library alone; the product is LIB."""
     if out is None:
         build_xmodal(force, verbose)
+        build_rgb(force, verbose)
         if not force and not needs_build():
             return LIB
     return _compile_and_link(sources(), out or LIB, '.o' if out is None else '.side.o', defines, verbose)

@@ -21,7 +21,8 @@ the reference's draws).  ``batch_device(indices)`` takes the indices as an int64
 (``tamgcn_clip_draw``: Philox4x32-10 keyed by ``seed``, counted by a call counter that lives on the device; the stream is
 defined in include/tamgcn.h and INTEGRATION.md): no host work, no synchronisation, capturable -- ``GraphedBatch``,
 ``CapturedEval`` and ``CapturedStep`` take this feeder as they take the N-UCLA one.  ``normalization=True`` is accepted and
-does nothing, as in the reference (``get_mean_map`` at :34-35 is empty).  RGB loading is the other modality: not here.
+does nothing, as in the reference (``get_mean_map`` at :34-35 is empty).  RGB loading is the other modality: it lives in
+``feeder/rgb_feeder.py`` (``RGBFeeder``), and ``FusionFeeder`` there pairs this feeder with it for the fusion batch.
 
 ``p_interval=`` switches to a second pipeline, the one CTR-GCN was published with for NTU-style arrays (its
 ``feeders/tools.py``: ``valid_crop_resize`` and ``random_rot``), in place of steps 1 to 3:
